@@ -2,14 +2,18 @@
 """bench.py — headline benchmark of the MI355X hot path (BASELINE.json metric, configs[1]).
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR      # + the last step's loss and parameters as .npy
+  python bench.py --gpus 1 --full                                         # + every secondary leg below
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 A "step" is one train step of the Conv3D PV-yield model (forward + NMAE loss + backward + Adam [+ gradient
 exchange over RCCL when N > 1]) on one batch of synthetic PV-site crop stacks [B, 11, 18, 64, 64]
 (12 observed + 6 forecast frames) already resident in HBM.  Per-GPU batch is fixed
-(weak scaling).  Rank 0 prints ONE JSON line with the whole-job samples/s plus, at N = 1 (all of it OUTSIDE the timed
-region, GPU legs first, the CPU leg last):
+(weak scaling).  A plain run sets up, warms up, times K steps, writes --dump-outputs if asked, and rank 0 prints ONE JSON
+line with the whole-job samples/s and ms_per_step.  With --full the line also carries the in-process device calibration, the
+clocks sampled during the timed steps, under N > 1 the other fc1 exchanges (grad_sync_modes) and, at N = 1 (all of it
+OUTSIDE the timed region, GPU legs first, the CPU leg last):
   roofline      the single largest kernel of the step (fc1's fused wgrad + Adam pass, HBM-bound) with the Conv3D
                 implicit-GEMM family (MFMA-bound) beside it under "mfma_conv3d"; every duration is measured IN THE STEP
                 with HIP events around each launch on the launching stream (a few extra, instrumented steps);
@@ -23,6 +27,7 @@ region, GPU legs first, the CPU leg last):
   cpu_baseline  those oracle steps, timed, at the benched batch (identical arithmetic to the reference's Lightning path).
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -118,6 +123,31 @@ TIMED_OPS = ("conv3d_fwd_bf16", "conv3d_fwd_bf16_f32in", "conv3d_bwd_weight_bf16
              "linear_wgrad_dx_adam_bf16",
              "linear_fwd_bf16", "linear_bwd_bf16", "repack_gate_ncdhw_to_ndhwc_bf16", "adam_step_multi",
              "conv3d_pack_weights_multi")
+
+
+DUMP_SAMPLE = 1 << 22      # --dump-outputs: a parameter with more elements is written as a fixed, seeded sample (16 MB in f32)
+
+
+def dump_outputs(out_dir, model, opt, loss, distributed, rank):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the loss and every parameter Adam left
+    (state_dict(): fc1.weight in the reference's column order) -- as float32 DIR/<name>.npy.  A parameter of more than
+    DUMP_SAMPLE elements (fc1.weight, 128 M) is written as DIR/<name>.sample.npy: the values at DUMP_SAMPLE flat indices drawn
+    once from a generator seeded with 518, in ascending order.  Under N > 1 the sharded parameters are gathered first
+    (collective) and rank 0 writes."""
+    import numpy as np
+    if distributed:
+        opt.consolidate_sharded()
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    for name, t in model.state_dict().items():
+        t = t.detach().float()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(518)).sort().values
+            np.save(os.path.join(out_dir, name + ".sample.npy"), t.reshape(-1)[idx.to(t.device)].cpu().numpy())
+        else:
+            np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
 
 
 def settle():
@@ -1144,10 +1174,17 @@ def main():
                          "default 0 = weak scaling with --batch samples per GPU")
     ap.add_argument("--history-minutes", type=int, default=55, help="55 -> T=18 (12 observed + 6 forecast frames)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU leg (matched training + cpu_baseline)")
-    ap.add_argument("--no-roofline", action="store_true", help="skip every secondary GPU leg")
-    ap.add_argument("--no-extras", action="store_true", help="keep roofline but skip config 3, fp32 and the other models")
-    ap.add_argument("--no-calibration", action="store_true", help="skip the in-process device calibration before the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: device calibration, clocks during the timed steps, the other fc1 exchanges "
+                         "(N > 1), roofline, config 3, fp32, other models, sweeps, matched validation and the CPU baselines "
+                         "(N = 1); the --no-* options below trim this set")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's loss and the parameters it left as float32 DIR/<name>.npy "
+                         "(fc1.weight as a fixed, seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU leg (matched training + cpu_baseline)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip every secondary GPU leg")
+    ap.add_argument("--no-extras", action="store_true", help="--full: keep roofline but skip config 3, fp32 and the other models")
+    ap.add_argument("--no-calibration", action="store_true", help="--full: skip the in-process device calibration before the timed steps")
     ap.add_argument("--overlap-update", action="store_true",
                     help="N = 1: launch fc1's fused wgrad+Adam from backward on a side stream (under the conv backward)")
     ap.add_argument("--f32-grads", action="store_true", help="N > 1: all-reduce fc1's gradient in f32 instead of bf16")
@@ -1161,8 +1198,8 @@ def main():
                          "(config.parallelism, config.collectives); a mode asked for BY NAME is never replaced (exit non-zero "
                          "instead, unless --allow-demotion)")
     ap.add_argument("--only-requested-mode", action="store_true",
-                    help="N > 1: time the requested exchange only (default: the other modes are timed afterwards in the same "
-                         "invocation and reported under grad_sync_modes; `value` is always the requested mode's)")
+                    help="N > 1, --full: time the requested exchange only (otherwise the other modes are timed afterwards in the "
+                         "same invocation and reported under grad_sync_modes; `value` is always the requested mode's)")
     ap.add_argument("--other-modes-budget", type=float, default=float(os.environ.get("PV_BENCH_OTHER_MODES_BUDGET_S", "120")),
                     help="N > 1: seconds the leg that times the OTHER fc1 exchanges may take; past it the requested mode's line is "
                          "printed with what the leg has recorded and the process ends (a collective one rank never enters cannot be interrupted)")
@@ -1170,6 +1207,8 @@ def main():
                     help="N > 1: accept a simpler gradient-exchange mode than the requested one when its trial step fails "
                          "(default: exit non-zero -- a scaling number on another exchange is not the number asked for)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from predict_pv_yield_amd import distributed as D
     from predict_pv_yield_amd.models.conv3d.model import Model
@@ -1239,7 +1278,7 @@ def main():
     # what THIS device sustains (copy rate, bare bf16 matrix-instruction rate), in this process, right before the timed steps:
     # one binary runs 1.52-1.71 ms per step across a pool's boxes, so fractions are reported against the spec peaks AND these
     calibration = None
-    if args.warmup > 0 and not args.no_calibration:
+    if args.full and args.warmup > 0 and not args.no_calibration:
         from predict_pv_yield_amd import hip_ops as K
         calibration = K.device_calibration()
         for _ in range(3):          # back into the step's own rhythm (allocator, clocks) before timing
@@ -1247,8 +1286,8 @@ def main():
     if distributed:
         torch.distributed.barrier()
     torch.cuda.synchronize()
-    clocks = ClockSampler()
-    with clocks:
+    clocks = ClockSampler() if args.full else None
+    with clocks or contextlib.nullcontext():
         t0 = time.perf_counter()
         for _ in range(args.steps):
             last = step()
@@ -1260,6 +1299,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, opt, last, distributed, rank)
     last = float(last.detach())
 
     # N > 1: the other exchanges of fc1, timed the same way in the SAME invocation (the first multi-GPU run
@@ -1282,7 +1323,7 @@ def main():
                        "parallelism": f"dp{world} ({grad_sync_mode})" if world > 1 else "single",
                        "collectives": collectives_info(world, requested_mode if distributed else None, grad_sync_mode)},
             "device_calibration": calibration,
-            "device_clocks_during_timed_steps": clocks.summary(),
+            "device_clocks_during_timed_steps": clocks.summary() if clocks else None,
         }
 
     def modes_record():
@@ -1294,7 +1335,7 @@ def main():
                                       "exchange_bytes_per_rank_and_step": exchange_bytes(grad_sync_mode, world, b, model)}},
                     **other_modes)
 
-    if distributed and not args.only_requested_mode:
+    if distributed and args.full and not args.only_requested_mode:
         # A collective that one rank never enters cannot be interrupted from inside: a timer thread prints the requested mode's
         # line with what the leg has recorded so far and ends the process (exit code 0 -- `value` was measured; never an exec).
         import threading
@@ -1385,7 +1426,7 @@ def main():
             "train_nmae_last_step": round(last, 6),
             "whole_step_frac_of_bf16_mfma_peak": round(value / world * (23.37e9 if t_frames == 18 else 25.27e9) / MFMA_BF16_PEAK, 4),
         })
-        if not args.no_roofline and world == 1:
+        if args.full and not args.no_roofline and world == 1:
             if args.precision == "bf16":
                 out["roofline"] = measure_step_rooflines(step, model, b, t_frames)
                 if "avg_launch_ms" in out["roofline"]:
@@ -1463,7 +1504,7 @@ def main():
                 settle()
         else:
             out["roofline"] = distributed_roofline or None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["val_nmae"], out["cpu_baseline"] = matched_validation_and_cpu_baseline(dev, args.history_minutes)
             if out.get("roofline"):      # scalars the driver's record keeps
                 out["roofline"]["val_nmae_bf16_minus_fp32"] = out["val_nmae"]["paired_bf16_minus_fp32"]["mean"]

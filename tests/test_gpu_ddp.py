@@ -291,7 +291,7 @@ def test_ksharded_rccl_branches_on_one_rank(device, tmp_path):
 
 def test_bench_times_every_exchange_mode_in_one_invocation(device):
     """bench.py --gpus N (N > 1) times the requested exchange of fc1 AND the others in the same invocation --
-    two gloo ranks on the one GPU here, the full 128 M-parameter fc1, default flags (--grad-sync auto: K-sharded first): the
+    two gloo ranks on the one GPU here, the full 128 M-parameter fc1, --full (--grad-sync auto: K-sharded first): the
     line's `value` is the mode in force's and says so, `grad_sync_modes` carries the row-sharded form, the bf16 all-reduce and the
     f32 all-reduce with their own ms_per_step, collectives and bytes."""
     import json
@@ -302,7 +302,7 @@ def test_bench_times_every_exchange_mode_in_one_invocation(device):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), PV_DIST_BACKEND="gloo", PV_SINGLE_DEVICE="1", PV_DIST_TIMEOUT_S="900")
         procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "4", "--steps", "1",
-                                       "--warmup", "1", "--no-cpu-baseline"], env=env,
+                                       "--warmup", "1", "--full", "--no-cpu-baseline"], env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=root))
     outs = [p.communicate(timeout=1500) for p in procs]
     for p, (o, e) in zip(procs, outs):
@@ -341,7 +341,7 @@ def test_bench_keeps_the_requested_modes_line_when_another_mode_hangs(device):
                    MASTER_PORT=str(port), PV_DIST_BACKEND="gloo", PV_SINGLE_DEVICE="1", PV_DIST_TIMEOUT_S="900",
                    PV_BENCH_HANG_IN_MODE="bf16")
         procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "4", "--steps", "1",
-                                       "--warmup", "1", "--no-roofline", "--no-cpu-baseline", "--other-modes-budget", "60"], env=env,
+                                       "--warmup", "1", "--full", "--no-roofline", "--no-cpu-baseline", "--other-modes-budget", "60"], env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=root))
     outs = [p.communicate(timeout=600) for p in procs]
     for p, (o, e) in zip(procs, outs):

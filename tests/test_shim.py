@@ -17,7 +17,8 @@ from predict_pv_yield_amd.data.fake import FakeDataConfiguration, FakeDataset
 from predict_pv_yield_amd.utils import extras, load_config, print_config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_CONFIGS = "/root/reference/configs"
+# the reference's yaml files that the tests below compose, as data (tests/golden/make_reference_configs.py)
+REF_CONFIGS = os.path.join(ROOT, "tests", "golden", "reference_configs")
 
 
 def test_compose_defaults_and_experiment_overlay():
@@ -45,7 +46,6 @@ def test_oc_env_and_missing_env(monkeypatch, tmp_path):
     assert cfg.a == "hello" and cfg.b == "fallback" and cfg.c == "hello/x"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIGS), reason="reference tree not present (GPU box)")
 def test_reference_config_tree_drives_this_package():
     """The reference's own yaml files compose and instantiate: `_target_` paths resolve through the alias table."""
     cfg = H.compose(REF_CONFIGS, "config", ["logger=csv", "experiment=conv3d", "datamodule.fake_data=true",
@@ -205,7 +205,6 @@ def test_baseline_model_forward_is_persistence():
     assert torch.equal(y[:, 0], b["gsp"]["gsp_yield"][:, -5, 0]) and torch.equal(y[:, 0], y[:, 3])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONFIGS), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name,module,cls", [
     ("conv3d_sat_nwp", "predict_pv_yield_amd.models.conv3d.model_sat_nwp", "Model"),
     ("conv3d_nwp", "predict_pv_yield_amd.models.conv3d.model_nwp", "Model"),

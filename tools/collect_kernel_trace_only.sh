@@ -1,5 +1,5 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r03kt; mkdir -p $O; cd $R
-python3 bench.py --no-extras --no-cpu-baseline > $O/bench_noextras.json 2> $O/bench.err
+python3 bench.py --full --no-extras --no-cpu-baseline > $O/bench_noextras.json 2> $O/bench.err
 cd /tmp; export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o p -- python3 $R/bench.py --no-roofline --no-cpu-baseline --no-extras > $O/kt.log 2>&1
 cd $R

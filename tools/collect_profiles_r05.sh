@@ -19,7 +19,7 @@ cp $(find $O/kt -name "p_kernel_stats.csv" | head -1) $O/bench_conv3d_B32_kernel
 cp $(find $O/flow -name "p_kernel_stats.csv" | head -1) $O/flow_pipeline_B32_kernel_stats.csv
 # 4. the default bench line, reading the counter files just made (bench.py looks under profiles/r05/)
 cp $O/pmc_hbm_traffic_bench_B32.json $O/pmc_flow_*.json profiles/r05/
-python3 bench.py > $O/bench_conv3d_B32_default_run.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_conv3d_B32_default_run.json 2> $O/bench_default.err
 python3 tools/time_fp32_step.py > $O/fp32_step_kernels.txt 2>&1
 bash tools/trace_fp32_step.sh > /dev/null 2>&1; cp gpurun_out/fp32_trace/kernel_stats.txt $O/fp32_step_kernel_stats.txt
 find $O -name "*kernel_trace.csv" -size +20M -delete

@@ -1,5 +1,5 @@
 for f in "" "--no-calibration" "" "--no-calibration"; do
-python bench.py --no-extras --no-cpu-baseline $f 2>/dev/null | python -c "
+python bench.py --full --no-extras --no-cpu-baseline $f 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 k=[v['us_per_launch'] for n,v in r['kernels'].items() if 'f32in' in n][0]
