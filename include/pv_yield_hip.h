@@ -195,6 +195,44 @@ int pv_conv3d_general_bwd_weight_workspace_bytes(const pv_conv3d_geom* d, size_t
 int pv_conv3d_general_bwd_weight_f32(const float* x, const float* dy, const float* y_relu_mask, float* dw,
                                      float* dbias, const pv_conv3d_geom* d, void* ws, size_t ws_bytes,
                                      void* stream);
+/* ---- Conv2d 3x3, stride 1, no padding, exact f32 (experiments/002_cnn_processes_single_sat_image_then_rnn.py) ---- */
+/* Images [n][c][h][w] (NCHW) unless stated; weights [c_out][c_in][3][3]; outputs [n][c][h - 2][w - 2].  Products on
+ * the f32 matrix cores with f32 accumulation.  Widths up to 96. */
+/* replaces: F.relu(self.sat_conv1(torch.cat((sat_data.permute(0, 3, 1, 2), center_marker, x_coords, y_coords, pixel_x,
+ * pixel_y), dim=1))), experiments/002_cnn_processes_single_sat_image_then_rnn.py:93-95, 140-162, 180-212.
+ * sat[n][h][w][12] is read in its native channels-last layout; x_coords[n / t_per_example][w] and
+ * y_coords[n / t_per_example][h] (metres); the 17 input channels (12 satellite, centre marker, (x - 309000) / 316387.42,
+ * (y - 519000) / 406454.18, (col - 64) / 37, (row - 64) / 37) are built while staged, never stored.  Bias and ReLU
+ * fused; c_out = 32. */
+int pv_conv2d_coords_fwd_f32(const float* sat, const float* x_coords, const float* y_coords, const float* w,
+                             const float* bias, float* y, int32_t n, int32_t t_per_example, int32_t h_in, int32_t w_in,
+                             int32_t c_out, void* stream);
+/* replaces: self.sat_conv2 / self.sat_conv3 (+ F.relu if relu), experiments/002...py:96-101, 209-211.  c_in = 32,
+ * c_out = 32 or 4; bias may be NULL. */
+int pv_conv2d_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                      int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of sat_conv2 / sat_conv3 (autograd of experiments/002...py:210-211).  dy[n][c_out][h-2][w-2]
+ * is the gradient at the layer's output, zeroed where dy_gate <= 0 (the layer's own ReLU output; NULL = dy is already the
+ * pre-activation gradient); dx[n][c_in][h][w] is zeroed where x_gate <= 0 (the layer input when it is the ReLU output of
+ * the layer below: dx is then that layer's pre-activation gradient; NULL = ungated).  (h, w) = the layer's input extent. */
+int pv_conv2d_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                           int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+/* bytes of the weight-gradient workspace (one partial [c_out][c_in * 9 + 1] per slab of images); c_in = 17 for the
+ * coords layer, else 32 */
+int pv_conv2d_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                         size_t* bytes);
+/* replaces: the weight and bias gradients of sat_conv2 / sat_conv3.  dw [c_out][c_in][3][3] and dbias [c_out] are
+ * overwritten; slab partials summed in slab order (deterministic, no atomics).  dy_gate as for bwd_data.  c_out = 4 runs
+ * pv_conv3d_general_bwd_weight_f32 as a 1x3x3 conv (faster there; the workspace query sizes it). */
+int pv_conv2d_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias, int32_t n,
+                             int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
+                             void* stream);
+/* replaces: the weight and bias gradients of sat_conv1, re-synthesising its 17-channel input as the forward does; dy is
+ * the pre-activation gradient (pv_conv2d_bwd_data_f32 of sat_conv2 with x_gate = sat_conv1's output). */
+int pv_conv2d_coords_bwd_weight_f32(const float* sat, const float* x_coords, const float* y_coords, const float* dy,
+                                    float* dw, float* dbias, int32_t n, int32_t t_per_example, int32_t h_in,
+                                    int32_t w_in, int32_t c_out, void* ws, size_t ws_bytes, void* stream);
+
 /* MaxPool3d over x[B*C planes][Ti,Hi,Wi]; argmax (may be NULL) = flat winner offset inside the plane stack, first
  * maximum wins, NaN propagates (torch CPU semantics).  bwd overwrites dx by gathering dy through argmax. */
 int pv_maxpool3d_fwd_f32(const float* x, float* y, int32_t* argmax, const pv_conv3d_geom* d, void* stream);

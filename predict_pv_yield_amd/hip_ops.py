@@ -1007,6 +1007,129 @@ def conv3d_general_bwd_weight_f32(x, dy, y_mask, weight_shape, stride=1, padding
     return dw, db
 
 
+# ------------------------------------------------------------------------------------------------
+# Conv2d 3x3 "valid" (experiments/002_cnn_processes_single_sat_image_then_rnn.py), exact f32
+# ------------------------------------------------------------------------------------------------
+def _f32_contig(*ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise TypeError("conv2d kernels take contiguous float32 tensors")
+
+
+def _shape_check(ok, who, msg):
+    if not ok:
+        raise ValueError(f"{who}: {msg}")
+
+
+def _check_coords(who, sat, x_coords, y_coords, t_per_example):
+    n, h, w, c = sat.shape
+    _shape_check(c == 12 and t_per_example > 0 and n % t_per_example == 0, who,
+                 f"sat [N, H, W, 12] with N a multiple of t_per_example={t_per_example}, got {tuple(sat.shape)}")
+    b = n // t_per_example
+    _shape_check(tuple(x_coords.shape) == (b, w) and tuple(y_coords.shape) == (b, h), who,
+                 f"x_coords [{b}, {w}] and y_coords [{b}, {h}] expected, got {tuple(x_coords.shape)} / {tuple(y_coords.shape)}")
+
+
+def _check_bias(who, bias, c_out):
+    if bias is not None and tuple(bias.shape) != (c_out,):
+        raise ValueError(f"{who}: bias [{c_out}] expected, got {tuple(bias.shape)}")
+
+
+def conv2d_coords_fwd_f32(sat, x_coords, y_coords, weight, bias, t_per_example):
+    """relu(conv2d(cat(sat.permute(0, 3, 1, 2), 5 synthesised channels), weight) + bias) with sat [N, H, W, 12],
+    x_coords [N / t, W], y_coords [N / t, H]: the 17-channel input is built inside the kernel.  Returns [N, C_out, H-2, W-2]."""
+    _check_coords("conv2d_coords_fwd_f32", sat, x_coords, y_coords, t_per_example)
+    n, h, w, c = sat.shape
+    _shape_check(weight.dim() == 4 and tuple(weight.shape[1:]) == (17, 3, 3), "conv2d_coords_fwd_f32",
+                 f"weight [C_out, 17, 3, 3] expected, got {tuple(weight.shape)}")
+    co = weight.shape[0]
+    _check_bias("conv2d_coords_fwd_f32", bias, co)
+    require_cuda(sat, x_coords, y_coords, weight, bias)
+    _f32_contig(sat, x_coords, y_coords, weight, bias)
+    y = torch.empty((n, co, h - 2, w - 2), dtype=torch.float32, device=sat.device)
+    check(get_lib().pv_conv2d_coords_fwd_f32(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(weight), ptr(bias), ptr(y), n,
+                                             t_per_example, h, w, co, current_stream_ptr()), "pv_conv2d_coords_fwd_f32")
+    return y
+
+
+def conv2d_fwd_f32(x, weight, bias, relu=True):
+    n, ci, h, w = x.shape
+    _shape_check(weight.dim() == 4 and tuple(weight.shape[1:]) == (ci, 3, 3), "conv2d_fwd_f32",
+                 f"weight [C_out, {ci}, 3, 3] expected for x {tuple(x.shape)}, got {tuple(weight.shape)}")
+    co = weight.shape[0]
+    _check_bias("conv2d_fwd_f32", bias, co)
+    require_cuda(x, weight, bias)
+    _f32_contig(x, weight, bias)
+    y = torch.empty((n, co, h - 2, w - 2), dtype=torch.float32, device=x.device)
+    check(get_lib().pv_conv2d_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, int(relu),
+                                      current_stream_ptr()), "pv_conv2d_fwd_f32")
+    return y
+
+
+def conv2d_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of a 3x3 valid conv; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
+    n, ci, h, w = x_shape
+    who = "conv2d_bwd_data_f32"
+    _shape_check(weight.dim() == 4 and tuple(weight.shape[1:]) == (ci, 3, 3), who,
+                 f"weight [C_out, {ci}, 3, 3] expected for x {tuple(x_shape)}, got {tuple(weight.shape)}")
+    y_shape = (n, weight.shape[0], h - 2, w - 2)
+    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
+                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
+    require_cuda(dy, dy_gate, weight, x_gate)
+    _f32_contig(dy, dy_gate, weight, x_gate)
+    dx = torch.empty(x_shape, dtype=torch.float32, device=dy.device)
+    check(get_lib().pv_conv2d_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci,
+                                           weight.shape[0], h, w, current_stream_ptr()), "pv_conv2d_bwd_data_f32")
+    return dx
+
+
+def _conv2d_wgrad_ws(n, ci, co, h, w, device):
+    nbytes = ctypes.c_size_t(0)
+    check(get_lib().pv_conv2d_bwd_weight_workspace_bytes(n, ci, co, h, w, ctypes.byref(nbytes)),
+          "pv_conv2d_bwd_weight_workspace_bytes")
+    return _workspace("conv2d_wgrad", nbytes.value, device), nbytes.value
+
+
+def conv2d_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw, dbias) of a 3x3 valid conv; deterministic (fixed slab split over images, slabs summed in order)."""
+    n, ci, h, w = x.shape
+    co = weight_shape[0]
+    y_shape = (n, co, h - 2, w - 2)
+    _shape_check(tuple(weight_shape) == (co, ci, 3, 3) and tuple(dy.shape) == y_shape
+                 and (dy_gate is None or tuple(dy_gate.shape) == y_shape), "conv2d_bwd_weight_f32",
+                 f"weight {(co, ci, 3, 3)} and dy / dy_gate {y_shape} expected for x {tuple(x.shape)}, got "
+                 f"{tuple(weight_shape)} / {tuple(dy.shape)}")
+    require_cuda(x, dy, dy_gate)
+    _f32_contig(x, dy, dy_gate)
+    ws, nbytes = _conv2d_wgrad_ws(n, ci, co, h, w, x.device)
+    dw = torch.empty(tuple(weight_shape), dtype=torch.float32, device=x.device)
+    db = torch.empty((co,), dtype=torch.float32, device=x.device)
+    check(get_lib().pv_conv2d_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, ptr(ws),
+                                             nbytes, current_stream_ptr()), "pv_conv2d_bwd_weight_f32")
+    return dw, db
+
+
+def conv2d_coords_bwd_weight_f32(sat, x_coords, y_coords, dy, t_per_example, weight_shape):
+    """(dw, dbias) of conv2d_coords_fwd_f32's conv from its pre-activation gradient dy, re-synthesising the input."""
+    who = "conv2d_coords_bwd_weight_f32"
+    _check_coords(who, sat, x_coords, y_coords, t_per_example)
+    n, h, w, _ = sat.shape
+    co = weight_shape[0]
+    _shape_check(tuple(weight_shape) == (co, 17, 3, 3) and tuple(dy.shape) == (n, co, h - 2, w - 2), who,
+                 f"weight {(co, 17, 3, 3)} and dy {(n, co, h - 2, w - 2)} expected, got {tuple(weight_shape)} / "
+                 f"{tuple(dy.shape)}")
+    require_cuda(sat, x_coords, y_coords, dy)
+    _f32_contig(sat, x_coords, y_coords, dy)
+    ws, nbytes = _conv2d_wgrad_ws(n, 17, co, h, w, sat.device)
+    dw = torch.empty(tuple(weight_shape), dtype=torch.float32, device=sat.device)
+    db = torch.empty((co,), dtype=torch.float32, device=sat.device)
+    check(get_lib().pv_conv2d_coords_bwd_weight_f32(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(dy), ptr(dw), ptr(db), n,
+                                                    t_per_example, h, w, co, ptr(ws), nbytes, current_stream_ptr()),
+          "pv_conv2d_coords_bwd_weight_f32")
+    return dw, db
+
+
 def maxpool3d_fwd_f32(x, kernel=3, stride=None, padding=0):
     require_cuda(x)
     b, c, t, h, w = x.shape
