@@ -62,10 +62,10 @@ def broadcast_parameters(module: torch.nn.Module, src: int = 0) -> None:
     """DDP's initial parameter broadcast from rank 0."""
     if not is_distributed():
         return
+    from .functional import drop_derived_copies
     for t in list(module.parameters()) + list(module.buffers()):
         dist.broadcast(t.data, src=src)
-        if hasattr(t, "_pv_bf16_shadow"):
-            del t._pv_bf16_shadow  # stale after the broadcast; rebuilt lazily
+        drop_derived_copies(t)     # (a write through .data leaves _version alone: the cached operand copies are rebuilt lazily)
 
 
 def all_reduce_gradients(module: torch.nn.Module, average: bool = False) -> None:

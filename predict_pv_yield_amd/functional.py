@@ -147,6 +147,15 @@ def split2_conv_weight(weight: torch.Tensor):
     return cache[1]
 
 
+def drop_derived_copies(p: torch.Tensor) -> None:
+    """Forget every operand copy derived from p's value and cached on it (conv fragment images, the f16x2 split, the bf16
+    shadow): each is rebuilt from p on its next use.  For writes that `_version` cannot see (through `.data` or raw pointers).
+    The fc1 column shard (`_pv_kshard`) is optimiser state, not a copy: HipAdam owns it."""
+    for name in ("_pv_packed", "_pv_split2", "_pv_bf16_shadow", "_pv_bf16_shadow_version"):
+        if getattr(p, name, None) is not None:
+            setattr(p, name, None)
+
+
 def refresh_packed_conv_weights(params) -> None:
     """Re-pack, in one launch, every cached fragment image of the given (just updated) conv weights."""
     jobs = []
@@ -414,8 +423,22 @@ def conv3d_relu_bf16(xp, weight, bias, c_in, padding=(0, 0, 0), relu=True, y_ncd
     return (y, mask) if want_relu_mask else y
 
 
+def _recut_kshard_weight(weight: torch.Tensor, ks: dict) -> None:
+    """torch changed fc1's full parameter (model.load_state_dict, an in-place edit) after HipAdam cut this rank's column shard
+    from it: the shard's weight and operand copy take this rank's columns of the new value, in place (the moments and the step
+    stay the optimiser's, as in every other mode)."""
+    with torch.no_grad():
+        ks["w"].copy_(weight.detach()[:, ks["k0"]:ks["k1"]])
+        check(get_lib().pv_cast_f32_to_bf16(ptr(ks["w"]), ptr(ks["shadow"]), ks["w"].numel(), current_stream_ptr()),
+              "pv_cast_f32_to_bf16")
+    ks["version"] = weight._version
+
+
 def linear_bf16(x, weight, bias, relu=False, x_is_relu_output=False):
-    if getattr(weight, "_pv_grad_mode", None) == "ksharded" and getattr(weight, "_pv_kshard", None) is not None:
+    ks = getattr(weight, "_pv_kshard", None) if getattr(weight, "_pv_grad_mode", None) == "ksharded" else None
+    if ks is not None:
+        if ks.get("version") != weight._version:
+            _recut_kshard_weight(weight, ks)
         return LinearBF16KSharded.apply(x, weight, bias, relu, x_is_relu_output)
     return LinearBF16.apply(x, weight, bias, relu, x_is_relu_output)
 

@@ -107,6 +107,12 @@ class GraphedTrainStep:
         self._pins = K.pin_workspaces()
         g = optimizer.param_groups[0]
         self._hyper = (g["lr"], tuple(g["betas"]), g["eps"])
+        # the operand copies the captured kernels read and write (conv fragment images, fc1's bf16 shadow): a replay keeps them
+        # current, but a change torch makes to a parameter between replays (load_state_dict, an in-place edit) does not reach
+        # them -- __call__ re-derives them from the parameter when its `_version` moved
+        self._params = [p for grp in optimizer.param_groups for p in grp["params"]]
+        self._held = [(getattr(p, "_pv_packed", None), getattr(p, "_pv_bf16_shadow", None)) for p in self._params]
+        self._versions = [p._version for p in self._params]
 
     def close(self) -> None:
         """Releases the graph and the workspaces it pinned."""
@@ -144,6 +150,37 @@ class GraphedTrainStep:
                                f"{(g['lr'], tuple(g['betas']), g['eps'])}); they were frozen as kernel arguments of the "
                                f"captured step -- capture a new GraphedTrainStep after changing them")
         _copy_into(self.static_batch, batch)
+        if any(p._version != v for p, v in zip(self._params, self._versions)):
+            self._rederive_held_copies()
         self.graph.replay()
         self.replays += 1
+        for p in self._params:
+            # the replay changed the weights through raw pointers: caches keyed on the optimiser's generation
+            # (functional.split2_conv_weight) must not serve the next eager forward
+            p._pv_opt_gen = getattr(p, "_pv_opt_gen", 0) + 1
         return self.static_loss
+
+    def _rederive_held_copies(self) -> None:
+        """Parameters torch changed since the last replay: their copies are packed again INTO the tensors the graph holds, and
+        the parameters' caches point at those tensors again (an eager forward in between may have replaced them)."""
+        from . import functional as F
+        from . import hip_ops as K
+        from ._lib import check, current_stream_ptr, get_lib, ptr
+        jobs = []
+        for i, (p, (packed, shadow)) in enumerate(zip(self._params, self._held)):
+            if p._version == self._versions[i]:
+                continue
+            F.drop_derived_copies(p)
+            if packed is not None:
+                if not p.is_contiguous():
+                    raise RuntimeError("GraphedTrainStep: a conv weight the captured step packs is no longer contiguous")
+                jobs += [(p.detach(), packed[flip], flip) for flip in (False, True) if flip in packed]
+                packed["version"] = p._version
+                p._pv_packed = packed
+            if shadow is not None:
+                check(get_lib().pv_cast_f32_to_bf16(ptr(p.detach()), ptr(shadow), p.numel(), current_stream_ptr()),
+                      "pv_cast_f32_to_bf16")
+                p._pv_bf16_shadow, p._pv_bf16_shadow_version = shadow, p._version
+            self._versions[i] = p._version
+        if jobs:
+            K.conv3d_pack_weights_multi(jobs)

@@ -610,10 +610,11 @@ class Trainer:
                 for o in self.optimizers:
                     o.zero_grad(set_to_none=True)
                 loss = self._timed("training_step", model.training_step, batch, i)
-                # terminate_on_nan: with a fused optimiser (HipAdam "fused": fc1 is stepped inside backward) the loss is
-                # tested BEFORE backward, so a non-finite step leaves weights and moments untouched (one host wait, only
-                # in this opt-in mode); otherwise after backward has been queued
-                nan_first = self.terminate_on_nan and any(getattr(o, "large_grad_mode", None) == "fused"
+                # terminate_on_nan: with an optimiser that steps fc1 inside backward (HipAdam "fused", and "ksharded": its
+                # one-pass backward updates the column shard) the loss is tested BEFORE backward, so a non-finite step
+                # leaves weights and moments untouched (one host wait, only in this opt-in mode); otherwise after backward
+                # has been queued
+                nan_first = self.terminate_on_nan and any(getattr(o, "large_grad_mode", None) in ("fused", "ksharded")
                                                           for o in self.optimizers)
                 if nan_first and not torch.isfinite(loss.detach()).all():
                     raise ValueError("loss is NaN or inf")
@@ -649,6 +650,10 @@ class Trainer:
         for o in self.optimizers:          # sharded large-parameter update: make every rank's f32 copy complete
             if hasattr(o, "consolidate_sharded"):
                 o.consolidate_sharded()
+            if getattr(o, "large_grad_mode", None) == "ksharded":
+                # fc1's forward in this mode is collective and reads the column shard: after fit() (test, predict, a
+                # load_state_dict of the best checkpoint, rank-local inference) it reads the full parameter again
+                o.set_large_grad_mode("bf16")
         if getattr(self, "_grad_sync", None) is not None:
             self._grad_sync.remove()
             self._grad_sync = None

@@ -70,6 +70,10 @@ class HipAdam(torch.optim.Optimizer):
         self.overlap_large_update = overlap_large_update
         self._side_stream = None
         self._inflight = []
+        for p in self.large_params():
+            # a column shard left on the parameter by another optimiser (an earlier fit, a resume) holds THAT optimiser's
+            # weights, moments and step: this one cuts its own from its own state (set_large_grad_mode("ksharded"))
+            p._pv_kshard = None
         self.set_large_grad_mode("fused" if fuse_large_linear else "autograd")
 
     def _advance_device_scalars(self, device) -> torch.Tensor:
@@ -106,9 +110,9 @@ class HipAdam(torch.optim.Optimizer):
         if getattr(self, "_layout_frozen", False) and mode != getattr(self, "large_grad_mode", mode):
             raise RuntimeError("HipAdam.set_large_grad_mode(): a captured HIP graph holds this optimiser's state tensors and the "
                                "gradient mode it was captured with -- release the graph first (GraphedTrainStep.close())")
-        if getattr(self, "large_grad_mode", None) in ("sharded", "ksharded") and mode != self.large_grad_mode:
+        if getattr(self, "large_grad_mode", None) in ("sharded", "ksharded") and (mode != self.large_grad_mode or mode == "ksharded"):
             # (collective, a no-op unless sharded steps were taken) the row / column shards hold the truth: back into the full
-            # tensors before another mode reads them
+            # tensors before another mode reads them, or before "ksharded" cuts its shard again from them
             self.consolidate_sharded()
             for p in self.large_params():
                 p._pv_kshard = None
@@ -124,8 +128,10 @@ class HipAdam(torch.optim.Optimizer):
         self.large_grad_mode = mode
         self._moments_rows()
         for p in self.large_params():
-            if mode == "ksharded" and getattr(p, "_pv_kshard", None) is None:
-                self._make_column_shard(p)
+            if mode == "ksharded":
+                self._make_column_shard(p)      # always from the full tensors as they stand: never a shard cut earlier
+            else:
+                p._pv_kshard = None
             p._pv_grad_mode = mode
             p._pv_kshard_pending = None
             p._pv_kshard_backward = self._make_kshard_backward(p) if mode == "ksharded" else None
@@ -142,7 +148,8 @@ class HipAdam(torch.optim.Optimizer):
         """large_grad_mode "ksharded": this rank's COLUMNS of p as contiguous tensors of their own -- f32 master, bf16 operand
         copy, both moments -- cut from the full parameter / optimiser state (replicated at this point: after the initial
         broadcast, a checkpoint load or consolidate_sharded()).  From here on the full tensors are stale until
-        consolidate_sharded(); the kernels only ever see the shard, an ordinary dense [N, K / W] matrix."""
+        consolidate_sharded(); the kernels only ever see the shard, an ordinary dense [N, K / W] matrix.  `version` is p's
+        `_version` at the cut: functional.linear_bf16 re-cuts the weight columns when torch has changed p since."""
         from . import distributed as D
         k0, k1 = D.column_shard(p.shape[1], multiple=K.MOMENT_TILE)
         st = self.state.get(p) or {}
@@ -151,7 +158,7 @@ class HipAdam(torch.optim.Optimizer):
             ks = {"k0": k0, "k1": k1, "w": w, "shadow": K.cast_f32_to_bf16(w),
                   "exp_avg": (st["exp_avg"][:, k0:k1].contiguous() if "exp_avg" in st else torch.zeros_like(w)),
                   "exp_avg_sq": (st["exp_avg_sq"][:, k0:k1].contiguous() if "exp_avg_sq" in st else torch.zeros_like(w)),
-                  "step": int(st["step"].item()) if "step" in st else 0}
+                  "step": int(st["step"].item()) if "step" in st else 0, "version": p._version}
         p._pv_kshard = ks
 
     def consolidate_sharded(self) -> None:
@@ -172,8 +179,8 @@ class HipAdam(torch.optim.Optimizer):
                         D.all_gather_columns(ks["exp_avg"], st["exp_avg"])
                         D.all_gather_columns(ks["exp_avg_sq"], st["exp_avg_sq"])
                         st["step"].fill_(float(ks["step"]))
-                    if hasattr(p, "_pv_bf16_shadow"):
-                        p._pv_bf16_shadow = None      # (the full operand copy, if any mode built one earlier, is stale)
+                    from .functional import drop_derived_copies
+                    drop_derived_copies(p)      # (the full operand copy, if any mode built one earlier, is stale)
                     continue
                 if getattr(p, "_pv_grad_mode", None) != "sharded":
                     continue
@@ -305,6 +312,12 @@ class HipAdam(torch.optim.Optimizer):
                     if key in st:
                         st[key] = _k_to_channels_last(st[key], c).contiguous()
                 st["exp_avg"]._pv_k_channels = c
+        if getattr(self, "large_grad_mode", None) == "ksharded":
+            # the column shards are the state the K-sharded steps use: cut again from the loaded moments and step (and from
+            # the parameter as it stands -- a model.load_state_dict() after this one is seen by functional.linear_bf16)
+            self._sharded_dirty = False
+            for p in self.large_params():
+                self._make_column_shard(p)
         if self.capturable:
             steps = [int(st["step"].item()) for st in self.state.values() if "step" in st]
             if self._dev_step is not None:

@@ -394,3 +394,75 @@ def test_kshard_one_pass_backward_kernel_against_the_separate_kernels(device, m,
     sh_diff = (sha.float() - shb.float()).abs()
     assert float((sh_diff > 0).float().mean()) < 1e-3 and float(sh_diff.max()) <= 2.0 ** -7 * float(sha.float().abs().max())
     assert not torch.equal(wb, w0)
+
+
+# ---- state around fc1's column shard and the cached operand copies (ddp_two_rank_worker.CASES) ---------------------------
+def _run_case(case, tmp_path, fuse_min_numel=100000):
+    """Two ranks on the one GPU; with fuse_min_numel=100000 fc1 is the only "large" matrix, so "ksharded" holds."""
+    return _run_two_ranks(case, str(tmp_path / f"{case}.pt"), steps=0, fuse_min_numel=fuse_min_numel)
+
+
+def _assert_same_step(got, want, what):
+    for k in want["state"]:
+        assert torch.equal(got["state"][k], want["state"][k]), (what, k)
+    for k in ("exp_avg", "exp_avg_sq"):
+        assert torch.equal(got[k], want[k]), (what, k)
+    assert got["step"] == want["step"] == 2.0, (what, got["step"], want["step"])
+
+
+@pytest.fixture(scope="module")
+def reload_case(device, tmp_path_factory):
+    return _run_case("case_reload", tmp_path_factory.mktemp("reload"))
+
+
+def test_ksharded_reload_of_a_checkpoint_repeats_the_step(device, reload_case):
+    """ksharded: step 1, consolidate, checkpoint C1, step 2; C1 loaded into the model and the optimiser, step 2 again: rank 0's
+    consolidated parameters and fc1's moments are those of the first step 2, bit for bit (the column
+    shard was cut once and never refreshed, so the reload was ignored)."""
+    r = reload_case
+    assert r["loss2"] == r["loss1"], (r["loss1"], r["loss2"])
+    _assert_same_step(r["r2"], r["r1"], "reload")
+
+
+def test_ksharded_new_optimizer_resumes_from_the_checkpoint(device, reload_case):
+    """A new HipAdam on the same model (a second fit, a resume) loads C1 and is set to ksharded: its first step is the
+    checkpoint's step 2, not a step of the shard the earlier optimiser left on the parameter."""
+    r = reload_case
+    assert r["mode3"] == "ksharded"
+    assert r["loss3"] == r["loss1"], (r["loss1"], r["loss3"])
+    _assert_same_step(r["r3"], r["r1"], "new optimiser")
+
+
+def test_ksharded_fit_leaves_fc1_rank_local(device, tmp_path):
+    """After Trainer(large_grad_mode="ksharded").fit fc1 carries no shard and its forward is not collective: a rank-local
+    no-grad forward equals a cold twin's.  (The worker reads the attributes before any forward.)"""
+    r = _run_case("case_after_fit", tmp_path)
+    assert r["during"] == [("ksharded", True)], r["during"]        # the fit really ran K-sharded
+    assert not r["kshard_after"]
+    assert r["grad_mode_after"] != "ksharded"
+    assert torch.equal(r["y"], r["y_twin"])
+
+
+def test_ksharded_nan_loss_raises_before_the_shard_changes(device, tmp_path):
+    """terminate_on_nan with a NaN loss on every rank in ksharded mode: fit raises, and fc1's shard (weight, operand copy,
+    moments, step) is what the step before left (the one-pass backward updates the shard inside backward())."""
+    r = _run_case("case_nan", tmp_path)
+    assert r["mode"] == "ksharded"
+    assert r["raised"] is not None and "NaN" in r["raised"], r["raised"]
+    assert r["before"]["step"] == r["after"]["step"] == 1, (r["before"]["step"], r["after"]["step"])
+    for k in ("w", "shadow", "exp_avg", "exp_avg_sq"):
+        assert torch.isfinite(r["after"][k].float()).all(), k
+        assert torch.equal(r["before"][k], r["after"][k]), k
+
+
+def test_broadcast_parameters_replaces_the_cached_operand_copies(device, tmp_path):
+    """Ranks seeded differently run a no-grad forward (which caches the operand copies of their own weights), then take rank 0's
+    parameters through broadcast_parameters (a write through .data: `_version` does not move): the next forward of every rank
+    is rank 0's, bit for bit, for both precisions."""
+    path = tmp_path / "case_broadcast.pt"
+    r0 = _run_two_ranks("case_broadcast", str(path), steps=0)
+    r1 = torch.load(f"{path}.rank1")
+    for precision in ("bf16", "fp32"):
+        # the forward really went through the cached copies: packed conv images (bf16), the half-float split images (fp32)
+        assert len(r0[precision]["cached"]) >= 3 and r0[precision]["cached"] == r1[precision]["cached"], precision
+        assert torch.equal(r0[precision]["y"], r1[precision]["y"]), precision
