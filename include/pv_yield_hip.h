@@ -232,6 +232,56 @@ int pv_conv2d_bwd_weight_f32(const float* x, const float* dy, const float* dy_ga
 int pv_conv2d_coords_bwd_weight_f32(const float* sat, const float* x_coords, const float* y_coords, const float* dy,
                                     float* dw, float* dbias, int32_t n, int32_t t_per_example, int32_t h_in,
                                     int32_t w_in, int32_t c_out, void* ws, size_t ws_bytes, void* stream);
+/* ---- Conv2d 3x3 144 -> 144 (+ MaxPool2d(3)), exact f32 (experiments/001_CNN_concat_all_timesteps_as_channels.py) ---- */
+/* Images [n][c][h][w] (NCHW); weights [144][c_in][3][3]; conv outputs [n][144][h - 2][w - 2].  Products on the f32 matrix
+ * cores with f32 accumulation, K streamed in channel chunks.  The pooled layers compute relu(max_pool2d(conv(x) + bias,
+ * 3)) == max_pool2d(relu(...), 3) over whole windows only (floor: the last (h - 2) % 3 rows / columns are not computed) and
+ * write pooled [n][144][(h - 2) / 3][(w - 2) / 3] plus codes (uint8, same shape): the window position 0..8 (row-major) of
+ * the first maximum, or 255 where the maximum is <= 0 (such a window passes no gradient).  Backward passes expand a pooled
+ * gradient through the codes while staging it.  Weight gradients: fixed slabs summed in slab order (no atomics). */
+/* replaces: self.maxpool(F.relu(self.sat_conv1(torch.cat((frames, center_marker, x_coords, y_coords, pixel_x, pixel_y),
+ * dim=1)))), experiments/001_CNN_concat_all_timesteps_as_channels.py:241-245, 264-307.  sat [b][t_total][h][w] (the
+ * trailing channel axis of 1 dropped) is read in place, frames 0..n_frames-1 as channels 0..n_frames-1 (n_frames <= 27,
+ * <= t_total); channels n_frames.. n_frames+4 (centre marker on rows / columns [h/2 - 2, h/2 + 2), (x_coords[b][col] -
+ * 309000) / 316387.42, (y_coords[b][row] - 519000) / 406454.18, (col - 64) / 37, (row - 64) / 37) are built while staged,
+ * never stored.  c_out = 144, h and w >= 5. */
+int pv_conv2d144_sat_pool_fwd_f32(const float* sat, const float* x_coords, const float* y_coords, const float* w,
+                                  const float* bias, float* y, uint8_t* codes, int32_t b, int32_t t_total,
+                                  int32_t n_frames, int32_t h, int32_t w_img, int32_t c_out, void* stream);
+/* replaces: self.maxpool(F.relu(self.sat_conv2(out))), experiments/001...py:308-309.  c_in = c_out = 144. */
+int pv_conv2d144_pool_fwd_f32(const float* x, const float* w, const float* bias, float* y, uint8_t* codes, int32_t n,
+                              int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+/* replaces: self.sat_conv3(out) (+ F.relu if relu), experiments/001...py:310.  c_in = c_out = 144; bias may be NULL. */
+int pv_conv2d144_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                         int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of sat_conv3 (autograd of experiments/001...py:310).  dy [n][144][h-2][w-2] zeroed where
+ * dy_gate <= 0 (NULL = none); dx [n][144][h][w] zeroed where x_gate <= 0 (NULL = ungated). */
+int pv_conv2d144_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                              int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+/* replaces: the input gradient of maxpool(relu(sat_conv2(x))) (autograd of experiments/001...py:308-309): dy_pooled and
+ * codes [n][144][(h-2)/3][(w-2)/3] as written by pv_conv2d144_pool_fwd_f32; dx [n][144][h][w], gated by x_gate as above. */
+int pv_conv2d144_pool_bwd_data_f32(const float* dy_pooled, const uint8_t* codes, const float* w, float* dx,
+                                   const float* x_gate, int32_t n, int32_t c_in, int32_t c_out, int32_t h_in,
+                                   int32_t w_in, void* stream);
+/* bytes of the weight-gradient workspace (partials [144][c_in * 9 + 1] per slab); c_in = 144, or n_frames + 5 for the
+ * first layer; pooled != 0 for the pooled layers (only whole windows carry a gradient) */
+int pv_conv2d144_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                            int32_t pooled, size_t* bytes);
+/* replaces: the weight and bias gradients of sat_conv3; dw [144][144][3][3] and dbias [144] overwritten; dy_gate as for
+ * pv_conv2d144_bwd_data_f32. */
+int pv_conv2d144_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias,
+                                int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
+                                size_t ws_bytes, void* stream);
+/* replaces: the weight and bias gradients of sat_conv2 under the max pool, from the pooled gradient and the codes. */
+int pv_conv2d144_pool_bwd_weight_f32(const float* x, const float* dy_pooled, const uint8_t* codes, float* dw,
+                                     float* dbias, int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                     void* ws, size_t ws_bytes, void* stream);
+/* replaces: the weight and bias gradients of sat_conv1 under the max pool, re-synthesising its input from sat as the
+ * forward does; dw [144][n_frames + 5][3][3]. */
+int pv_conv2d144_sat_pool_bwd_weight_f32(const float* sat, const float* x_coords, const float* y_coords,
+                                         const float* dy_pooled, const uint8_t* codes, float* dw, float* dbias,
+                                         int32_t b, int32_t t_total, int32_t n_frames, int32_t h, int32_t w_img,
+                                         int32_t c_out, void* ws, size_t ws_bytes, void* stream);
 
 /* MaxPool3d over x[B*C planes][Ti,Hi,Wi]; argmax (may be NULL) = flat winner offset inside the plane stack, first
  * maximum wins, NaN propagates (torch CPU semantics).  bwd overwrites dx by gathering dy through argmax. */

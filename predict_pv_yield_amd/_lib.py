@@ -152,6 +152,18 @@ SIGNATURES = {
     "pv_conv2d_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
     "pv_conv2d_coords_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz,
                                         c_vp],
+    "pv_conv2d144_sat_pool_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                      c_vp],
+    "pv_conv2d144_pool_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "pv_conv2d144_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "pv_conv2d144_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "pv_conv2d144_pool_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "pv_conv2d144_bwd_weight_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)],
+    "pv_conv2d144_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
+    "pv_conv2d144_pool_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz,
+                                         c_vp],
+    "pv_conv2d144_sat_pool_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                             c_i32, c_vp, c_sz, c_vp],
     "pv_maxpool3d_fwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_maxpool3d_bwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_mse_loss_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp],

@@ -1130,6 +1130,187 @@ def conv2d_coords_bwd_weight_f32(sat, x_coords, y_coords, dy, t_per_example, wei
     return dw, db
 
 
+# ------------------------------------------------------------------------------------------------
+# Conv2d 3x3 144 -> 144 (+ MaxPool2d(3)) (experiments/001_CNN_concat_all_timesteps_as_channels.py), exact f32
+# ------------------------------------------------------------------------------------------------
+C144 = 144
+
+
+def _u8_contig(who, codes):
+    if codes.dtype != torch.uint8 or not codes.is_contiguous():
+        raise TypeError(f"{who}: codes must be a contiguous uint8 tensor")
+
+
+def _pooled_shape(n, h, w):
+    return (n, C144, (h - 2) // 3, (w - 2) // 3)
+
+
+def _check_sat001(who, sat, x_coords, y_coords, n_frames):
+    _shape_check(sat.dim() == 5 and sat.shape[4] == 1, who, f"sat_data [B, T, H, W, 1] expected, got {tuple(sat.shape)}")
+    b, t, h, w, _ = sat.shape
+    _shape_check(0 < n_frames <= t, who, f"n_frames={n_frames} must lie in 1..T={t}")
+    _shape_check(h >= 5 and w >= 5, who, f"images of at least 5 x 5 expected, got {h} x {w}")
+    _shape_check(tuple(x_coords.shape) == (b, w) and tuple(y_coords.shape) == (b, h), who,
+                 f"x_coords [{b}, {w}] and y_coords [{b}, {h}] expected, got {tuple(x_coords.shape)} / {tuple(y_coords.shape)}")
+    return b, t, h, w
+
+
+def _check_c144(who, x_shape, weight_shape, pooled):
+    _shape_check(len(x_shape) == 4 and x_shape[1] == C144, who, f"x [N, 144, H, W] expected, got {tuple(x_shape)}")
+    _shape_check(tuple(weight_shape) == (C144, C144, 3, 3), who, f"weight [144, 144, 3, 3] expected, got {tuple(weight_shape)}")
+    lo = 5 if pooled else 3
+    _shape_check(x_shape[2] >= lo and x_shape[3] >= lo, who, f"images of at least {lo} x {lo} expected, got {tuple(x_shape)}")
+
+
+def conv2d144_sat_pool_fwd_f32(sat, x_coords, y_coords, weight, bias, n_frames):
+    """relu(max_pool2d(conv2d(cat(frames 0..n_frames-1 of sat [B, T, H, W, 1], 5 synthesised channels), weight) + bias, 3))
+    with x_coords [B, W], y_coords [B, H]; the input is built inside the kernel.  Returns (pooled [B, 144, (H-2)//3, (W-2)//3],
+    codes uint8 of the same shape)."""
+    who = "conv2d144_sat_pool_fwd_f32"
+    b, t, h, w = _check_sat001(who, sat, x_coords, y_coords, n_frames)
+    _shape_check(tuple(weight.shape) == (C144, n_frames + 5, 3, 3), who,
+                 f"weight [144, {n_frames + 5}, 3, 3] expected, got {tuple(weight.shape)}")
+    _shape_check(bias is not None and tuple(bias.shape) == (C144,), who, "bias [144] expected")
+    require_cuda(sat, x_coords, y_coords, weight, bias)
+    _f32_contig(sat, x_coords, y_coords, weight, bias)
+    y = torch.empty(_pooled_shape(b, h, w), dtype=torch.float32, device=sat.device)
+    codes = torch.empty(y.shape, dtype=torch.uint8, device=sat.device)
+    check(get_lib().pv_conv2d144_sat_pool_fwd_f32(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(weight), ptr(bias), ptr(y),
+                                                  ptr(codes), b, t, n_frames, h, w, C144, current_stream_ptr()),
+          "pv_conv2d144_sat_pool_fwd_f32")
+    return y, codes
+
+
+def conv2d144_pool_fwd_f32(x, weight, bias):
+    """relu(max_pool2d(conv2d(x, weight) + bias, 3)) for x [N, 144, H, W] -> (pooled, codes uint8)."""
+    who = "conv2d144_pool_fwd_f32"
+    _check_c144(who, x.shape, weight.shape, True)
+    _shape_check(bias is not None and tuple(bias.shape) == (C144,), who, "bias [144] expected")
+    require_cuda(x, weight, bias)
+    _f32_contig(x, weight, bias)
+    n, c, h, w = x.shape
+    y = torch.empty(_pooled_shape(n, h, w), dtype=torch.float32, device=x.device)
+    codes = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
+    check(get_lib().pv_conv2d144_pool_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(codes), n, c, C144, h, w,
+                                              current_stream_ptr()), "pv_conv2d144_pool_fwd_f32")
+    return y, codes
+
+
+def conv2d144_fwd_f32(x, weight, bias, relu=True):
+    """conv2d(x, weight) + bias (+ ReLU) for x [N, 144, H, W] -> [N, 144, H-2, W-2]."""
+    who = "conv2d144_fwd_f32"
+    _check_c144(who, x.shape, weight.shape, False)
+    _check_bias(who, bias, C144)
+    require_cuda(x, weight, bias)
+    _f32_contig(x, weight, bias)
+    n, c, h, w = x.shape
+    y = torch.empty((n, C144, h - 2, w - 2), dtype=torch.float32, device=x.device)
+    check(get_lib().pv_conv2d144_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), n, c, C144, h, w, int(relu),
+                                         current_stream_ptr()), "pv_conv2d144_fwd_f32")
+    return y
+
+
+def conv2d144_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of conv2d144_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
+    who = "conv2d144_bwd_data_f32"
+    _check_c144(who, x_shape, weight.shape, False)
+    n, c, h, w = x_shape
+    y_shape = (n, C144, h - 2, w - 2)
+    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
+                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
+    require_cuda(dy, dy_gate, weight, x_gate)
+    _f32_contig(dy, dy_gate, weight, x_gate)
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
+    check(get_lib().pv_conv2d144_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, c, C144, h, w,
+                                              current_stream_ptr()), "pv_conv2d144_bwd_data_f32")
+    return dx
+
+
+def conv2d144_pool_bwd_data_f32(dy_pooled, codes, weight, x_gate, x_shape):
+    """dx of conv2d144_pool_fwd_f32 from the pooled gradient and the forward's codes; dx zeroed where x_gate <= 0."""
+    who = "conv2d144_pool_bwd_data_f32"
+    _check_c144(who, x_shape, weight.shape, True)
+    n, c, h, w = x_shape
+    p_shape = _pooled_shape(n, h, w)
+    _shape_check(tuple(dy_pooled.shape) == p_shape and tuple(codes.shape) == p_shape, who,
+                 f"dy_pooled / codes {p_shape} expected, got {tuple(dy_pooled.shape)} / {tuple(codes.shape)}")
+    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
+    require_cuda(dy_pooled, codes, weight, x_gate)
+    _f32_contig(dy_pooled, weight, x_gate)
+    _u8_contig(who, codes)
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy_pooled.device)
+    check(get_lib().pv_conv2d144_pool_bwd_data_f32(ptr(dy_pooled), ptr(codes), ptr(weight), ptr(dx), ptr(x_gate), n, c,
+                                                   C144, h, w, current_stream_ptr()), "pv_conv2d144_pool_bwd_data_f32")
+    return dx
+
+
+def _conv2d144_wgrad_ws(n, ci, h, w, pooled, device):
+    nbytes = ctypes.c_size_t(0)
+    check(get_lib().pv_conv2d144_bwd_weight_workspace_bytes(n, ci, C144, h, w, int(pooled), ctypes.byref(nbytes)),
+          "pv_conv2d144_bwd_weight_workspace_bytes")
+    return _workspace("conv2d144_wgrad", nbytes.value, device), nbytes.value
+
+
+def _grads_out(ci, device):
+    return (torch.empty((C144, ci, 3, 3), dtype=torch.float32, device=device),
+            torch.empty((C144,), dtype=torch.float32, device=device))
+
+
+def conv2d144_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw, dbias) of conv2d144_fwd_f32; deterministic (fixed slabs summed in order)."""
+    who = "conv2d144_bwd_weight_f32"
+    _check_c144(who, x.shape, weight_shape, False)
+    n, c, h, w = x.shape
+    y_shape = (n, C144, h - 2, w - 2)
+    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
+                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    require_cuda(x, dy, dy_gate)
+    _f32_contig(x, dy, dy_gate)
+    ws, nbytes = _conv2d144_wgrad_ws(n, c, h, w, False, x.device)
+    dw, db = _grads_out(c, x.device)
+    check(get_lib().pv_conv2d144_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, c, C144, h, w, ptr(ws),
+                                                nbytes, current_stream_ptr()), "pv_conv2d144_bwd_weight_f32")
+    return dw, db
+
+
+def conv2d144_pool_bwd_weight_f32(x, dy_pooled, codes, weight_shape):
+    """(dw, dbias) of conv2d144_pool_fwd_f32 from the pooled gradient and the codes; deterministic."""
+    who = "conv2d144_pool_bwd_weight_f32"
+    _check_c144(who, x.shape, weight_shape, True)
+    n, c, h, w = x.shape
+    p_shape = _pooled_shape(n, h, w)
+    _shape_check(tuple(dy_pooled.shape) == p_shape and tuple(codes.shape) == p_shape, who,
+                 f"dy_pooled / codes {p_shape} expected, got {tuple(dy_pooled.shape)} / {tuple(codes.shape)}")
+    require_cuda(x, dy_pooled, codes)
+    _f32_contig(x, dy_pooled)
+    _u8_contig(who, codes)
+    ws, nbytes = _conv2d144_wgrad_ws(n, c, h, w, True, x.device)
+    dw, db = _grads_out(c, x.device)
+    check(get_lib().pv_conv2d144_pool_bwd_weight_f32(ptr(x), ptr(dy_pooled), ptr(codes), ptr(dw), ptr(db), n, c, C144, h,
+                                                     w, ptr(ws), nbytes, current_stream_ptr()),
+          "pv_conv2d144_pool_bwd_weight_f32")
+    return dw, db
+
+
+def conv2d144_sat_pool_bwd_weight_f32(sat, x_coords, y_coords, dy_pooled, codes, n_frames):
+    """(dw [144, n_frames + 5, 3, 3], dbias) of conv2d144_sat_pool_fwd_f32, re-synthesising its input; deterministic."""
+    who = "conv2d144_sat_pool_bwd_weight_f32"
+    b, t, h, w = _check_sat001(who, sat, x_coords, y_coords, n_frames)
+    p_shape = _pooled_shape(b, h, w)
+    _shape_check(tuple(dy_pooled.shape) == p_shape and tuple(codes.shape) == p_shape, who,
+                 f"dy_pooled / codes {p_shape} expected, got {tuple(dy_pooled.shape)} / {tuple(codes.shape)}")
+    require_cuda(sat, x_coords, y_coords, dy_pooled, codes)
+    _f32_contig(sat, x_coords, y_coords, dy_pooled)
+    _u8_contig(who, codes)
+    ws, nbytes = _conv2d144_wgrad_ws(b, n_frames + 5, h, w, True, sat.device)
+    dw, db = _grads_out(n_frames + 5, sat.device)
+    check(get_lib().pv_conv2d144_sat_pool_bwd_weight_f32(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(dy_pooled), ptr(codes),
+                                                         ptr(dw), ptr(db), b, t, n_frames, h, w, C144, ptr(ws), nbytes,
+                                                         current_stream_ptr()), "pv_conv2d144_sat_pool_bwd_weight_f32")
+    return dw, db
+
+
 def maxpool3d_fwd_f32(x, kernel=3, stride=None, padding=0):
     require_cuda(x)
     b, c, t, h, w = x.shape
