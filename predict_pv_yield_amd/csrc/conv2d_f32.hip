@@ -10,17 +10,15 @@
 // its 12 satellite channels are read channels-last from sat_data and the 5 synthesised channels are computed while the
 // band is staged.  wgrad splits the (image, band) items into fixed slabs, each block writing its partial sums to its own
 // workspace slab, then adds the slabs in index order: no atomics, identical bits run to run.  The 32 -> 4 layer's weight
-// gradient is the one pass these tiles do not fit; it takes the general Conv3d f32 kernel (general_wgrad_geom below).
-#include "pv_common.h"
+// gradient is the one pass these tiles do not fit; it takes the general Conv3d f32 kernel (general_wgrad_geom below).  The
+// slab sum, the synthesised channels and the shared argument checks are in conv2d_f32_common.h.
+#include "conv2d_f32_common.h"
 
 namespace pv {
 namespace {
 
 constexpr int kSatChannels = 12;
 constexpr int kCoordChannels = 17;   // 12 satellite + centre marker, geo x, geo y, pixel x, pixel y
-constexpr int kBlock = 256;          // 4 waves
-
-typedef __attribute__((ext_vector_type(4))) float acc4;
 
 struct C2 {
   // input of the pass: x[n][c_in][h_in][w_in] (mode plain) or sat[n][h_in][w_in][12] + coords (mode coords)
@@ -34,22 +32,6 @@ struct C2 {
   const float* out_gate;   // y zeroed where out_gate <= 0 (same layout as y); may be null
   int n, c_in, m_out, h_in, w_in, pad, h_out, w_out, rb, n_bands, t_per_ex, w_sm, w_sc, flip, relu;
 };
-
-// The five synthesised channels of experiments/002...py:140-162, 180-208 at input row r (the W axis), column c (the H axis).
-__device__ __forceinline__ float coord_channel(int ch, int r, int c, int h_in, int w_in, const float* xc_b,
-                                               const float* yc_b) {
-  switch (ch) {
-    case 12: {   // centre marker: 1 on rows and columns [S//2 - 2, S//2 + 2)
-      const int hr = h_in / 2, hc = w_in / 2;
-      return (r >= hr - 2 && r < hr + 2 && c >= hc - 2 && c < hc + 2) ? 1.0f : 0.0f;
-    }
-    case 13: return __fdiv_rn(xc_b[c] - 309000.0f, 316387.42073603f);   // (x - SAT_X_MEAN) / SAT_X_STD in f32
-    case 14: return __fdiv_rn(yc_b[r] - 519000.0f, 406454.17945938f);   // (y - SAT_Y_MEAN) / SAT_Y_STD in f32
-    case 15: return __fdiv_rn((float)(c - 64), 37.0f);                  // (arange(S) - 64) / 37 along the last axis
-    case 16: return __fdiv_rn((float)(r - 64), 37.0f);                  // ... and along rows
-    default: return 0.0f;                                                // channels padded to a multiple of 4
-  }
-}
 
 // Stage input rows [ir0, ir0 + rows) x columns [ic0, ic0 + cols) of image n, channels [0, cinp), as lds[c][r][col]
 // (channel stride cs, row stride cols); outside the image (padding) and beyond c_in: 0.
@@ -75,7 +57,9 @@ __device__ void stage_band(float* lds, const C2& a, int cinp, int cs, int n, int
       const int col = i % cols, r = (i / cols) % rows, ch = kSatChannels + i / (cols * rows);
       const int ir = ir0 + r, ic = ic0 + col;
       float v = 0.0f;
-      if (ir >= 0 && ir < a.h_in && ic >= 0 && ic < a.w_in) v = coord_channel(ch, ir, ic, a.h_in, a.w_in, xc_b, yc_b);
+      // the channels of experiments/002...py:140-162, 180-208 (row r = the W axis, column c = the H axis); 0 beyond them
+      if (ir >= 0 && ir < a.h_in && ic >= 0 && ic < a.w_in)
+        v = synth_channel(ch - kSatChannels, ir, ic, a.h_in / 2, a.w_in / 2, xc_b, yc_b);
       lds[ch * cs + r * cols + col] = v;
     }
   } else {
@@ -271,38 +255,6 @@ __global__ __launch_bounds__(kBlock) void conv2d_wgrad_mfma_f32(W2 q) {
   }
 }
 
-// dw[co][j] = sum_s slabs[s][co][j] (j < k9), dbias[co] = sum_s slabs[s][co][k9] in a fixed order: block = 32 elements x 8
-// slab groups; group g adds slabs g, g + 8, ... into four interleaved partial sums (independent loads in flight), then
-// the four and the 8 groups' results are added in index order.
-constexpr int kSumElems = 32, kSumGroups = kBlock / kSumElems;
-__global__ __launch_bounds__(kBlock) void conv2d_slab_sum_f32(const float* __restrict__ slabs, float* __restrict__ dw,
-                                                              float* __restrict__ db, int c_out, int k9, int n_slabs) {
-  __shared__ float part[kSumGroups][kSumElems];
-  const int ncols = k9 + 1, total = c_out * ncols;
-  const int le = threadIdx.x % kSumElems, g = threadIdx.x / kSumElems;
-  const int e = blockIdx.x * kSumElems + le;
-  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (e < total) {
-    int i = g;
-    for (; i + 3 * kSumGroups < n_slabs; i += 4 * kSumGroups)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s[u] += slabs[(size_t)(i + u * kSumGroups) * total + e];
-    for (; i < n_slabs; i += kSumGroups) s[0] += slabs[(size_t)i * total + e];
-  }
-  part[g][le] = (s[0] + s[1]) + (s[2] + s[3]);
-  __syncthreads();
-  if (g != 0 || e >= total) return;
-  float t = part[0][le];
-#pragma unroll
-  for (int j = 1; j < kSumGroups; ++j) t += part[j][le];
-  const int co = e / ncols, j = e - co * ncols;
-  if (j < k9) {
-    if (dw) dw[co * k9 + j] = t;
-  } else if (db) {
-    db[co] = t;
-  }
-}
-
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
 constexpr int kMaxSlabs = 512;
@@ -346,10 +298,8 @@ WgradPlan wgrad_plan(int n, int c_in, int c_out, int h_in, int w_in) {
 }
 
 int check_dims(const char* who, int n, int c_in, int c_out, int h_in, int w_in, bool coords) {
-  PV_REQUIRE(n > 0 && c_in > 0 && c_out > 0, PV_EINVAL, "%s: non-positive dimension", who);
-  PV_REQUIRE(h_in >= 3 && w_in >= 3, PV_ESIZE, "%s: spatial extent %d x %d smaller than the 3x3 kernel", who, h_in, w_in);
-  PV_REQUIRE((long long)n * c_in * h_in * w_in < (1LL << 31) && (long long)n * c_out * h_in * w_in < (1LL << 31),
-             PV_ESIZE, "%s: tensor beyond 2^31 elements", who);
+  int rc = check_conv_dims(who, n, c_in, c_out, h_in, w_in);
+  if (rc) return rc;
   PV_REQUIRE(w_in <= 96, PV_ESIZE, "%s: width %d beyond 96 (one band row per LDS image)", who, w_in);
   if (coords)
     PV_REQUIRE(c_out == 32, PV_ESIZE, "%s: unsupported channel count c_out=%d (the coords layer has 32)", who, c_out);
@@ -359,10 +309,8 @@ int check_dims(const char* who, int n, int c_in, int c_out, int h_in, int w_in, 
   return PV_OK;
 }
 
-int check_wgrad_ws(const char* who, const WgradPlan& p, int c_in, int c_out, void* ws, size_t ws_bytes) {
-  const size_t need = (size_t)p.n_slabs * c_out * (c_in * 9 + 1) * sizeof(float);
-  PV_REQUIRE(ws && ws_bytes >= need, PV_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, need);
-  return PV_OK;
+size_t wgrad_ws_bytes(const WgradPlan& p, int c_in, int c_out) {
+  return (size_t)p.n_slabs * c_out * (c_in * 9 + 1) * sizeof(float);
 }
 
 int launch_wgrad(const char* who, const C2& a, const float* dy, const float* dy_gate, float* dw, float* db,
@@ -377,9 +325,7 @@ int launch_wgrad(const char* who, const C2& a, const float* dy, const float* dy_
   else conv2d_wgrad_mfma_f32<2, 5, false><<<grid, block, p.lds, st>>>(q);
   int rc = check_launch(who);
   if (rc) return rc;
-  const int total = a.m_out * (a.c_in * 9 + 1);
-  conv2d_slab_sum_f32<<<dim3((unsigned)((total + kSumElems - 1) / kSumElems)), block, 0, st>>>((const float*)ws, dw, db, a.m_out,
-                                                                                        a.c_in * 9, p.n_slabs);
+  launch_slab_sum(ws, dw, db, a.m_out, a.c_in * 9, p.n_slabs, st);
   return check_launch(who);
 }
 
@@ -474,7 +420,7 @@ int pv_conv2d_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out,
     return pv_conv3d_general_bwd_weight_workspace_bytes(&g, bytes);
   }
   const WgradPlan p = wgrad_plan(n, c_in, c_out, h_in, w_in);
-  *bytes = (size_t)p.n_slabs * c_out * (c_in * 9 + 1) * sizeof(float);
+  *bytes = wgrad_ws_bytes(p, c_in, c_out);
   return PV_OK;
 }
 
@@ -490,11 +436,12 @@ int pv_conv2d_bwd_weight_f32(const float* x, const float* dy, const float* dy_ga
     size_t need = 0;
     rc = pv_conv3d_general_bwd_weight_workspace_bytes(&g, &need);
     if (rc) return rc;
-    PV_REQUIRE(ws && ws_bytes >= need, PV_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, need);
+    rc = check_workspace(who, ws, ws_bytes, need);
+    if (rc) return rc;
     return pv_conv3d_general_bwd_weight_f32(x, dy, dy_gate, dw, dbias, &g, ws, ws_bytes, stream);
   }
   const WgradPlan p = wgrad_plan(n, c_in, c_out, h_in, w_in);
-  rc = check_wgrad_ws(who, p, c_in, c_out, ws, ws_bytes);
+  rc = check_workspace(who, ws, ws_bytes, wgrad_ws_bytes(p, c_in, c_out));
   if (rc) return rc;
   C2 a = {};
   a.x = x, a.n = n, a.c_in = c_in, a.m_out = c_out, a.h_in = h_in, a.w_in = w_in, a.h_out = h_in - 2, a.w_out = w_in - 2;
@@ -512,7 +459,7 @@ int pv_conv2d_coords_bwd_weight_f32(const float* sat, const float* x_coords, con
   PV_REQUIRE(t_per_example > 0 && n % t_per_example == 0, PV_EINVAL, "%s: n=%d is not a multiple of t_per_example=%d",
              who, n, t_per_example);
   const WgradPlan p = wgrad_plan(n, kCoordChannels, c_out, h_in, w_in);
-  rc = check_wgrad_ws(who, p, kCoordChannels, c_out, ws, ws_bytes);
+  rc = check_workspace(who, ws, ws_bytes, wgrad_ws_bytes(p, kCoordChannels, c_out));
   if (rc) return rc;
   C2 a = {};
   a.x = sat, a.xc = x_coords, a.yc = y_coords;

@@ -17,13 +17,13 @@
 // epilogue may gate dx by the layer input (> 0).  The first layer reads frames 0..n_frames-1 of sat_data [B][T][H][W][1]
 // in place and computes the five extra channels while staging (forward and weight gradient).  wgrad splits the tiles
 // into fixed slabs, each block writing its partial sums to its own workspace slab, then adds the slabs in index order:
-// no atomics, identical bits run to run.
-#include "pv_common.h"
+// no atomics, identical bits run to run.  The slab sum, the synthesised channels and the shared argument checks are in
+// conv2d_f32_common.h.
+#include "conv2d_f32_common.h"
 
 namespace pv {
 namespace {
 
-constexpr int kBlock = 256;   // 4 waves
 constexpr int kM = 144;       // output channels of every layer
 constexpr uint8_t kDead = 255;
 
@@ -31,8 +31,6 @@ constexpr uint8_t kDead = 255;
 constexpr int kFwdMT = 3, kFwdNTW = 2, kFwdCC = 12, kFwdPos = 4 * kFwdNTW * 16;   // 128 positions per block
 // wgrad: CC input channels per chunk -> 126 (ci, tap) columns + a ones column + a zero column = 8 tiles, 2 per wave
 constexpr int kWgCC = 14, kWgNTW = 2, kWgMT = kM / 16, kWgPos = 84;
-
-typedef __attribute__((ext_vector_type(4))) float acc4;
 
 enum Src { SRC_PLAIN = 0, SRC_SAT = 1, SRC_POOLED = 2 };
 
@@ -49,27 +47,14 @@ struct In {
   int c_in, h, w, ph, pw, t_total, n_frames;
 };
 
-// The five synthesised channels of experiments/001...py:278-301 at row r, column c (k = 0..4).  The reference takes the
-// centre and the pixel ramps from the row count (`width`, :266-267) on both axes.
-__device__ __forceinline__ float synth_channel(int k, int r, int c, int h, const float* xc_b, const float* yc_b) {
-  switch (k) {
-    case 0: {   // centre marker: 1 on rows and columns [h//2 - 2, h//2 + 2)
-      const int hw = h / 2;
-      return (r >= hw - 2 && r < hw + 2 && c >= hw - 2 && c < hw + 2) ? 1.0f : 0.0f;
-    }
-    case 1: return __fdiv_rn(xc_b[c] - 309000.0f, 316387.42073603f);   // (x - SAT_X_MEAN) / SAT_X_STD in f32
-    case 2: return __fdiv_rn(yc_b[r] - 519000.0f, 406454.17945938f);   // (y - SAT_Y_MEAN) / SAT_Y_STD in f32
-    case 3: return __fdiv_rn((float)(c - 64), 37.0f);                  // (arange - 64) / 37 along the last axis
-    default: return __fdiv_rn((float)(r - 64), 37.0f);                 // ... and along rows
-  }
-}
-
 // input channel ch (0 <= ch < c_in) of image n at (r, c), which the caller has checked lies inside [0, h) x [0, w)
 template <int SRC>
 __device__ __forceinline__ float load_in(const In& s, int n, int ch, int r, int c) {
   if (SRC == SRC_SAT) {
     if (ch < s.n_frames) return s.x[(((size_t)n * s.t_total + ch) * s.h + r) * s.w + c];
-    return synth_channel(ch - s.n_frames, r, c, s.h, s.xc + (size_t)n * s.w, s.yc + (size_t)n * s.h);
+    // the channels of experiments/001...py:278-301.  The reference takes the centre and the pixel ramps from the row count
+    // (`width`, :266-267) on both axes, so the centre is (h / 2, h / 2).
+    return synth_channel(ch - s.n_frames, r, c, s.h / 2, s.h / 2, s.xc + (size_t)n * s.w, s.yc + (size_t)n * s.h);
   } else if (SRC == SRC_POOLED) {
     const int pr = r / 3, pc = c / 3;
     if (pr >= s.ph || pc >= s.pw) return 0.0f;
@@ -326,35 +311,6 @@ __global__ __launch_bounds__(kBlock) void conv144_wgrad(Wg q) {
   }
 }
 
-// dw[co][j] = sum_s slabs[s][co][j] (j < k9), dbias[co] = sum_s slabs[s][co][k9] in a fixed order: block = 32 elements x 8
-// slab groups; group g adds slabs g, g + 8, ... into four interleaved partial sums, then the four and the 8 groups'
-// results are added in index order.
-constexpr int kSumElems = 32, kSumGroups = kBlock / kSumElems;
-__global__ __launch_bounds__(kBlock) void conv144_slab_sum(const float* __restrict__ slabs, float* __restrict__ dw,
-                                                           float* __restrict__ db, int k9, int n_slabs) {
-  __shared__ float part[kSumGroups][kSumElems];
-  const int ncols = k9 + 1, total = kM * ncols;
-  const int le = threadIdx.x % kSumElems, g = threadIdx.x / kSumElems;
-  const int e = blockIdx.x * kSumElems + le;
-  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (e < total) {
-    int i = g;
-    for (; i + 3 * kSumGroups < n_slabs; i += 4 * kSumGroups)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s[u] += slabs[(size_t)(i + u * kSumGroups) * total + e];
-    for (; i < n_slabs; i += kSumGroups) s[0] += slabs[(size_t)i * total + e];
-  }
-  part[g][le] = (s[0] + s[1]) + (s[2] + s[3]);
-  __syncthreads();
-  if (g != 0 || e >= total) return;
-  float t = part[0][le];
-#pragma unroll
-  for (int j = 1; j < kSumGroups; ++j) t += part[j][le];
-  const int co = e / ncols, j = e - co * ncols;
-  if (j < k9) dw[co * k9 + j] = t;
-  else db[co] = t;
-}
-
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
 constexpr int kMaxSatFrames = 27;     // c_in = n_frames + 5 <= 32
@@ -413,14 +369,12 @@ WgPlan wg_plan(int n, int c_in, int h_out, int w_out) {
 }
 
 int check_common(const char* who, int n, int c_in, int c_out, int h_in, int w_in, bool pooled) {
-  PV_REQUIRE(n > 0 && c_in > 0 && c_out > 0, PV_EINVAL, "%s: non-positive dimension", who);
+  int rc = check_conv_dims(who, n, c_in, c_out, h_in, w_in);
+  if (rc) return rc;
   PV_REQUIRE(c_out == kM, PV_ESIZE, "%s: unsupported channel count c_out=%d (144)", who, c_out);
-  PV_REQUIRE(h_in >= 3 && w_in >= 3, PV_ESIZE, "%s: spatial extent %d x %d smaller than the 3x3 kernel", who, h_in, w_in);
   if (pooled)
     PV_REQUIRE(h_in >= 5 && w_in >= 5, PV_ESIZE, "%s: spatial extent %d x %d gives no whole 3x3 pool window", who, h_in,
                w_in);
-  PV_REQUIRE((long long)n * std::max(c_in, c_out) * h_in * w_in < (1LL << 31), PV_ESIZE,
-             "%s: tensor beyond 2^31 elements (32-bit indexing)", who);
   return PV_OK;
 }
 
@@ -473,17 +427,16 @@ int run_fwd(const char* who, Fwd a, int n, hipStream_t st) {
 template <int SRC, int DSRC>
 int run_wgrad(const char* who, const In& in, const In& dy, const WgPlan& p, float* dw, float* db, void* ws,
               size_t ws_bytes, hipStream_t st) {
-  PV_REQUIRE(ws && ws_bytes >= p.ws, PV_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, p.ws);
+  int rc = check_workspace(who, ws, ws_bytes, p.ws);
+  if (rc) return rc;
   Wg q;
   q.in = in, q.dy = dy, q.slabs = (float*)ws;
   q.h_out = p.h_out, q.w_out = p.w_out, q.tr = p.tr, q.tc = p.tc, q.n_rb = p.n_rb, q.n_cb = p.n_cb;
   q.items = p.items, q.per = p.per;
   conv144_wgrad<SRC, DSRC><<<dim3((unsigned)p.n_slabs, (unsigned)p.n_chunks), dim3(kBlock), p.lds, st>>>(q);
-  int rc = check_launch(who);
+  rc = check_launch(who);
   if (rc) return rc;
-  const int total = kM * (in.c_in * 9 + 1);
-  conv144_slab_sum<<<dim3((unsigned)((total + kSumElems - 1) / kSumElems)), dim3(kBlock), 0, st>>>((const float*)ws, dw, db,
-                                                                                            in.c_in * 9, p.n_slabs);
+  launch_slab_sum(ws, dw, db, kM, in.c_in * 9, p.n_slabs, st);
   return check_launch(who);
 }
 

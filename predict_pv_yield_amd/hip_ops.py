@@ -1008,12 +1008,21 @@ def conv3d_general_bwd_weight_f32(x, dy, y_mask, weight_shape, stride=1, padding
 
 
 # ------------------------------------------------------------------------------------------------
-# Conv2d 3x3 "valid" (experiments/002_cnn_processes_single_sat_image_then_rnn.py), exact f32
+# Conv2d 3x3 "valid", exact f32: conv2d_* for experiments/002_cnn_processes_single_sat_image_then_rnn.py (17 / 32 -> 32 / 4
+# channels), conv2d144_* for experiments/001_CNN_concat_all_timesteps_as_channels.py (144 -> 144, + MaxPool2d(3))
 # ------------------------------------------------------------------------------------------------
+C144 = 144
+
+
 def _f32_contig(*ts):
     for t in ts:
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
             raise TypeError("conv2d kernels take contiguous float32 tensors")
+
+
+def _u8_contig(who, codes):
+    if codes.dtype != torch.uint8 or not codes.is_contiguous():
+        raise TypeError(f"{who}: codes must be a contiguous uint8 tensor")
 
 
 def _shape_check(ok, who, msg):
@@ -1021,18 +1030,111 @@ def _shape_check(ok, who, msg):
         raise ValueError(f"{who}: {msg}")
 
 
-def _check_coords(who, sat, x_coords, y_coords, t_per_example):
-    n, h, w, c = sat.shape
-    _shape_check(c == 12 and t_per_example > 0 and n % t_per_example == 0, who,
-                 f"sat [N, H, W, 12] with N a multiple of t_per_example={t_per_example}, got {tuple(sat.shape)}")
-    b = n // t_per_example
+def _check_bias(who, bias, c_out):
+    if bias is not None and tuple(bias.shape) != (c_out,):
+        raise ValueError(f"{who}: bias [{c_out}] expected, got {tuple(bias.shape)}")
+
+
+def _check_xy_coords(who, x_coords, y_coords, b, h, w):
     _shape_check(tuple(x_coords.shape) == (b, w) and tuple(y_coords.shape) == (b, h), who,
                  f"x_coords [{b}, {w}] and y_coords [{b}, {h}] expected, got {tuple(x_coords.shape)} / {tuple(y_coords.shape)}")
 
 
-def _check_bias(who, bias, c_out):
-    if bias is not None and tuple(bias.shape) != (c_out,):
-        raise ValueError(f"{who}: bias [{c_out}] expected, got {tuple(bias.shape)}")
+def _check_coords(who, sat, x_coords, y_coords, t_per_example):
+    n, h, w, c = sat.shape
+    _shape_check(c == 12 and t_per_example > 0 and n % t_per_example == 0, who,
+                 f"sat [N, H, W, 12] with N a multiple of t_per_example={t_per_example}, got {tuple(sat.shape)}")
+    _check_xy_coords(who, x_coords, y_coords, n // t_per_example, h, w)
+
+
+def _check_sat001(who, sat, x_coords, y_coords, n_frames):
+    _shape_check(sat.dim() == 5 and sat.shape[4] == 1, who, f"sat_data [B, T, H, W, 1] expected, got {tuple(sat.shape)}")
+    b, t, h, w, _ = sat.shape
+    _shape_check(0 < n_frames <= t, who, f"n_frames={n_frames} must lie in 1..T={t}")
+    _shape_check(h >= 5 and w >= 5, who, f"images of at least 5 x 5 expected, got {h} x {w}")
+    _check_xy_coords(who, x_coords, y_coords, b, h, w)
+    return b, t, h, w
+
+
+def _check_c32(who, x_shape, weight_shape):
+    n, ci, h, w = x_shape
+    _shape_check(len(weight_shape) == 4 and tuple(weight_shape[1:]) == (ci, 3, 3), who,
+                 f"weight [C_out, {ci}, 3, 3] expected for x {tuple(x_shape)}, got {tuple(weight_shape)}")
+
+
+def _check_c144(who, x_shape, weight_shape, pooled=False):
+    _shape_check(len(x_shape) == 4 and x_shape[1] == C144, who, f"x [N, 144, H, W] expected, got {tuple(x_shape)}")
+    _shape_check(tuple(weight_shape) == (C144, C144, 3, 3), who, f"weight [144, 144, 3, 3] expected, got {tuple(weight_shape)}")
+    lo = 5 if pooled else 3
+    _shape_check(x_shape[2] >= lo and x_shape[3] >= lo, who, f"images of at least {lo} x {lo} expected, got {tuple(x_shape)}")
+
+
+def _pooled_shape(n, h, w):
+    return (n, C144, (h - 2) // 3, (w - 2) // 3)
+
+
+def _wgrad_ws(family, device, *dims):
+    """(buffer, bytes) for pv_{family}_bwd_weight_*.  Each family keeps its own workspace key: a captured graph pins
+    workspaces by key."""
+    query = f"pv_{family}_bwd_weight_workspace_bytes"
+    nbytes = ctypes.c_size_t(0)
+    check(getattr(get_lib(), query)(*dims, ctypes.byref(nbytes)), query)
+    return _workspace(f"{family}_wgrad", nbytes.value, device), nbytes.value
+
+
+def _grads_out(weight_shape, device):
+    return (torch.empty(tuple(weight_shape), dtype=torch.float32, device=device),
+            torch.empty((weight_shape[0],), dtype=torch.float32, device=device))
+
+
+# the plain passes of both families ("conv2d", "conv2d144"): check_channels(who, x_shape, weight_shape) is the family's
+# channel-count check, the rest is the same for both
+def _conv_fwd(family, check_channels, x, weight, bias, relu):
+    who = f"{family}_fwd_f32"
+    check_channels(who, x.shape, weight.shape)
+    n, ci, h, w = x.shape
+    co = weight.shape[0]
+    _check_bias(who, bias, co)
+    require_cuda(x, weight, bias)
+    _f32_contig(x, weight, bias)
+    y = torch.empty((n, co, h - 2, w - 2), dtype=torch.float32, device=x.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, int(relu),
+                                          current_stream_ptr()), "pv_" + who)
+    return y
+
+
+def _conv_bwd_data(family, check_channels, dy, dy_gate, weight, x_gate, x_shape):
+    who = f"{family}_bwd_data_f32"
+    check_channels(who, x_shape, weight.shape)
+    n, ci, h, w = x_shape
+    y_shape = (n, weight.shape[0], h - 2, w - 2)
+    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
+                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
+    require_cuda(dy, dy_gate, weight, x_gate)
+    _f32_contig(dy, dy_gate, weight, x_gate)
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci, weight.shape[0],
+                                          h, w, current_stream_ptr()), "pv_" + who)
+    return dx
+
+
+def _conv_bwd_weight(family, check_channels, x, dy, dy_gate, weight_shape, ws_args=()):
+    """ws_args: the workspace query's arguments after (n, c_in, c_out, h, w)."""
+    who = f"{family}_bwd_weight_f32"
+    check_channels(who, x.shape, weight_shape)
+    n, ci, h, w = x.shape
+    co = weight_shape[0]
+    y_shape = (n, co, h - 2, w - 2)
+    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
+                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    require_cuda(x, dy, dy_gate)
+    _f32_contig(x, dy, dy_gate)
+    ws, nbytes = _wgrad_ws(family, x.device, n, ci, co, h, w, *ws_args)
+    dw, db = _grads_out(weight_shape, x.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, ptr(ws), nbytes,
+                                          current_stream_ptr()), "pv_" + who)
+    return dw, db
 
 
 def conv2d_coords_fwd_f32(sat, x_coords, y_coords, weight, bias, t_per_example):
@@ -1053,61 +1155,17 @@ def conv2d_coords_fwd_f32(sat, x_coords, y_coords, weight, bias, t_per_example):
 
 
 def conv2d_fwd_f32(x, weight, bias, relu=True):
-    n, ci, h, w = x.shape
-    _shape_check(weight.dim() == 4 and tuple(weight.shape[1:]) == (ci, 3, 3), "conv2d_fwd_f32",
-                 f"weight [C_out, {ci}, 3, 3] expected for x {tuple(x.shape)}, got {tuple(weight.shape)}")
-    co = weight.shape[0]
-    _check_bias("conv2d_fwd_f32", bias, co)
-    require_cuda(x, weight, bias)
-    _f32_contig(x, weight, bias)
-    y = torch.empty((n, co, h - 2, w - 2), dtype=torch.float32, device=x.device)
-    check(get_lib().pv_conv2d_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, int(relu),
-                                      current_stream_ptr()), "pv_conv2d_fwd_f32")
-    return y
+    return _conv_fwd("conv2d", _check_c32, x, weight, bias, relu)
 
 
 def conv2d_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
     """dx of a 3x3 valid conv; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
-    n, ci, h, w = x_shape
-    who = "conv2d_bwd_data_f32"
-    _shape_check(weight.dim() == 4 and tuple(weight.shape[1:]) == (ci, 3, 3), who,
-                 f"weight [C_out, {ci}, 3, 3] expected for x {tuple(x_shape)}, got {tuple(weight.shape)}")
-    y_shape = (n, weight.shape[0], h - 2, w - 2)
-    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
-                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
-    require_cuda(dy, dy_gate, weight, x_gate)
-    _f32_contig(dy, dy_gate, weight, x_gate)
-    dx = torch.empty(x_shape, dtype=torch.float32, device=dy.device)
-    check(get_lib().pv_conv2d_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci,
-                                           weight.shape[0], h, w, current_stream_ptr()), "pv_conv2d_bwd_data_f32")
-    return dx
-
-
-def _conv2d_wgrad_ws(n, ci, co, h, w, device):
-    nbytes = ctypes.c_size_t(0)
-    check(get_lib().pv_conv2d_bwd_weight_workspace_bytes(n, ci, co, h, w, ctypes.byref(nbytes)),
-          "pv_conv2d_bwd_weight_workspace_bytes")
-    return _workspace("conv2d_wgrad", nbytes.value, device), nbytes.value
+    return _conv_bwd_data("conv2d", _check_c32, dy, dy_gate, weight, x_gate, x_shape)
 
 
 def conv2d_bwd_weight_f32(x, dy, dy_gate, weight_shape):
     """(dw, dbias) of a 3x3 valid conv; deterministic (fixed slab split over images, slabs summed in order)."""
-    n, ci, h, w = x.shape
-    co = weight_shape[0]
-    y_shape = (n, co, h - 2, w - 2)
-    _shape_check(tuple(weight_shape) == (co, ci, 3, 3) and tuple(dy.shape) == y_shape
-                 and (dy_gate is None or tuple(dy_gate.shape) == y_shape), "conv2d_bwd_weight_f32",
-                 f"weight {(co, ci, 3, 3)} and dy / dy_gate {y_shape} expected for x {tuple(x.shape)}, got "
-                 f"{tuple(weight_shape)} / {tuple(dy.shape)}")
-    require_cuda(x, dy, dy_gate)
-    _f32_contig(x, dy, dy_gate)
-    ws, nbytes = _conv2d_wgrad_ws(n, ci, co, h, w, x.device)
-    dw = torch.empty(tuple(weight_shape), dtype=torch.float32, device=x.device)
-    db = torch.empty((co,), dtype=torch.float32, device=x.device)
-    check(get_lib().pv_conv2d_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, ptr(ws),
-                                             nbytes, current_stream_ptr()), "pv_conv2d_bwd_weight_f32")
-    return dw, db
+    return _conv_bwd_weight("conv2d", _check_c32, x, dy, dy_gate, weight_shape)
 
 
 def conv2d_coords_bwd_weight_f32(sat, x_coords, y_coords, dy, t_per_example, weight_shape):
@@ -1121,45 +1179,12 @@ def conv2d_coords_bwd_weight_f32(sat, x_coords, y_coords, dy, t_per_example, wei
                  f"{tuple(dy.shape)}")
     require_cuda(sat, x_coords, y_coords, dy)
     _f32_contig(sat, x_coords, y_coords, dy)
-    ws, nbytes = _conv2d_wgrad_ws(n, 17, co, h, w, sat.device)
-    dw = torch.empty(tuple(weight_shape), dtype=torch.float32, device=sat.device)
-    db = torch.empty((co,), dtype=torch.float32, device=sat.device)
+    ws, nbytes = _wgrad_ws("conv2d", sat.device, n, 17, co, h, w)
+    dw, db = _grads_out(weight_shape, sat.device)
     check(get_lib().pv_conv2d_coords_bwd_weight_f32(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(dy), ptr(dw), ptr(db), n,
                                                     t_per_example, h, w, co, ptr(ws), nbytes, current_stream_ptr()),
           "pv_conv2d_coords_bwd_weight_f32")
     return dw, db
-
-
-# ------------------------------------------------------------------------------------------------
-# Conv2d 3x3 144 -> 144 (+ MaxPool2d(3)) (experiments/001_CNN_concat_all_timesteps_as_channels.py), exact f32
-# ------------------------------------------------------------------------------------------------
-C144 = 144
-
-
-def _u8_contig(who, codes):
-    if codes.dtype != torch.uint8 or not codes.is_contiguous():
-        raise TypeError(f"{who}: codes must be a contiguous uint8 tensor")
-
-
-def _pooled_shape(n, h, w):
-    return (n, C144, (h - 2) // 3, (w - 2) // 3)
-
-
-def _check_sat001(who, sat, x_coords, y_coords, n_frames):
-    _shape_check(sat.dim() == 5 and sat.shape[4] == 1, who, f"sat_data [B, T, H, W, 1] expected, got {tuple(sat.shape)}")
-    b, t, h, w, _ = sat.shape
-    _shape_check(0 < n_frames <= t, who, f"n_frames={n_frames} must lie in 1..T={t}")
-    _shape_check(h >= 5 and w >= 5, who, f"images of at least 5 x 5 expected, got {h} x {w}")
-    _shape_check(tuple(x_coords.shape) == (b, w) and tuple(y_coords.shape) == (b, h), who,
-                 f"x_coords [{b}, {w}] and y_coords [{b}, {h}] expected, got {tuple(x_coords.shape)} / {tuple(y_coords.shape)}")
-    return b, t, h, w
-
-
-def _check_c144(who, x_shape, weight_shape, pooled):
-    _shape_check(len(x_shape) == 4 and x_shape[1] == C144, who, f"x [N, 144, H, W] expected, got {tuple(x_shape)}")
-    _shape_check(tuple(weight_shape) == (C144, C144, 3, 3), who, f"weight [144, 144, 3, 3] expected, got {tuple(weight_shape)}")
-    lo = 5 if pooled else 3
-    _shape_check(x_shape[2] >= lo and x_shape[3] >= lo, who, f"images of at least {lo} x {lo} expected, got {tuple(x_shape)}")
 
 
 def conv2d144_sat_pool_fwd_f32(sat, x_coords, y_coords, weight, bias, n_frames):
@@ -1198,33 +1223,12 @@ def conv2d144_pool_fwd_f32(x, weight, bias):
 
 def conv2d144_fwd_f32(x, weight, bias, relu=True):
     """conv2d(x, weight) + bias (+ ReLU) for x [N, 144, H, W] -> [N, 144, H-2, W-2]."""
-    who = "conv2d144_fwd_f32"
-    _check_c144(who, x.shape, weight.shape, False)
-    _check_bias(who, bias, C144)
-    require_cuda(x, weight, bias)
-    _f32_contig(x, weight, bias)
-    n, c, h, w = x.shape
-    y = torch.empty((n, C144, h - 2, w - 2), dtype=torch.float32, device=x.device)
-    check(get_lib().pv_conv2d144_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), n, c, C144, h, w, int(relu),
-                                         current_stream_ptr()), "pv_conv2d144_fwd_f32")
-    return y
+    return _conv_fwd("conv2d144", _check_c144, x, weight, bias, relu)
 
 
 def conv2d144_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
     """dx of conv2d144_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
-    who = "conv2d144_bwd_data_f32"
-    _check_c144(who, x_shape, weight.shape, False)
-    n, c, h, w = x_shape
-    y_shape = (n, C144, h - 2, w - 2)
-    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
-                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
-    require_cuda(dy, dy_gate, weight, x_gate)
-    _f32_contig(dy, dy_gate, weight, x_gate)
-    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
-    check(get_lib().pv_conv2d144_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, c, C144, h, w,
-                                              current_stream_ptr()), "pv_conv2d144_bwd_data_f32")
-    return dx
+    return _conv_bwd_data("conv2d144", _check_c144, dy, dy_gate, weight, x_gate, x_shape)
 
 
 def conv2d144_pool_bwd_data_f32(dy_pooled, codes, weight, x_gate, x_shape):
@@ -1245,33 +1249,9 @@ def conv2d144_pool_bwd_data_f32(dy_pooled, codes, weight, x_gate, x_shape):
     return dx
 
 
-def _conv2d144_wgrad_ws(n, ci, h, w, pooled, device):
-    nbytes = ctypes.c_size_t(0)
-    check(get_lib().pv_conv2d144_bwd_weight_workspace_bytes(n, ci, C144, h, w, int(pooled), ctypes.byref(nbytes)),
-          "pv_conv2d144_bwd_weight_workspace_bytes")
-    return _workspace("conv2d144_wgrad", nbytes.value, device), nbytes.value
-
-
-def _grads_out(ci, device):
-    return (torch.empty((C144, ci, 3, 3), dtype=torch.float32, device=device),
-            torch.empty((C144,), dtype=torch.float32, device=device))
-
-
 def conv2d144_bwd_weight_f32(x, dy, dy_gate, weight_shape):
     """(dw, dbias) of conv2d144_fwd_f32; deterministic (fixed slabs summed in order)."""
-    who = "conv2d144_bwd_weight_f32"
-    _check_c144(who, x.shape, weight_shape, False)
-    n, c, h, w = x.shape
-    y_shape = (n, C144, h - 2, w - 2)
-    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
-                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    require_cuda(x, dy, dy_gate)
-    _f32_contig(x, dy, dy_gate)
-    ws, nbytes = _conv2d144_wgrad_ws(n, c, h, w, False, x.device)
-    dw, db = _grads_out(c, x.device)
-    check(get_lib().pv_conv2d144_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, c, C144, h, w, ptr(ws),
-                                                nbytes, current_stream_ptr()), "pv_conv2d144_bwd_weight_f32")
-    return dw, db
+    return _conv_bwd_weight("conv2d144", _check_c144, x, dy, dy_gate, weight_shape, ws_args=(0,))
 
 
 def conv2d144_pool_bwd_weight_f32(x, dy_pooled, codes, weight_shape):
@@ -1285,8 +1265,8 @@ def conv2d144_pool_bwd_weight_f32(x, dy_pooled, codes, weight_shape):
     require_cuda(x, dy_pooled, codes)
     _f32_contig(x, dy_pooled)
     _u8_contig(who, codes)
-    ws, nbytes = _conv2d144_wgrad_ws(n, c, h, w, True, x.device)
-    dw, db = _grads_out(c, x.device)
+    ws, nbytes = _wgrad_ws("conv2d144", x.device, n, c, C144, h, w, 1)
+    dw, db = _grads_out((C144, c, 3, 3), x.device)
     check(get_lib().pv_conv2d144_pool_bwd_weight_f32(ptr(x), ptr(dy_pooled), ptr(codes), ptr(dw), ptr(db), n, c, C144, h,
                                                      w, ptr(ws), nbytes, current_stream_ptr()),
           "pv_conv2d144_pool_bwd_weight_f32")
@@ -1303,8 +1283,8 @@ def conv2d144_sat_pool_bwd_weight_f32(sat, x_coords, y_coords, dy_pooled, codes,
     require_cuda(sat, x_coords, y_coords, dy_pooled, codes)
     _f32_contig(sat, x_coords, y_coords, dy_pooled)
     _u8_contig(who, codes)
-    ws, nbytes = _conv2d144_wgrad_ws(b, n_frames + 5, h, w, True, sat.device)
-    dw, db = _grads_out(n_frames + 5, sat.device)
+    ws, nbytes = _wgrad_ws("conv2d144", sat.device, b, n_frames + 5, C144, h, w, 1)
+    dw, db = _grads_out((C144, n_frames + 5, 3, 3), sat.device)
     check(get_lib().pv_conv2d144_sat_pool_bwd_weight_f32(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(dy_pooled), ptr(codes),
                                                          ptr(dw), ptr(db), b, t, n_frames, h, w, C144, ptr(ws), nbytes,
                                                          current_stream_ptr()), "pv_conv2d144_sat_pool_bwd_weight_f32")

@@ -7,7 +7,7 @@ follow (centre marker, normalised geo x / y, pixel x / y: :278-301), and three 3
 reference's flatten order).  fc1 (-> 256), then the head: fc1's output, the PV history, the flattened NWP [10, 19, 2, 2],
 four datetime features x 19 and the PV-system embedding (1 115 values) through fc2..fc5 to forecast yields.  Loss = NMAE,
 metrics MSE / NMAE for Train and Validation (:352-364), Adam lr 0.001 (:378-380).  The experiment trains in f32
-(pl.Trainer(gpus=1)): every product here is exact f32 (conv2d_pool_functional on csrc/conv2d_pool_f32.hip, fc layers and
+(pl.Trainer(gpus=1)): every product here is exact f32 (conv2d_functional on csrc/conv2d_pool_f32.hip, fc layers and
 embedding on the f32 kernels of experiment 003).
 
 Same constructor (history_len, forecast_len), attribute / state_dict names and batch keys.  NWP_SIZE, N_DATETIME_FEATURES and
@@ -69,7 +69,7 @@ class LitAutoEncoder(LightningModule):
 
     def forward(self, x):
         from ... import functional as Fn
-        from ...conv2d_pool_functional import sat_encoder001_f32
+        from ...conv2d_functional import sat_encoder001_f32
         # ******************* Satellite imagery *************************
         # Shape: batch_size, seq_length, width, height, channel
         sat_data = x["sat_data"]

@@ -17,6 +17,7 @@ All arithmetic runs in the gfx950 kernels behind include/pv_yield_hip.h; there i
 import torch
 from torch import nn
 
+from ...data.seeded import SeededBatchDataset, make_fake_sat_batch
 from ...lightning import LightningModule
 from .perceiver_core import Perceiver
 
@@ -152,30 +153,9 @@ class LitModel(LightningModule):
 def make_fake_exp003_batch(batch_size: int = 32, image_size_pixels: int = 128, generator=None, history_len=params["history_len"],
                            forecast_len=params["forecast_len"]):
     """Synthetic dict batch with the experiment's keys and shapes (experiments/003...py:139-203)."""
-    g = generator
-    t = history_len + forecast_len + 1
-    phase = torch.rand(batch_size, 1, generator=g) * 6.2831853
-    steps = torch.arange(t, dtype=torch.float32)[None] * 0.02
-    return {
-        "sat_data": torch.randn(batch_size, t, image_size_pixels, image_size_pixels, len(params["sat_channels"]), generator=g),
-        "pv_system_row_number": torch.randint(0, 940, (batch_size,), generator=g),
-        "nwp": torch.randn(batch_size, len(params["nwp_channels"]), t, 2, 2, generator=g),
-        "hour_of_day_sin": torch.sin(phase + steps), "hour_of_day_cos": torch.cos(phase + steps),
-        "day_of_year_sin": torch.sin(phase * 0.5 + steps * 0.01), "day_of_year_cos": torch.cos(phase * 0.5 + steps * 0.01),
-        "pv_yield": torch.rand(batch_size, t, generator=g),
-    }
+    return make_fake_sat_batch(batch_size, image_size_pixels, len(params["sat_channels"]), generator, False, history_len,
+                               forecast_len)
 
 
-class FakeExp003Dataset(torch.utils.data.Dataset):
-    """Each item is a whole seeded batch (DataLoader(batch_size=None)), like the experiment's own loaders."""
-
-    def __init__(self, batch_size: int = 32, image_size_pixels: int = 128, length: int = 4, seed: int = 1234):
-        self.batch_size, self.image_size_pixels, self.length, self.seed = batch_size, image_size_pixels, length, seed
-
-    def __len__(self):
-        return self.length
-
-    def __getitem__(self, idx):
-        if idx >= self.length:
-            raise IndexError(idx)
-        return make_fake_exp003_batch(self.batch_size, self.image_size_pixels, torch.Generator().manual_seed(self.seed + idx))
+class FakeExp003Dataset(SeededBatchDataset):
+    make_batch = staticmethod(make_fake_exp003_batch)

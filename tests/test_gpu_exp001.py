@@ -11,7 +11,6 @@ maximum, dead windows have a maximum within the tolerance of <= 0 -- and the flo
 kernel's own codes.  Against the reference's golden, computed with torch CPU's picks, the two gradients below a pool
 (sat_conv1, sat_conv2) are held to ROUTED_TOL instead: one differing pick among the ~10^5 windows moves them by ~1e-3.
 """
-import importlib.util
 import os
 import subprocess
 import sys
@@ -21,43 +20,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv2d_f32_helpers import ELEM_TOL, NORM_TOL, ROOT, _golden_module, _ops, _rel, _to, _within
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "exp001_small.npz")
-ELEM_TOL = 1e-6      # per element, relative to its sum of |products|
-NORM_TOL = 1e-5      # relative norm of a reduction (weight / bias gradient)
 ROUTED_TOL = 2e-2    # gradients below a pool against another implementation's picks (golden only)
 DEAD = 255
-
-
-def _golden_module():
-    spec = importlib.util.spec_from_file_location("make_exp001_golden", os.path.join(ROOT, "tests", "golden",
-                                                                                     "make_exp001_golden.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def _rel(a, b):
-    a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
-
-
-def _within(got, ref64, absref64, tol=ELEM_TOL, what=""):
-    err = (got.double().cpu() - ref64).abs()
-    bound = tol * absref64 + 1e-30
-    worst = (err / bound).max().item()
-    assert worst <= 1.0, f"{what}: error {worst:.2f} x the bound {tol} x sum|products|"
-
-
-def _to(batch, device):
-    return {k: v.to(device) for k, v in batch.items()}
-
-
-def _ops():
-    from predict_pv_yield_amd import hip_ops as K
-    return K
 
 
 def _windows(z, ph, pw):
@@ -254,7 +223,7 @@ def _model_from(params_np, device):
 
 
 def test_model_against_the_reference_golden(device):
-    gm = _golden_module()
+    gm = _golden_module("exp001")
     gold = np.load(GOLDEN)
     from predict_pv_yield_amd.models.conv2d.exp001 import LitAutoEncoder
     shapes = {k: tuple(v.shape) for k, v in LitAutoEncoder().state_dict().items()}

@@ -6,7 +6,6 @@ from torch: an output element's error is then a few ulp of its sum of |products|
 depths, K <= 288), so each element is held to 1e-6 of its own sum of |products|, computed alongside in float64.  The weight
 gradients add up to 600 000 products per element: held to 1e-5 relative norm against float64.
 """
-import importlib.util
 import os
 import subprocess
 import sys
@@ -16,41 +15,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv2d_f32_helpers import NORM_TOL, ROOT, _golden_module, _ops, _rel, _to, _within
+
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "exp002_small.npz")
-ELEM_TOL = 1e-6      # per element, relative to its sum of |products|
-NORM_TOL = 1e-5      # relative norm of a reduction (weight / bias gradient)
-
-
-def _golden_module():
-    spec = importlib.util.spec_from_file_location("make_exp002_golden", os.path.join(ROOT, "tests", "golden",
-                                                                                     "make_exp002_golden.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def _rel(a, b):
-    a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
-
-
-def _within(got, ref64, absref64, tol=ELEM_TOL, what=""):
-    err = (got.double().cpu() - ref64).abs()
-    bound = tol * absref64 + 1e-30
-    worst = (err / bound).max().item()
-    assert worst <= 1.0, f"{what}: error {worst:.2f} x the bound {tol} x sum|products|"
-
-
-def _to(batch, device):
-    return {k: v.to(device) for k, v in batch.items()}
-
-
-def _ops():
-    from predict_pv_yield_amd import hip_ops as K
-    return K
 
 
 # ---- entry points against float64 torch.nn.functional.conv2d ------------------------------------------------------------
@@ -170,7 +139,7 @@ def _model_from(params_np, device):
 
 
 def test_model_against_the_reference_golden(device):
-    gm = _golden_module()
+    gm = _golden_module("exp002")
     gold = np.load(GOLDEN)
     from predict_pv_yield_amd.models.conv2d.exp002 import LitModel
     shapes = {k: tuple(v.shape) for k, v in LitModel().state_dict().items()}
