@@ -139,6 +139,34 @@ int pv_prepare_stacks_i16(const int16_t* raw, uint8_t* u8, float* out, int64_t b
 int pv_prepare_stacks_f32(const float* raw, uint8_t* u8, float* out, int64_t batch, int32_t t, int32_t c, int64_t frame,
                           int32_t t_out, int mode, const float* mean, const float* std_, int32_t* range_flag, void* stream);
 
+/* The join the reference leaves open -- `# TODO: Use optical flow, not actual sat images of the future!`
+ * (predict_pv_yield/models/perceiver/perceiver.py:118, perceiver_nwp_sat.py:117, perceiver_conv3d_nwp_sat.py:145,
+ * experiments/002_cnn_processes_single_sat_image_then_rnn.py:167, experiments/003_perceiver_processes_single_sat_image_
+ * then_rnn.py:155) -- for NORMALISED model input: the first t_obs time slices of f32 frames -> the planar u8 stacks
+ * [batch, C_out, t_obs, frame] pv_farneback_batch_u8 takes, in one pass.
+ *   src      : element (b, t, ch, pixel) at src + b*stride_b + t*stride_t + ch*stride_c + pixel*stride_px (elements), so
+ *              planar [B, C, T, H, W] (stride_px 1) and channels-last [B, T, H, W, C] (stride_c 1, stride_px C) are one call
+ *   channel  : -1 = every channel (C_out = c); i = channel i only (C_out = 1)
+ *   u8       = round_half_even(clamp(x * scale + 512, 0, 1020) / 4); the multiply and the add are separately rounded f32
+ *              operations, the rounding is pv_u8_from_10bit_f32's PV_U8_ROUND_DIV4.  Inputs are finite. */
+int pv_u8_stacks_from_normalised_f32(const float* src, int64_t stride_b, int64_t stride_t, int64_t stride_c, int64_t stride_px,
+                                     uint8_t* u8, int64_t batch, int32_t t_obs, int32_t c, int64_t frame, int32_t channel,
+                                     float scale, void* stream);
+
+/* pv_remap_bilinear_f32 (remap_image -> cv.remap, notebooks/13_...ipynb:259-281, optical_flow_1.ipynb:415-430; the
+ * `flow * forecast_step` schedule of :317-323) on channels-last frames, as experiments/002...py:167-174 and
+ * experiments/003...py:155-162 carry them ([B, T, W, H, 12] -> [B*T, W, H, 12]): same 1/32-px quantisation, weights, sum
+ * order and borders, bit for bit.
+ *   src  : [n_images][h, w, c]            frame i at src + i*src_image_stride (elements)
+ *   flow : f32 [n_images, c, h, w, 2]     field (i, ch) at flow + i*flow_image_stride + ch*flow_channel_stride;
+ *          flow_channel_stride = 0: one field [h, w, 2] per image shared by its c channels
+ *   dst  : [n_images][n_steps][h, w, c]   frame (i, s) at dst + i*dst_image_stride + s*dst_step_stride, step s samples
+ *          at (step0 + s) * flow */
+int pv_remap_bilinear_nhwc_f32(const float* src, int64_t src_image_stride, const float* flow, int64_t flow_image_stride,
+                               int64_t flow_channel_stride, float* dst, int64_t dst_image_stride, int64_t dst_step_stride,
+                               int64_t n_images, int32_t n_steps, float step0, int32_t h, int32_t w, int32_t c,
+                               int border_mode, float border_value, void* stream);
+
 /* replaces: satellite_data -= SAT_IMAGE_MEAN; satellite_data /= SAT_IMAGE_STD
  * (notebooks/13_...ipynb:345-346, 463-464; per-channel constants
  * predict_pv_yield/netcdf_dataset.py:19-32).  dst[i] = (src[i] − mean[c]) / std[c]

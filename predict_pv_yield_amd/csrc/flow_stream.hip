@@ -1,6 +1,7 @@
 // HBM-bound streaming stages of the optical-flow advection path:
 // u8 conversion, weighted mean of flow fields, per-channel normalisation and the cv.remap-exact
-// bilinear warp.  All kernels are grid-stride, 16 B per lane where the layout allows it.
+// bilinear warp (planar and channels-last frames), and the u8 stacks of normalised model input for the flow join of the
+// satellite models.  All kernels are grid-stride, 16 B per lane where the layout allows it.
 #include "pv_common.h"
 
 namespace pv {
@@ -556,6 +557,319 @@ static int prepare_stacks_launch(const T* raw, uint8_t* u8, float* out, int64_t 
   return check_launch("pv_prepare_stacks");
 }
 
+// ---------------------------------------------------------------------------------------------
+// Join prologue for NORMALISED model input (optical_flow.replace_future_frames_with_flow): the observed f32 frames, planar
+// [B, C, T, H, W] or channels-last [B, T, H, W, C] (element strides b / t / c / pixel), -> planar u8 stacks
+// [B, C_out, T_obs, frame] in one pass.  u8 = round_half_even(clamp(x * s + 512, 0, 1020) / 4): the multiply and the add are
+// two separately rounded f32 operations (the chain this replaces was a torch multiply, add and clamp in front of
+// u8_from_10bit_kernel), the rounding is u8_from_f32.  The clamp keeps every value inside 0..255: there is no range flag.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t u8_from_normalised(float x, float s) {
+  float v = __fadd_rn(__fmul_rn(x, s), 512.0f);
+  v = fminf(fmaxf(v, 0.0f), 1020.0f);
+  bool bad = false;
+  return (uint32_t)u8_from_f32(v, PV_U8_ROUND_DIV4, bad);
+}
+
+// pixel stride 1, frame % 8 == 0: a workgroup takes 256 x VPT vectors (8 pixels: 32 B in, 8 B out) of ONE output frame, so
+// (b, c, t) are wave-uniform and every load of a trip is issued before the first conversion (prepare_stacks_kernel's shape)
+__global__ __launch_bounds__(256) void u8_stacks_planar_kernel(const float* __restrict__ src, long long sb, long long st,
+                                                               long long sc, uint8_t* __restrict__ u8, long long n_frames,
+                                                               int t_obs, int c_out, int c0, int frame8, float s) {
+  const int bpf = (frame8 + 256 * PS_VPT - 1) / (256 * PS_VPT);
+  for (long long blk = blockIdx.x; blk < n_frames * bpf; blk += gridDim.x) {
+    const long long fr = blk / bpf;                 // output frame (b * c_out + co) * t_obs + t
+    const int px0 = (int)(blk - fr * bpf) * (256 * PS_VPT) + (int)threadIdx.x;
+    long long f = fr;
+    const int ti = (int)(f % t_obs);
+    f /= t_obs;
+    const int co = (int)(f % c_out);
+    const long long bi = f / c_out;
+    const float* in = src + bi * sb + ti * st + (long long)(c0 + co) * sc;
+    f32x4 ra[PS_VPT], rb[PS_VPT];
+#pragma unroll
+    for (int v = 0; v < PS_VPT; ++v) {
+      const int px = px0 + 256 * v;
+      if (px < frame8) {
+        ra[v] = *reinterpret_cast<const f32x4*>(in + (long long)px * 8);
+        rb[v] = *reinterpret_cast<const f32x4*>(in + (long long)px * 8 + 4);
+      }
+    }
+#pragma unroll
+    for (int v = 0; v < PS_VPT; ++v) {
+      const int px = px0 + 256 * v;
+      if (px >= frame8) continue;
+      uint32_t lo = 0, hi = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        lo |= u8_from_normalised(ra[v][j], s) << (8 * j);
+        hi |= u8_from_normalised(rb[v][j], s) << (8 * j);
+      }
+      const u32x2 o8 = {lo, hi};
+      *reinterpret_cast<u32x2*>(u8 + (fr * (long long)frame8 + px) * 8) = o8;
+    }
+  }
+}
+
+// channels-last, every channel: a (b, t) slab is frame x C contiguous floats.  A workgroup reads the C x 256-pixel tile of
+// one slab as one contiguous run (16 B per lane when C % 4 == 0), converts, transposes the bytes through LDS (row pitch 260 B:
+// the C bytes of a pixel land in consecutive banks) and writes each channel's 256 bytes as one contiguous run of its plane.
+constexpr int US_TILE = 256, US_PITCH = US_TILE + 4;
+template <int VEC>
+__global__ __launch_bounds__(256) void u8_stacks_nhwc_kernel(const float* __restrict__ src, long long sb, long long st,
+                                                             uint8_t* __restrict__ u8, long long n_slabs, int t_obs, int c,
+                                                             long long frame, float s, int store4) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  uint8_t* tile = lds_raw;                           // [c][US_PITCH]
+  const int tpf = (int)((frame + US_TILE - 1) / US_TILE);
+  for (long long blk = blockIdx.x; blk < n_slabs * tpf; blk += gridDim.x) {
+    const long long slab = blk / tpf;               // b * t_obs + t
+    const long long p0 = (blk - slab * tpf) * US_TILE;
+    const int np = (int)(frame - p0 < US_TILE ? frame - p0 : US_TILE);
+    const long long bi = slab / t_obs;
+    const int ti = (int)(slab - bi * t_obs);
+    const float* in = src + bi * sb + ti * st + p0 * c;
+    const int n_el = np * c;
+    if constexpr (VEC == 4) {
+      for (int e = (int)threadIdx.x * 4; e < n_el; e += 256 * 4) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(in + e);
+        const int p = e / c, ch = e - p * c;         // c % 4 == 0: the four values are channels ch..ch+3 of pixel p
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tile[(ch + j) * US_PITCH + p] = (uint8_t)u8_from_normalised(x[j], s);
+      }
+    } else {
+      for (int e = (int)threadIdx.x; e < n_el; e += 256) {
+        const int p = e / c, ch = e - p * c;
+        tile[ch * US_PITCH + p] = (uint8_t)u8_from_normalised(in[e], s);
+      }
+    }
+    __syncthreads();
+    uint8_t* out = u8 + (bi * c * t_obs + ti) * frame + p0;      // channel ch: + ch * t_obs * frame
+    if (store4) {                                    // frame % 4 == 0 and u8 4-byte aligned: np % 4 == 0
+      const int nq = np / 4;
+      for (int q = (int)threadIdx.x; q < c * nq; q += 256) {
+        const int ch = q / nq, pq = q - ch * nq;
+        *reinterpret_cast<uint32_t*>(out + (long long)ch * t_obs * frame + pq * 4) =
+            *reinterpret_cast<const uint32_t*>(tile + ch * US_PITCH + pq * 4);
+      }
+    } else {
+      for (int q = (int)threadIdx.x; q < c * np; q += 256) {
+        const int ch = q / np, p = q - ch * np;
+        out[(long long)ch * t_obs * frame + p] = tile[ch * US_PITCH + p];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// any strides (odd frame sizes, one channel of a channels-last tensor): one thread = VEC consecutive output pixels
+template <int VEC>
+__global__ __launch_bounds__(256) void u8_stacks_strided_kernel(const float* __restrict__ src, long long sb, long long st,
+                                                                long long sc, long long sp, uint8_t* __restrict__ u8,
+                                                                long long total, int t_obs, int c_out, int c0,
+                                                                long long frame, float s) {
+  const long long fq = frame / VEC;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const long long fr = i / fq;
+    const long long px = (i - fr * fq) * VEC;
+    long long f = fr;
+    const int ti = (int)(f % t_obs);
+    f /= t_obs;
+    const int co = (int)(f % c_out);
+    const long long bi = f / c_out;
+    const float* in = src + bi * sb + ti * st + (long long)(c0 + co) * sc + px * sp;
+    if constexpr (VEC == 4) {
+      uint32_t o = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o |= u8_from_normalised(in[j * sp], s) << (8 * j);
+      *reinterpret_cast<uint32_t*>(u8 + fr * frame + px) = o;
+    } else {
+      u8[fr * frame + px] = (uint8_t)u8_from_normalised(in[0], s);
+    }
+  }
+}
+
+static int u8_stacks_launch(const float* src, int64_t sb, int64_t st, int64_t sc, int64_t sp, uint8_t* u8, int64_t batch,
+                            int32_t t_obs, int32_t c, int64_t frame, int32_t channel, float scale, void* stream) {
+  const char* who = "pv_u8_stacks_from_normalised_f32";
+  PV_REQUIRE(src && u8, PV_EINVAL, "%s: null pointer", who);
+  PV_REQUIRE(batch > 0 && t_obs > 0 && c > 0 && frame > 0, PV_EINVAL, "%s: bad sizes batch=%lld t_obs=%d c=%d frame=%lld", who,
+             (long long)batch, t_obs, c, (long long)frame);
+  PV_REQUIRE(channel >= -1 && channel < c, PV_EINVAL, "%s: channel %d outside -1..%d", who, channel, c - 1);
+  PV_REQUIRE(sb >= 0 && st >= 0 && sc >= 0 && sp >= 1, PV_EINVAL, "%s: strides must be non-negative (pixel stride >= 1)", who);
+  PV_REQUIRE(scale == scale && fabsf(scale) < INFINITY, PV_EINVAL, "%s: scale must be finite", who);
+  const int c_out = channel < 0 ? c : 1, c0 = channel < 0 ? 0 : channel;
+  const long long n_frames = (long long)batch * c_out * t_obs;
+  PV_REQUIRE(n_frames <= 0x7fffffffLL && frame <= 0x7fffffffLL, PV_ESIZE, "%s: too many frames or pixels", who);
+  hipStream_t stq = as_stream(stream);
+  const bool src16 = (uintptr_t)src % 16 == 0 && sb % 4 == 0 && st % 4 == 0;
+  if (sp == 1 && frame % 8 == 0 && src16 && sc % 4 == 0 && (uintptr_t)u8 % 8 == 0) {
+    const int frame8 = (int)(frame / 8);
+    const long long n_blk = n_frames * ((frame8 + 256 * PS_VPT - 1) / (256 * PS_VPT));
+    hipLaunchKernelGGL(u8_stacks_planar_kernel, dim3((unsigned)std::min<long long>(n_blk, 1 << 20)), dim3(256), 0, stq, src,
+                       (long long)sb, (long long)st, (long long)sc, u8, n_frames, t_obs, c_out, c0, frame8, scale);
+    return check_launch(who);
+  }
+  if (channel < 0 && sc == 1 && sp == c && c <= 64) {
+    const long long n_slabs = (long long)batch * t_obs;
+    const long long n_blk = n_slabs * ((frame + US_TILE - 1) / US_TILE);
+    const int store4 = (frame % 4 == 0 && (uintptr_t)u8 % 4 == 0) ? 1 : 0;
+    const dim3 grid((unsigned)std::min<long long>(n_blk, 1 << 20));
+    const size_t lds = (size_t)c * US_PITCH;
+    if (c % 4 == 0 && src16)
+      hipLaunchKernelGGL((u8_stacks_nhwc_kernel<4>), grid, dim3(256), lds, stq, src, (long long)sb, (long long)st, u8, n_slabs,
+                         t_obs, c, (long long)frame, scale, store4);
+    else
+      hipLaunchKernelGGL((u8_stacks_nhwc_kernel<1>), grid, dim3(256), lds, stq, src, (long long)sb, (long long)st, u8, n_slabs,
+                         t_obs, c, (long long)frame, scale, store4);
+    return check_launch(who);
+  }
+  if (frame % 4 == 0 && (uintptr_t)u8 % 4 == 0) {
+    const long long total = n_frames * (frame / 4);
+    hipLaunchKernelGGL((u8_stacks_strided_kernel<4>), dim3(stream_grid((size_t)total, 256)), dim3(256), 0, stq, src,
+                       (long long)sb, (long long)st, (long long)sc, (long long)sp, u8, total, t_obs, c_out, c0, (long long)frame,
+                       scale);
+  } else {
+    const long long total = n_frames * frame;
+    hipLaunchKernelGGL((u8_stacks_strided_kernel<1>), dim3(stream_grid((size_t)total, 256)), dim3(256), 0, stq, src,
+                       (long long)sb, (long long)st, (long long)sc, (long long)sp, u8, total, t_obs, c_out, c0, (long long)frame,
+                       scale);
+  }
+  return check_launch(who);
+}
+
+// ---------------------------------------------------------------------------------------------
+// cv.remap on channels-last frames [H, W, C] (experiments 002 / 003 carry [B, T, H, W, C]): the arithmetic of remap_one,
+// applied to VEC consecutive channels of one pixel that share a flow vector.  One thread = VEC channels of one destination
+// pixel, all n_steps steps; lanes run over (pixel, channel group) with the channels fastest, so a wave's stores are one
+// contiguous run of the destination frame.  VEC == 4 needs a shared flow (channel stride 0): coordinates and the four
+// weights are computed once and serve four channels, taps and results move as 16-byte vectors.  VEC == 1 is the per-channel
+// flow [C, H, W, 2] (and C % 4 != 0): one thread per (pixel, channel), its flow vector an 8-byte gather.
+// ---------------------------------------------------------------------------------------------
+template <int VEC> struct NhwcVec { typedef f32x4 type; };
+template <> struct NhwcVec<1> { typedef float type; };
+
+template <int VEC>
+__device__ __forceinline__ typename NhwcVec<VEC>::type nhwc_splat(float v) {
+  if constexpr (VEC == 4) { const f32x4 r = {v, v, v, v}; return r; } else { return v; }
+}
+
+template <int VEC>
+__device__ __forceinline__ typename NhwcVec<VEC>::type remap_nhwc_one(const float* __restrict__ img, int h, int w, int c,
+                                                                       float mx, float my, int border_mode, float border_value) {
+  typedef typename NhwcVec<VEC>::type V;
+  const int sx = cv_round_x86(mx * 32.0f);
+  const int sy = cv_round_x86(my * 32.0f);
+  const int fxi = sx & 31, fyi = sy & 31;
+  const int ix = sat_short(sx >> 5), iy = sat_short(sy >> 5);
+  auto tap = [&](int yy, int xx) { return *reinterpret_cast<const V*>(img + ((int64_t)yy * w + xx) * c); };
+  V p00, p01, p10, p11;
+  const bool inside = (unsigned)ix < (unsigned)(w - 1) && (unsigned)iy < (unsigned)(h - 1);
+  if (inside) {
+    p00 = tap(iy, ix); p01 = tap(iy, ix + 1); p10 = tap(iy + 1, ix); p11 = tap(iy + 1, ix + 1);
+  } else if (border_mode == PV_BORDER_REPLICATE) {
+    const int x0 = clampi(ix, 0, w - 1), x1 = clampi(ix + 1, 0, w - 1);
+    const int y0 = clampi(iy, 0, h - 1), y1 = clampi(iy + 1, 0, h - 1);
+    p00 = tap(y0, x0); p01 = tap(y0, x1); p10 = tap(y1, x0); p11 = tap(y1, x1);
+  } else {
+    const V bv = nhwc_splat<VEC>(border_value);
+    if (ix >= w || ix + 1 < 0 || iy >= h || iy + 1 < 0) return bv;
+    const bool x0in = (unsigned)ix < (unsigned)w, x1in = (unsigned)(ix + 1) < (unsigned)w;
+    const bool y0in = (unsigned)iy < (unsigned)h, y1in = (unsigned)(iy + 1) < (unsigned)h;
+    p00 = (x0in && y0in) ? tap(iy, ix) : bv;
+    p01 = (x1in && y0in) ? tap(iy, ix + 1) : bv;
+    p10 = (x0in && y1in) ? tap(iy + 1, ix) : bv;
+    p11 = (x1in && y1in) ? tap(iy + 1, ix + 1) : bv;
+  }
+  // the f32 weight table of remap_one: products of (1 - k/32, k/32), summed in its order
+  const float ax = (float)fxi * 0.03125f, ay = (float)fyi * 0.03125f;
+  const float w00 = (1.0f - ax) * (1.0f - ay), w01 = ax * (1.0f - ay);
+  const float w10 = (1.0f - ax) * ay, w11 = ax * ay;
+  if constexpr (VEC == 4) {
+    f32x4 r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float a = __fmul_rn(p00[j], w00);
+      a = __fadd_rn(a, __fmul_rn(p01[j], w01));
+      a = __fadd_rn(a, __fmul_rn(p10[j], w10));
+      r[j] = __fadd_rn(a, __fmul_rn(p11[j], w11));
+    }
+    return r;
+  } else {
+    float a = __fmul_rn(p00, w00);
+    a = __fadd_rn(a, __fmul_rn(p01, w01));
+    a = __fadd_rn(a, __fmul_rn(p10, w10));
+    return __fadd_rn(a, __fmul_rn(p11, w11));
+  }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void remap_nhwc_kernel(const float* __restrict__ src, int64_t src_image_stride,
+                                                         const float* __restrict__ flow, int64_t flow_image_stride,
+                                                         int64_t flow_channel_stride, float* __restrict__ dst,
+                                                         int64_t dst_image_stride, int64_t dst_step_stride, int64_t n_images,
+                                                         int n_steps, float step0, int h, int w, int c, int border_mode,
+                                                         float border_value) {
+  typedef typename NhwcVec<VEC>::type V;
+  struct __attribute__((packed, aligned(4))) Pair { float a, b; };
+  const int cq = c / VEC;
+  const int64_t per_image = (int64_t)h * w * cq;
+  const int64_t total = n_images * per_image;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const int64_t img_i = i / per_image;
+    const int64_t rem = i - img_i * per_image;
+    const int px = (int)(rem / cq);
+    const int ch = (int)(rem - (int64_t)px * cq) * VEC;
+    const int y = px / w, x = px - y * w;
+    const Pair f = *reinterpret_cast<const Pair*>(flow + img_i * flow_image_stride + (int64_t)ch * flow_channel_stride +
+                                                  (int64_t)px * 2);
+    const float* img = src + img_i * src_image_stride + ch;
+    float* d = dst + img_i * dst_image_stride + (int64_t)px * c + ch;
+    for (int s = 0; s < n_steps; ++s) {
+      const float k = step0 + (float)s;
+      // remap = -(flow * k); remap += arange   (f32, no fused multiply-add)
+      const float mx = __fadd_rn(-__fmul_rn(f.a, k), (float)x);
+      const float my = __fadd_rn(-__fmul_rn(f.b, k), (float)y);
+      *reinterpret_cast<V*>(d + (int64_t)s * dst_step_stride) =
+          remap_nhwc_one<VEC>(img, h, w, c, mx, my, border_mode, border_value);
+    }
+  }
+}
+
+static int remap_nhwc_launch(const float* src, int64_t src_image_stride, const float* flow, int64_t flow_image_stride,
+                             int64_t flow_channel_stride, float* dst, int64_t dst_image_stride, int64_t dst_step_stride,
+                             int64_t n_images, int32_t n_steps, float step0, int32_t h, int32_t w, int32_t c, int border_mode,
+                             float border_value, void* stream) {
+  const char* who = "pv_remap_bilinear_nhwc_f32";
+  PV_REQUIRE(src && flow && dst, PV_EINVAL, "%s: null pointer", who);
+  PV_REQUIRE(n_images >= 0 && n_steps >= 0 && h > 0 && w > 0 && c > 0, PV_EINVAL,
+             "%s: bad sizes n_images=%lld n_steps=%d h=%d w=%d c=%d", who, (long long)n_images, n_steps, h, w, c);
+  PV_REQUIRE(border_mode == PV_BORDER_CONSTANT || border_mode == PV_BORDER_REPLICATE, PV_EINVAL,
+             "%s: border_mode %d not supported", who, border_mode);
+  PV_REQUIRE(h <= 32767 && w <= 32767, PV_ESIZE, "%s: image larger than SHRT_MAX", who);
+  PV_REQUIRE((int64_t)h * w * c <= 0x7fffffffLL, PV_ESIZE, "%s: frame of %d x %d x %d values is too large", who, h, w, c);
+  PV_REQUIRE(src_image_stride >= 0 && flow_image_stride >= 0 && flow_channel_stride >= 0 && dst_image_stride >= 0 &&
+                 dst_step_stride >= 0, PV_EINVAL, "%s: strides must be non-negative", who);
+  if (n_images == 0 || n_steps == 0) return PV_OK;
+  hipStream_t stq = as_stream(stream);
+  const bool vec = flow_channel_stride == 0 && c % 4 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0 &&
+                   src_image_stride % 4 == 0 && dst_image_stride % 4 == 0 && dst_step_stride % 4 == 0;
+  if (vec) {
+    const size_t work = (size_t)n_images * h * w * (c / 4);
+    hipLaunchKernelGGL((remap_nhwc_kernel<4>), dim3(stream_grid(work, 256)), dim3(256), 0, stq, src, src_image_stride, flow,
+                       flow_image_stride, flow_channel_stride, dst, dst_image_stride, dst_step_stride, n_images, n_steps, step0,
+                       h, w, c, border_mode, border_value);
+  } else {
+    const size_t work = (size_t)n_images * h * w * c;
+    hipLaunchKernelGGL((remap_nhwc_kernel<1>), dim3(stream_grid(work, 256)), dim3(256), 0, stq, src, src_image_stride, flow,
+                       flow_image_stride, flow_channel_stride, dst, dst_image_stride, dst_step_stride, n_images, n_steps, step0,
+                       h, w, c, border_mode, border_value);
+  }
+  return check_launch(who);
+}
+
 template <typename T>
 static int normalise_launch(const T* src, float* dst, size_t n, int64_t inner, int32_t n_channels,
                             const float* mean, const float* std_, void* stream) {
@@ -619,6 +933,26 @@ int pv_prepare_stacks_f32(const float* raw, uint8_t* u8, float* out, int64_t bat
                           int32_t t_out, int mode, const float* mean, const float* std_, int32_t* range_flag, void* stream) {
   stage_mark("prepare_stacks (raw -> u8 stacks + normalised frames)", as_stream(stream));
   const int rc = prepare_stacks_launch<float>(raw, u8, out, batch, t, c, frame, t_out, mode, mean, std_, range_flag, stream);
+  stage_mark(nullptr, as_stream(stream));
+  return rc;
+}
+
+int pv_u8_stacks_from_normalised_f32(const float* src, int64_t stride_b, int64_t stride_t, int64_t stride_c, int64_t stride_px,
+                                     uint8_t* u8, int64_t batch, int32_t t_obs, int32_t c, int64_t frame, int32_t channel,
+                                     float scale, void* stream) {
+  stage_mark("u8_stacks_from_normalised (normalised f32 -> u8 stacks)", as_stream(stream));
+  const int rc = u8_stacks_launch(src, stride_b, stride_t, stride_c, stride_px, u8, batch, t_obs, c, frame, channel, scale, stream);
+  stage_mark(nullptr, as_stream(stream));
+  return rc;
+}
+
+int pv_remap_bilinear_nhwc_f32(const float* src, int64_t src_image_stride, const float* flow, int64_t flow_image_stride,
+                               int64_t flow_channel_stride, float* dst, int64_t dst_image_stride, int64_t dst_step_stride,
+                               int64_t n_images, int32_t n_steps, float step0, int32_t h, int32_t w, int32_t c, int border_mode,
+                               float border_value, void* stream) {
+  stage_mark("remap_bilinear_nhwc", as_stream(stream));
+  const int rc = remap_nhwc_launch(src, src_image_stride, flow, flow_image_stride, flow_channel_stride, dst, dst_image_stride,
+                                   dst_step_stride, n_images, n_steps, step0, h, w, c, border_mode, border_value, stream);
   stage_mark(nullptr, as_stream(stream));
   return rc;
 }

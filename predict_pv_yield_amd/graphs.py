@@ -79,6 +79,8 @@ class GraphedTrainStep:
     def __init__(self, model, optimizer, example_batch: Dict, batch_idx: int = 0, warmup: int = 3):
         if not getattr(optimizer, "capturable", False):
             raise ValueError("GraphedTrainStep needs HipAdam(capturable=True): the by-value Adam step would be frozen at capture")
+        from .models._flow_join import refuse_graph_capture
+        refuse_graph_capture(model)      # the models that compute the optical-flow join inside forward(): not replayed
         self.model, self.optimizer = model, optimizer
         self.static_batch = _map_tensors(example_batch, _clone_keeping_marks)
         side = torch.cuda.Stream()

@@ -178,12 +178,73 @@ def remap_bilinear(src: torch.Tensor, flow: torch.Tensor, n_steps: int = 1, step
 
 def remap_bilinear_strided(src_ptr: int, src_stride: int, flow: torch.Tensor, out_ptr: int, out_image_stride: int,
                            out_step_stride: int, n: int, n_steps: int, step0: float, h: int, w: int,
-                           border_mode: int, border_value: float) -> None:
-    """f32 remap on raw strided views (used to write advected frames straight into the conv input stack)."""
-    check(get_lib().pv_remap_bilinear_f32(ctypes.c_void_p(src_ptr), src_stride, ptr(flow), h * w * 2,
+                           border_mode: int, border_value: float, flow_stride: Optional[int] = None) -> None:
+    """f32 remap on raw strided views (used to write advected frames straight into the conv input stack).  flow_stride
+    (elements between the fields of consecutive images; default one field [h, w, 2] each): 0 advects every image along
+    the one field `flow` points at."""
+    check(get_lib().pv_remap_bilinear_f32(ctypes.c_void_p(src_ptr), src_stride, ptr(flow),
+                                          h * w * 2 if flow_stride is None else flow_stride,
                                           ctypes.c_void_p(out_ptr), out_image_stride, out_step_stride, n, n_steps,
                                           step0, h, w, border_mode, border_value, current_stream_ptr()),
           "pv_remap_bilinear_f32")
+
+
+_LAYOUT_DIMS = {"NCTHW": (0, 2, 1, 3, 4), "NTHWC": (0, 1, 4, 2, 3)}      # positions of (b, t, c, rows, columns)
+
+
+def _layout_dims(who: str, x: torch.Tensor, layout: str):
+    if layout not in _LAYOUT_DIMS:
+        raise ValueError(f"{who}: layout must be 'NCTHW' or 'NTHWC', got {layout!r}")
+    if x.dtype != torch.float32 or x.dim() != 5:
+        raise TypeError(f"{who}: float32 [B,C,T,H,W] (NCTHW) or [B,T,H,W,C] (NTHWC) expected, got {x.dtype} {tuple(x.shape)}")
+    return _LAYOUT_DIMS[layout]
+
+
+def u8_stacks_from_normalised(x: torch.Tensor, t_obs: int, counts_scale: float, layout: str = "NCTHW",
+                              channel: Optional[int] = None) -> torch.Tensor:
+    """Normalised f32 frames -> the u8 frame stacks farneback_stack takes, one pass (pv_u8_stacks_from_normalised_f32):
+    u8 = round_half_even(clamp(x * float32(4 * counts_scale) + 512, 0, 1020) / 4) of the first t_obs time slices.
+    x: [B,C,T,H,W] (layout "NCTHW") or [B,T,H,W,C] ("NTHWC"), any strides whose image rows follow each other
+    (stride(rows) == W * stride(columns)); -> u8 [B, C, t_obs, H, W], or [B, 1, t_obs, H, W] for `channel` = i."""
+    _require_device(x)       # a strided view is fine: the kernel reads through element strides
+    db, dt, dc, dh, dw = _layout_dims("u8_stacks_from_normalised", x, layout)
+    b, t, c, h, w = (x.shape[d] for d in (db, dt, dc, dh, dw))
+    if not 1 <= t_obs <= t:
+        raise ValueError(f"u8_stacks_from_normalised: t_obs = {t_obs} outside 1..{t}")
+    if channel is not None and not 0 <= channel < c:
+        raise ValueError(f"u8_stacks_from_normalised: channel {channel} outside 0..{c - 1}")
+    if x.stride(dh) != w * x.stride(dw) or min(x.stride()) < 0:
+        raise TypeError("u8_stacks_from_normalised: the rows of an image must follow each other in memory")
+    out = torch.empty((b, c if channel is None else 1, t_obs, h, w), dtype=torch.uint8, device=x.device)
+    if out.numel():
+        check(get_lib().pv_u8_stacks_from_normalised_f32(ptr(x), x.stride(db), x.stride(dt), x.stride(dc), x.stride(dw),
+                                                         ptr(out), b, t_obs, c, h * w, -1 if channel is None else channel,
+                                                         4.0 * counts_scale, current_stream_ptr()),
+              "pv_u8_stacks_from_normalised_f32")
+    return out
+
+
+def remap_bilinear_nhwc(src: torch.Tensor, flow: torch.Tensor, out: torch.Tensor, step0: float = 1.0,
+                        border_mode: int = PV_BORDER_CONSTANT, border_value: float = float("nan")) -> torch.Tensor:
+    """remap_bilinear on channels-last frames (pv_remap_bilinear_nhwc_f32): src f32 [N,H,W,C] (frame strides free, each
+    frame dense), flow f32 [N,C,H,W,2] (per channel) or [N,H,W,2] (shared by the C channels), out f32 [N,n_steps,H,W,C]
+    (image and step strides free) <- cv.remap(src[n,:,:,c], meshgrid - flow*(step0+s), INTER_LINEAR, border)."""
+    _require_device(src, flow, out)      # src and out are time slices of one tensor: strided, each frame dense
+    if src.dtype != torch.float32 or src.dim() != 4 or out.dtype != torch.float32 or out.dim() != 5:
+        raise TypeError("remap_bilinear_nhwc: float32 src [N,H,W,C] and out [N,n_steps,H,W,C] expected")
+    n, h, w, c = src.shape
+    n_steps = out.shape[1]
+    if out.shape != (n, n_steps, h, w, c) or src.stride()[1:] != (w * c, c, 1) or out.stride()[2:] != (w * c, c, 1):
+        raise TypeError("remap_bilinear_nhwc: out must be [N,n_steps,H,W,C] like src; frames must be dense")
+    if flow.dtype != torch.float32 or not flow.is_contiguous() or tuple(flow.shape) not in ((n, c, h, w, 2), (n, h, w, 2)):
+        raise TypeError("remap_bilinear_nhwc: flow must be contiguous float32 [N,C,H,W,2] or [N,H,W,2]")
+    per_channel = flow.dim() == 5
+    if n and n_steps:
+        check(get_lib().pv_remap_bilinear_nhwc_f32(ptr(src), src.stride(0), ptr(flow), (c if per_channel else 1) * h * w * 2,
+                                                   h * w * 2 if per_channel else 0, ptr(out), out.stride(0), out.stride(1), n,
+                                                   n_steps, step0, h, w, c, border_mode, border_value, current_stream_ptr()),
+              "pv_remap_bilinear_nhwc_f32")
+    return out
 
 
 def ssim_mean(im1: torch.Tensor, im2: torch.Tensor, data_range: Optional[float] = None) -> torch.Tensor:

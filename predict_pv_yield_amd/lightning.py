@@ -446,6 +446,8 @@ class Trainer:
         self._graph_step, self._graph_logs, self._graph_eager, self._graph_side = None, [], 0, None
         if not self.hip_graph:
             return False
+        from .models._flow_join import refuse_graph_capture
+        refuse_graph_capture(model)      # raises before any step: the in-forward optical-flow join is not replayed as a graph
         from .optim import HipAdam
         if self.world_size > 1 or len(self.optimizers) != 1 or not isinstance(self.optimizers[0], HipAdam):
             return False

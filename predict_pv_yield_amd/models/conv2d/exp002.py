@@ -18,10 +18,13 @@ plus `sat_x_coords` [B, H] and `sat_y_coords` [B, W], metres).  Deliberate diffe
   - validation_step does not plot an example to Neptune (:277-286);
   - it runs on the MI355X only: CPU tensors raise a RuntimeError (there is no CPU path).
 """
+from typing import Optional
+
 import torch
 from torch import nn
 
 from ...lightning import LightningModule
+from .._flow_join import check_knobs, joined_frames
 
 params = dict(
     batch_size=32,
@@ -52,9 +55,15 @@ RNN_HIDDEN_SIZE = 16
 
 class LitModel(LightningModule):
     name = "exp002_cnn_then_rnn"
+    flow_join_in_forward = True
 
-    def __init__(self, history_len=params["history_len"], forecast_len=params["forecast_len"]):
+    def __init__(self, history_len=params["history_len"], forecast_len=params["forecast_len"], future_frames: str = "true",
+                 flow_channel: Optional[int] = None):
         super().__init__()
+        # future_frames (new, optional): "optical_flow" closes the experiment's TODO at :167 (models/_flow_join.py)
+        check_knobs(future_frames, flow_channel)
+        self.future_frames = future_frames
+        self.flow_channel = flow_channel
         self.history_len = history_len
         self.forecast_len = forecast_len
         self.total_seq_len = history_len + forecast_len + 1
@@ -86,6 +95,7 @@ class LitModel(LightningModule):
             raise RuntimeError("predict_pv_yield_amd exp002.LitModel runs on the MI355X only: move the module and the batch to "
                                "cuda (there is no CPU fallback)")
         batch_size, seq_len, width, height, n_chans = sat_data.shape
+        sat_data = joined_frames(self, sat_data, self.forecast_len, "NTHWC")
         # Stack timesteps as examples (to make a large batch)
         new_batch_size = batch_size * seq_len
         sat_data = sat_data.float().reshape(new_batch_size, width, height, n_chans)

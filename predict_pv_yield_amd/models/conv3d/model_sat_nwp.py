@@ -8,13 +8,18 @@ length preserved, 2 px lost per layer in H and W), each followed by two fully-co
 in the reference's order before fc3/fc4.  All arithmetic runs in the gfx950 kernels behind
 include/pv_yield_hip.h (conv towers + fc1/nwp_fc1 on the bf16 MFMA path by default, the small layers and the
 embedding gather in f32); the modules are parameter holders only.
+
+New optional knobs: `precision`, and `future_frames` / `flow_channel` (models/_flow_join.py): "optical_flow" replaces the
+forecast_len_5 future satellite slices by HIP Farnebäck-advected ones; `include_future_satellite=False` drops them and wins.
 """
 import logging
+from typing import Optional
 
 import torch
 from torch import nn
 
 from ...data.batch import BatchML
+from .._flow_join import check_knobs, joined_frames
 from ..base_model import BaseModel
 
 logging.basicConfig()
@@ -24,6 +29,7 @@ _LOG = logging.getLogger("predict_pv_yield_amd")
 class Model(BaseModel):
 
     name = "conv3d_sat_nwp"
+    flow_join_in_forward = True
 
     def __init__(
         self,
@@ -45,6 +51,8 @@ class Model(BaseModel):
         include_pv_yield_history: int = True,
         include_future_satellite: int = True,
         precision: str = "bf16",
+        future_frames: str = "true",
+        flow_channel: Optional[int] = None,
     ):
         self.include_pv_or_gsp_yield_history = include_pv_or_gsp_yield_history
         self.include_nwp = include_nwp
@@ -65,6 +73,9 @@ class Model(BaseModel):
         if precision not in ("bf16", "fp32"):
             raise ValueError("precision must be 'bf16' or 'fp32'")
         self.precision = precision
+        check_knobs(future_frames, flow_channel)
+        self.future_frames = future_frames
+        self.flow_channel = flow_channel
 
         super().__init__()
 
@@ -135,6 +146,8 @@ class Model(BaseModel):
         batch_size = sat_data.shape[0]
         if not self.include_future_satellite:
             sat_data = sat_data[:, :, : self.history_len_5 + 1].contiguous()
+        else:
+            sat_data = joined_frames(self, sat_data, self.forecast_len_5, "NCTHW", source=x.satellite.data)
         bf16 = self.precision == "bf16"
         out = conv_tower_fc1(sat_data, self._tower_layers("sat"), self.fc1, self.number_sat_channels,
                              self.conv3d_channels, (1, 0, 0), self.cnn_output_size,

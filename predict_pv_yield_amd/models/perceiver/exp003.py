@@ -14,11 +14,14 @@ experiment's dict batches (`sat_data`, `pv_system_row_number`, `nwp`, `hour_of_d
 attention products on the bf16 matrix cores (f32 accumulation, f32 softmax), "f32" keeps the exact-f32 kernels.
 All arithmetic runs in the gfx950 kernels behind include/pv_yield_hip.h; there is no CPU path.
 """
+from typing import Optional
+
 import torch
 from torch import nn
 
 from ...data.seeded import SeededBatchDataset, make_fake_sat_batch
 from ...lightning import LightningModule
+from .._flow_join import check_knobs, joined_frames
 from .perceiver_core import Perceiver
 
 params = dict(
@@ -43,9 +46,15 @@ RNN_HIDDEN_SIZE = 16
 
 class LitModel(LightningModule):
     name = "exp003_perceiver_then_rnn"
+    flow_join_in_forward = True
 
-    def __init__(self, history_len=params["history_len"], forecast_len=params["forecast_len"], operand_dtype: str = "bf16"):
+    def __init__(self, history_len=params["history_len"], forecast_len=params["forecast_len"], operand_dtype: str = "bf16",
+                 future_frames: str = "true", flow_channel: Optional[int] = None):
         super().__init__()
+        # future_frames (new, optional): "optical_flow" closes the experiment's TODO at :155 (models/_flow_join.py)
+        check_knobs(future_frames, flow_channel)
+        self.future_frames = future_frames
+        self.flow_channel = flow_channel
         self.history_len = history_len
         self.forecast_len = forecast_len
         self.total_seq_len = history_len + forecast_len + 1
@@ -87,6 +96,7 @@ class LitModel(LightningModule):
             raise RuntimeError("predict_pv_yield_amd exp003.LitModel runs on the MI355X only: move the module and the batch to "
                                "cuda (there is no CPU fallback)")
         batch_size, seq_len, width, height, n_chans = sat_data.shape
+        sat_data = joined_frames(self, sat_data, self.forecast_len, "NTHWC")
         # Stack timesteps as examples (to make a large batch)
         new_batch_size = batch_size * seq_len
         sat_data = sat_data.reshape(new_batch_size, width, height, n_chans)

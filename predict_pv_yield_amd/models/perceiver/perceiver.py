@@ -8,12 +8,13 @@ encoder over the history (+ yield history) and a GRU decoder over the forecast s
 gfx950 kernels behind include/pv_yield_hip.h: perceiver_core.Perceiver (pv_gemm_f32 on the f32 matrix cores,
 LayerNorm / softmax / GEGLU kernels), pv_linear_*_f32 for the head, pv_embedding_*, pv_gru_seq_* for the RNNs.
 """
-from typing import Iterable
+from typing import Iterable, Optional
 
 import torch
 from torch import nn
 
 from ...data.batch import BatchML
+from .._flow_join import check_knobs, joined_frames
 from ..base_model import BaseModel
 from .perceiver_core import Perceiver
 
@@ -112,6 +113,7 @@ def require_cuda_input(t, who):
 class PerceiverModel(BaseModel):
 
     name = "perceiver"
+    flow_join_in_forward = True
 
     def __init__(
         self,
@@ -124,6 +126,8 @@ class PerceiverModel(BaseModel):
         embedding_dem: int = 16,
         output_variable: str = "pv_yield",
         operand_dtype: str = "f32",
+        future_frames: str = "true",
+        flow_channel: Optional[int] = None,
     ):
         # operand_dtype (new, optional): "bf16" runs the attention products on the bf16 matrix cores (Lightning precision=16)
         self.history_minutes = history_minutes
@@ -134,6 +138,10 @@ class PerceiverModel(BaseModel):
         self.latent_dim = latent_dim
         self.embedding_dem = embedding_dem
         self.output_variable = output_variable
+        # future_frames (new, optional): "optical_flow" closes the reference's TODO at perceiver.py:118 (models/_flow_join.py)
+        check_knobs(future_frames, flow_channel)
+        self.future_frames = future_frames
+        self.flow_channel = flow_channel
 
         self.total_seq_length = self.history_minutes // 5 + self.forecast_minutes // 5 + 1
 
@@ -161,6 +169,7 @@ class PerceiverModel(BaseModel):
         # Shape: batch_size, channel, seq_length, height, width
         sat_data = x.satellite.data[0 : self.batch_size].float()
         require_cuda_input(sat_data, "PerceiverModel")
+        sat_data = joined_frames(self, sat_data, self.forecast_len_5, "NCTHW", source=x.satellite.data)
         batch_size, n_chans, seq_len, width, height = sat_data.shape
 
         # Stack timesteps as examples (to make a large batch), channels last

@@ -10,13 +10,14 @@ head is the shared perceiver_head() of perceiver.py.
 Both run on the gfx950 kernels behind include/pv_yield_hip.h (pv_conv3d_general_*_f32, pv_maxpool3d_*_f32); the
 modules are parameter / hyper-parameter holders with the reference's attribute (state_dict) names.
 """
-from typing import Iterable
+from typing import Iterable, Optional
 
 import torch
 from torch import nn
 
 from ... import functional as Fn
 from ...data.batch import BatchML
+from .._flow_join import check_knobs, joined_frames
 from ..base_model import BaseModel
 
 
@@ -41,6 +42,7 @@ class Conv3dMaxPool(nn.Module):
 class Model(BaseModel):
 
     name = "perceiver_conv3d_nwp_sat"
+    flow_join_in_forward = True
 
     def __init__(
         self,
@@ -54,6 +56,8 @@ class Model(BaseModel):
         output_variable: str = "pv_yield",
         conv3d_channels: int = 16,
         use_future_satellite_images: bool = True,  # option not to use future sat images
+        future_frames: str = "true",
+        flow_channel: Optional[int] = None,
     ):
         from .perceiver import PERCEIVER_OUTPUT_SIZE, make_perceiver_head, params
         from .perceiver_core import Perceiver
@@ -67,6 +71,11 @@ class Model(BaseModel):
         self.embedding_dem = embedding_dem
         self.output_variable = output_variable
         self.use_future_satellite_images = use_future_satellite_images
+        # future_frames (new, optional): "optical_flow" closes the reference's TODO at perceiver_conv3d_nwp_sat.py:145;
+        # use_future_satellite_images=False wins (no flow is computed)
+        check_knobs(future_frames, flow_channel)
+        self.future_frames = future_frames
+        self.flow_channel = flow_channel
         self.total_seq_length = self.history_minutes // 5 + self.forecast_minutes // 5 + 1
 
         super().__init__()
@@ -98,6 +107,8 @@ class Model(BaseModel):
             # axis of [B, C, T, H, W]; kept as is, on a copy so that the caller's batch is not modified
             sat_data = sat_data.clone()
             sat_data[:, -self.forecast_len_5 :] = 0
+        else:
+            sat_data = joined_frames(self, sat_data, self.forecast_len_5, "NCTHW", source=x.satellite.data)
         sat_data = self.sat_conv3d_maxpool(sat_data)
         nwp_data = self.nwp_conv3d_maxpool(x.nwp.data[0 : self.batch_size].float())
         data, batch_size = stack_sat_and_nwp(sat_data, nwp_data)

@@ -4,11 +4,12 @@ The NWP fields (same pixel size as the satellite crop) are concatenated to the s
 before the Perceiver; the GRU encoder / decoder see the per-step features only.  Same constructor kwargs, attribute /
 state_dict names and forward contract as the reference; all arithmetic on the HIP kernels (perceiver.py: perceiver_head).
 """
-from typing import Iterable
+from typing import Iterable, Optional
 
 import torch
 
 from ...data.batch import BatchML
+from .._flow_join import check_knobs, joined_frames
 from ..base_model import BaseModel
 from .perceiver import (PERCEIVER_OUTPUT_SIZE, make_perceiver_head, params, perceiver_head, require_cuda_input)
 from .perceiver_core import Perceiver
@@ -31,6 +32,7 @@ def stack_sat_and_nwp(sat_data: torch.Tensor, nwp_data: torch.Tensor):
 class Model(BaseModel):
 
     name = "perceiver_nwp_sat"
+    flow_join_in_forward = True
 
     def __init__(
         self,
@@ -42,6 +44,8 @@ class Model(BaseModel):
         latent_dim: int = 64,
         embedding_dem: int = 16,
         output_variable: str = "pv_yield",
+        future_frames: str = "true",
+        flow_channel: Optional[int] = None,
     ):
         self.history_minutes = history_minutes
         self.forecast_minutes = forecast_minutes
@@ -51,6 +55,10 @@ class Model(BaseModel):
         self.latent_dim = latent_dim
         self.embedding_dem = embedding_dem
         self.output_variable = output_variable
+        # future_frames (new, optional): "optical_flow" closes the reference's TODO at perceiver_nwp_sat.py:117
+        check_knobs(future_frames, flow_channel)
+        self.future_frames = future_frames
+        self.flow_channel = flow_channel
         self.total_seq_length = self.history_minutes // 5 + self.forecast_minutes // 5 + 1
 
         super().__init__()
@@ -73,6 +81,7 @@ class Model(BaseModel):
             x = BatchML(**x)
         sat_data = x.satellite.data[0 : self.batch_size].float()
         require_cuda_input(sat_data, "perceiver_nwp_sat.Model")
+        sat_data = joined_frames(self, sat_data, self.forecast_len_5, "NCTHW", source=x.satellite.data)
         data, batch_size = stack_sat_and_nwp(sat_data, x.nwp.data[0 : self.batch_size].float())
         out = self.perceiver(data)
         # (the reference takes the embedding id from pv_system_row_number whatever the output variable)

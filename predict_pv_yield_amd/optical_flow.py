@@ -255,30 +255,70 @@ def advect_future_frames(raw: torch.Tensor, n_future: int, mean: Optional[torch.
 
 
 def replace_future_frames_with_flow(sat_data: torch.Tensor, n_future: int, border_mode: int = BORDER_REPLICATE,
-                                    counts_scale: float = 255.0 / 6.0, **farneback_kwargs) -> torch.Tensor:
-    """For a NORMALISED model input [B, C, T, H, W]: recompute the last n_future time slices by advecting the
+                                    counts_scale: float = 255.0 / 6.0, layout: str = "NCTHW",
+                                    flow_channel: Optional[int] = None, **farneback_kwargs) -> torch.Tensor:
+    """For a NORMALISED float32 model input, [B, C, T, H, W] (layout "NCTHW") or channels-last [B, T, H, W, C] ("NTHWC",
+    experiments 002 / 003; image rows = dim 2, columns = dim 3): recompute the last n_future time slices by advecting the
     last observed frame along the weighted-mean Farnebäck flow of the observed frames.  The u8 images Farnebäck
     needs are obtained by mapping the normalised values (about N(0,1)) affinely onto 0..255
-    (u8 = clip(round(128 + x * counts_scale)))."""
+    (u8 = clip(round(128 + x * counts_scale))).
+
+    flow_channel=None: every channel is advected along its own flow (C Farnebäck stacks per sample); an integer i: the flow
+    is estimated on channel i alone and every channel is advected along it (one stack per sample: clouds move the same
+    way in every band, and the reference's own flow notebook estimates motion on HRV only).
+
+    Stages: one kernel writes the u8 stacks straight from the input (either layout), Farnebäck, the weighted mean, ONE
+    output allocation into which the observed slices are copied once and the remap writes the future slices in place.
+    Returns a new contiguous tensor of the input's shape; the input is never written and its future slices never read."""
     if not sat_data.is_cuda:
         raise RuntimeError("replace_future_frames_with_flow: input must be on the MI355X")
-    b, c, t, h, w = sat_data.shape
+    if layout not in ("NCTHW", "NTHWC"):
+        raise ValueError(f"replace_future_frames_with_flow: layout must be 'NCTHW' or 'NTHWC', got {layout!r}")
+    if sat_data.dtype != torch.float32 or sat_data.dim() != 5:
+        raise TypeError(f"replace_future_frames_with_flow: float32 input with 5 dimensions expected, got {sat_data.dtype} "
+                        f"{tuple(sat_data.shape)}")
+    planar = layout == "NCTHW"
+    if planar:
+        b, c, t, h, w = sat_data.shape
+    else:
+        b, t, h, w, c = sat_data.shape
     t_obs = t - n_future
     if t_obs < 2:
         raise ValueError("need at least two observed frames to estimate a flow")
-    obs = sat_data[:, :, :t_obs].contiguous()
-    # affine map onto 10-bit-like counts, then the reference's u8 conversion
-    counts = ((obs * (4.0 * counts_scale)) + 512.0).clamp_(0.0, 1020.0)
-    u8 = K.u8_from_10bit(counts, 0)
+    if flow_channel is not None and not 0 <= flow_channel < c:
+        raise ValueError(f"replace_future_frames_with_flow: flow_channel {flow_channel} outside 0..{c - 1}")
+    row, col = (3, 4) if planar else (2, 3)
+    if sat_data.stride(row) != w * sat_data.stride(col) or min(sat_data.stride()) < 0:
+        sat_data = sat_data.contiguous()      # image rows apart in memory: the kernel takes one pixel stride
+    # affine map onto 10-bit-like counts and the reference's u8 conversion, as planar stacks [B, C or 1, T_obs, H, W]
+    u8 = K.u8_stacks_from_normalised(sat_data, t_obs, counts_scale, layout, flow_channel)
     kw = dict(REFERENCE_FARNEBACK_KWARGS)
     kw.update(farneback_kwargs)
-    flows = K.farneback_stack(u8, **kw)
-    mean_flow = K.flow_weighted_mean(flows.view(b * c, t_obs - 1, h, w, 2))
-    out = sat_data.contiguous().clone()
+    flows = K.farneback_stack(u8, **kw)                                 # [B, C or 1, T_obs-1, H, W, 2]
+    mean_flow = K.flow_weighted_mean(flows.view(-1, t_obs - 1, h, w, 2))  # [B*C or B, H, W, 2]
+    out = torch.empty(sat_data.shape, dtype=torch.float32, device=sat_data.device)
+    nan = float("nan")
+    if not planar:
+        out[:, :t_obs].copy_(sat_data[:, :t_obs])
+        K.remap_bilinear_nhwc(out[:, t_obs - 1], mean_flow.view(b, c, h, w, 2) if flow_channel is None else mean_flow,
+                              out[:, t_obs:], 1.0, border_mode, nan)
+        return out
+    out[:, :, :t_obs].copy_(sat_data[:, :, :t_obs])
     frame = h * w
-    K.remap_bilinear_strided(out.data_ptr() + (t_obs - 1) * frame * 4, t * frame, mean_flow,
-                             out.data_ptr() + t_obs * frame * 4, t * frame, frame, b * c, n_future, 1.0, h, w,
-                             border_mode, float("nan"))
+    src0, dst0 = out.data_ptr() + (t_obs - 1) * frame * 4, out.data_ptr() + t_obs * frame * 4
+    if flow_channel is None:
+        K.remap_bilinear_strided(src0, t * frame, mean_flow, dst0, t * frame, frame, b * c, n_future, 1.0, h, w,
+                                 border_mode, nan)
+    elif b == 1:
+        # one sample: its C channels are the images, all along the one field (flow stride 0)
+        K.remap_bilinear_strided(src0, t * frame, mean_flow, dst0, t * frame, frame, c, n_future, 1.0, h, w, border_mode, nan,
+                                 flow_stride=0)
+    else:
+        # the planar remap takes ONE flow stride over its B*C images, and a launch per sample or per channel costs more than
+        # the remap itself at these sizes (11 launches: 408 us against 36 us at B = 32, 24 x 24 x 11): the B fields are
+        # repeated per channel first (8 B per pixel and image, against the n_future x 4 B the remap then writes)
+        per_image = mean_flow[:, None].expand(b, c, h, w, 2).contiguous()
+        K.remap_bilinear_strided(src0, t * frame, per_image, dst0, t * frame, frame, b * c, n_future, 1.0, h, w, border_mode, nan)
     return out
 
 
