@@ -310,6 +310,88 @@ int pv_conv2d144_sat_pool_bwd_weight_f32(const float* sat, const float* x_coords
                                          const float* dy_pooled, const uint8_t* codes, float* dw, float* dbias,
                                          int32_t b, int32_t t_total, int32_t n_frames, int32_t h, int32_t w_img,
                                          int32_t c_out, void* ws, size_t ws_bytes, void* stream);
+/* ---- notebooks/16_maxpool.ipynb: Conv2d / ConvTranspose2d 3x3 encoder-decoder, exact f32, planes up to 128 wide ---- */
+/* (line numbers: the raw .ipynb file; the LitAutoEncoder cell starts at 13737, normalise_images_in_model at 13721)
+ * NCHW f32 as above.  Counts are raw 10-bit satellite counts, int16 (*_is_i16 != 0) or f32, normalised inside the kernels
+ * as (v - 93.23458) / 115.34247 (subtract, then a true f32 divide).  Gates, codes and weight-gradient slabs follow the
+ * conventions of pv_conv2d_bwd_data_f32 and pv_conv2d144_pool_fwd_f32.  Unsupported shapes return PV_ESIZE. */
+/* replaces: images = torch.cat((x[HISTORICAL_SAT_IMAGES], x[OPTICAL_FLOW_PREDICTIONS].unsqueeze(1)), dim=1);
+ * normalise_images_in_model(images); torch.cat((images, forecast_horizon), dim=1); F.relu(self.encoder_conv1(images)),
+ * 16_maxpool.ipynb:13721-13728, 13760-13779.  history [n][4][h][w], flow_pred [n][h][w], horizon [n] (not normalised
+ * again); the 6-channel input is built while staged, never stored.  c_out = 16; 11 <= h, w and w <= 128. */
+int pv_conv2d_ae_counts_fwd_f32(const void* history, int32_t history_is_i16, const void* flow_pred, int32_t flow_is_i16,
+                                const float* horizon, const float* w, const float* bias, float* y, int32_t n, int32_t h,
+                                int32_t w_img, int32_t c_out, void* stream);
+/* replaces: the weight and bias gradients of encoder_conv1 (autograd of 16_maxpool.ipynb:13779), re-reading and
+ * re-normalising the counts as the forward does; dy is the pre-activation gradient.  dw [16][6][3][3]. */
+int pv_conv2d_ae_counts_bwd_weight_f32(const void* history, int32_t history_is_i16, const void* flow_pred,
+                                       int32_t flow_is_i16, const float* horizon, const float* dy, float* dw, float* dbias,
+                                       int32_t n, int32_t h, int32_t w_img, int32_t c_out, void* ws, size_t ws_bytes,
+                                       void* stream);
+/* replaces: F.relu(self.encoder_conv2(out)) / F.relu(self.encoder_conv3(out)), 16_maxpool.ipynb:13782, 13785.
+ * (c_in, c_out) = (16, 32) or (32, 32), w_in <= 128; bias may be NULL.  32 -> 32 launches of >= 32768 output positions run
+ * pv_conv3d_general_fwd_f32 (provisional threshold, as for the gradients below). */
+int pv_conv2d_ae_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                         int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of encoder_conv2 / encoder_conv3 (autograd of 16_maxpool.ipynb:13782, 13785); dy_gate and
+ * x_gate as for pv_conv2d_bwd_data_f32.  Launches of >= 32768 output positions run pv_conv3d_general_bwd_data_f32 as a
+ * 1x3x3 conv (faster there in the one run at B = 64, S = 128: profiles/nb16/; the threshold is provisional). */
+int pv_conv2d_ae_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                              int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+/* bytes of the weight-gradient workspace of the three Conv2d weight gradients: c_in = 6 (counts layer, c_out = 16), 16 or
+ * 32; pooled != 0 for pv_conv2d_ae_pool_bwd_weight_f32 */
+int pv_conv2d_ae_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                            int32_t pooled, size_t* bytes);
+/* replaces: the weight and bias gradients of encoder_conv2 / encoder_conv3.  dw [c_out][c_in][3][3] and dbias [c_out]
+ * are overwritten; slab partials summed in slab order (deterministic).  Launches of >= 32768 output positions run
+ * pv_conv3d_general_bwd_weight_f32 as a 1x3x3 conv (as pv_conv2d_ae_bwd_data_f32; the workspace query sizes it). */
+int pv_conv2d_ae_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias, int32_t n,
+                                int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
+                                void* stream);
+/* replaces: out = F.relu(self.encoder_conv4(out)); out, indices3 = self.maxpool(out), 16_maxpool.ipynb:13788-13789 (the
+ * indices are never used by the model).  c_in = c_out = 32, h and w >= 5; pooled y and codes [n][32][(h-2)/3][(w-2)/3]. */
+int pv_conv2d_ae_pool_fwd_f32(const float* x, const float* w, const float* bias, float* y, uint8_t* codes, int32_t n,
+                              int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
+                              void* stream);
+/* bytes of pv_conv2d_ae_pool_fwd_f32's workspace: 0 below 32768 output positions (the fused kernel; ws may be NULL), else
+ * the pre-activations [n][32][h-2][w-2] that pv_conv3d_general_fwd_f32 writes before a pool kernel reads them */
+int pv_conv2d_ae_pool_fwd_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                          size_t* bytes);
+/* replaces: the input gradient of maxpool(relu(encoder_conv4(x))) from the pooled gradient and the forward's codes. */
+int pv_conv2d_ae_pool_bwd_data_f32(const float* dy_pooled, const uint8_t* codes, const float* w, float* dx,
+                                   const float* x_gate, int32_t n, int32_t c_in, int32_t c_out, int32_t h_in,
+                                   int32_t w_in, void* stream);
+/* replaces: the weight and bias gradients of encoder_conv4 under the max pool.  From 32768 output positions up the
+ * pre-pool gradient is written to the workspace and pv_conv3d_general_bwd_weight_f32 runs on it (the query sizes both). */
+int pv_conv2d_ae_pool_bwd_weight_f32(const float* x, const float* dy_pooled, const uint8_t* codes, float* dw, float* dbias,
+                                     int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
+                                     size_t ws_bytes, void* stream);
+/* replaces: self.decoder_conv1..4(out) (+ F.relu if relu), 16_maxpool.ipynb:13793-13801: nn.ConvTranspose2d(c_in, c_out,
+ * 3), stride 1, no padding.  x [n][c_in][h][w] -> y [n][c_out][h + 2][w + 2]; w [c_in][c_out][3][3]; (c_in, c_out) =
+ * (32, 32), (32, 16), (16, 16) or (16, 1); w + 2 <= 128; bias may be NULL.  All four pairs run these kernels (16 -> 1 on
+ * one 16-row tile). */
+int pv_convt2d_ae_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                          int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of decoder_conv1..4: a valid correlation of dy [n][c_out][h + 2][w + 2] (zeroed where
+ * dy_gate <= 0; NULL = none) with the unmirrored weights; dx [n][c_in][h][w] zeroed where x_gate <= 0 (NULL = ungated). */
+int pv_convt2d_ae_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                               int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+/* bytes of the weight-gradient workspace of pv_convt2d_ae_bwd_weight_f32 (one partial [c_out][c_in * 9 + 1] per slab
+ * of tiles); (h, w) = the extent of x */
+int pv_convt2d_ae_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                             size_t* bytes);
+/* replaces: the weight and bias gradients of decoder_conv1..4: dw[ci][co][tap] = sum x[ci][p] dy[co][p + tap] in the
+ * [c_in][c_out][3][3] layout, dbias [c_out]; (h, w) = the extent of x; deterministic slab sums. */
+int pv_convt2d_ae_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias, int32_t n,
+                                 int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
+                                 void* stream);
+/* replaces: y = normalise_images_in_model(batch[TARGET_SAT_IMAGE]); y = y[..., 8:-8, 8:-8]; F.mse_loss(y_hat.squeeze(),
+ * y), 16_maxpool.ipynb:13805-13809.  y_hat [n][out_h][out_w] f32, target [n][target_h][target_w] counts with target_h - 16
+ * == out_h and target_w - 16 == out_w (else PV_ESIZE).  loss: device f32[1]; dy_hat (may be NULL) = 2 (y_hat - y) / count.
+ * ws: n floats (one partial sum per example, added in index order). */
+int pv_mse_crop_norm_f32(const float* y_hat, const void* target, int32_t target_is_i16, int32_t n, int32_t out_h,
+                         int32_t out_w, int32_t target_h, int32_t target_w, float* loss, float* dy_hat, void* ws,
+                         size_t ws_bytes, void* stream);
 
 /* MaxPool3d over x[B*C planes][Ti,Hi,Wi]; argmax (may be NULL) = flat winner offset inside the plane stack, first
  * maximum wins, NaN propagates (torch CPU semantics).  bwd overwrites dx by gathering dy through argmax. */

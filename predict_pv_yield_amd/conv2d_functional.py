@@ -1,5 +1,6 @@
 """torch.autograd.Function wrappers over the exact-f32 Conv2d 3x3 "valid" kernels: csrc/conv2d_f32.hip (experiments/002) and
-the 144-channel kernels with fused MaxPool2d(3) of csrc/conv2d_pool_f32.hip (experiments/001).
+the 144-channel kernels with fused MaxPool2d(3) of csrc/conv2d_pool_f32.hip (experiments/001) and the encoder / decoder
+kernels of csrc/conv2d_ae_f32.hip (notebooks/16_maxpool.ipynb: Conv2d up to 128 wide, ConvTranspose2d, cropped MSE).
 
 Reference operators replaced:
   experiments/002_cnn_processes_single_sat_image_then_rnn.py
@@ -9,6 +10,12 @@ Reference operators replaced:
     self.maxpool(F.relu(self.sat_conv1(torch.cat((frames, center_marker, x_coords, ...), dim=1))))             :264-307
     self.maxpool(F.relu(self.sat_conv2(out)))                                                                 :308-309
     F.relu(self.sat_conv3(out))                                                                               :310
+  notebooks/16_maxpool.ipynb (raw lines of the .ipynb file)
+    F.relu(self.encoder_conv1(cat(normalise_images_in_model(cat(history, flow)), horizon plane)))             :13760-13779
+    F.relu(self.encoder_conv2(out)), F.relu(self.encoder_conv3(out))                                          :13782-13785
+    self.maxpool(F.relu(self.encoder_conv4(out)))                                                             :13788-13789
+    F.relu(self.decoder_conv1..3(out)), self.decoder_conv4(out)                                               :13793-13801
+    F.mse_loss(y_hat.squeeze(), normalise_images_in_model(y)[..., 8:-8, 8:-8])                                :13805-13809
 
 Gating.  As in functional.Conv3dGeneralF32, the ReLU gating of an activation gradient is moved into the kernel that
 produces it.  x_is_relu_output -> this layer's dx leaves already zeroed where x <= 0 (the lower layer's pre-activation
@@ -28,6 +35,7 @@ from . import hip_ops as K
 # entry points of the plain (unpooled) conv: (forward, data gradient, weight gradient)
 CONV2D_OPS = (K.conv2d_fwd_f32, K.conv2d_bwd_data_f32, K.conv2d_bwd_weight_f32)
 CONV2D144_OPS = (K.conv2d144_fwd_f32, K.conv2d144_bwd_data_f32, K.conv2d144_bwd_weight_f32)
+CONV2D_AE_OPS = (K.conv2d_ae_fwd_f32, K.conv2d_ae_bwd_data_f32, K.conv2d_ae_bwd_weight_f32)
 
 
 class CoordsConv2dReLU(torch.autograd.Function):
@@ -161,3 +169,130 @@ def sat_encoder001_f32(sat, x_coords, y_coords, conv1, conv2, conv3, n_frames):
     y1 = SatConvPool.apply(sat, x_coords, y_coords, conv1.weight, conv1.bias, int(n_frames))
     y2 = ConvPool.apply(y1, conv2.weight, conv2.bias, False)
     return ConvReLU.apply(CONV2D144_OPS, y2, conv3.weight, conv3.bias, True, False, False)
+
+
+# ---- notebooks/16_maxpool.ipynb ----------------------------------------------------------------------------------------
+class CountsConvReLU(torch.autograd.Function):
+    """First layer of notebook 16: history [N, 4, H, W] and flow prediction [N, H, W] as raw counts (int16 or f32), horizon
+    [N]; the normalised 6-channel input is built inside the kernels (forward and weight gradient), never stored.  No
+    gradient flows to the inputs."""
+
+    @staticmethod
+    def forward(ctx, history, flow_pred, horizon, weight, bias, dy_pregated):
+        history, flow_pred = history.contiguous(), flow_pred.contiguous()
+        horizon = horizon.to(torch.float32).contiguous()
+        y = K.conv2d_ae_counts_fwd_f32(history, flow_pred, horizon, weight.contiguous(), bias.contiguous())
+        ctx.save_for_backward(history, flow_pred, horizon, None if dy_pregated else y)
+        ctx.weight_shape = tuple(weight.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        history, flow_pred, horizon, y = ctx.saved_tensors
+        dy = dy.contiguous()
+        if y is not None:
+            dy = K.relu_gate_f32(dy, y)
+        dw, db = K.conv2d_ae_counts_bwd_weight_f32(history, flow_pred, horizon, dy, ctx.weight_shape)
+        return None, None, None, dw, db, None
+
+
+class ConvReLUPool32(torch.autograd.Function):
+    """relu(max_pool2d(nn.Conv2d(32, 32, 3)(x), 3)) on NCHW f32, planes up to 128 wide; saves the input and the codes."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, x_is_relu_output):
+        x = x.contiguous()
+        y, codes = K.conv2d_ae_pool_fwd_f32(x, weight.contiguous(), bias.contiguous())
+        ctx.save_for_backward(x, weight, codes)
+        ctx.x_is_relu_output = x_is_relu_output
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, codes = ctx.saved_tensors
+        dy, weight = dy.contiguous(), weight.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.conv2d_ae_pool_bwd_data_f32(dy, codes, weight, x if ctx.x_is_relu_output else None, tuple(x.shape))
+        dw, db = K.conv2d_ae_pool_bwd_weight_f32(x, dy, codes, tuple(weight.shape))
+        return dx, dw, db, None
+
+
+class ConvTranspose2dReLU(torch.autograd.Function):
+    """nn.ConvTranspose2d(C_in, C_out, 3) (+ ReLU) on NCHW f32 for (C_in, C_out) = (32, 32), (32, 16), (16, 16), (16, 1).
+    Saves the input, and the output only where backward gates dy by it (relu and not dy_pregated)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu, x_is_relu_output, dy_pregated):
+        x = x.contiguous()
+        y = K.convt2d_ae_fwd_f32(x, weight.contiguous(), bias.contiguous() if bias is not None else None, relu)
+        ctx.save_for_backward(x, weight, y if (relu and not dy_pregated) else None)
+        ctx.has_bias, ctx.x_is_relu_output = bias is not None, x_is_relu_output
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        dy, weight = dy.contiguous(), weight.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.convt2d_ae_bwd_data_f32(dy, y, weight, x if ctx.x_is_relu_output else None, tuple(x.shape))
+        dw, db = K.convt2d_ae_bwd_weight_f32(x, dy, y, tuple(weight.shape))
+        return dx, dw, (db if ctx.has_bias else None), None, None, None
+
+
+class MseCropNorm(torch.autograd.Function):
+    """F.mse_loss(y_hat, normalise(target)[..., 8:-8, 8:-8]): y_hat [N, P, Q] f32, target [N, P + 16, Q + 16] raw counts;
+    the gradient 2 (y_hat - y) / count is produced in the same pass."""
+
+    @staticmethod
+    def forward(ctx, y_hat, target):
+        out, grad = K.mse_crop_norm_f32(y_hat.contiguous(), target.contiguous(), need_grad=True)
+        ctx.save_for_backward(grad)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None
+
+
+def counts_conv_relu(history, flow_pred, horizon, weight, bias):
+    """relu(encoder_conv1(normalised 6-channel input of 16_maxpool.ipynb:13760-13779)); gradients to weight and bias only."""
+    return CountsConvReLU.apply(history, flow_pred, horizon, weight, bias, False)
+
+
+def conv2d_ae_relu(x, weight, bias, relu=True, x_is_relu_output=False):
+    """nn.Conv2d(16 or 32, 32, 3)(x) (+ ReLU), planes up to 128 wide.  x_is_relu_output: dx leaves gated by x > 0."""
+    return ConvReLU.apply(CONV2D_AE_OPS, x, weight, bias, bool(relu), bool(x_is_relu_output), False)
+
+
+def conv_relu_pool32(x, weight, bias, x_is_relu_output=False):
+    """maxpool(relu(nn.Conv2d(32, 32, 3)(x))).  x_is_relu_output: dx leaves gated by x > 0."""
+    return ConvReLUPool32.apply(x, weight, bias, bool(x_is_relu_output))
+
+
+def conv_transpose2d_relu(x, weight, bias, relu=True, x_is_relu_output=False):
+    """nn.ConvTranspose2d(C_in, C_out, 3)(x) (+ ReLU).  x_is_relu_output: dx leaves gated by x > 0."""
+    return ConvTranspose2dReLU.apply(x, weight, bias, bool(relu), bool(x_is_relu_output), False)
+
+
+def mse_crop_norm(y_hat, target):
+    """F.mse_loss(y_hat, normalise_images_in_model(target)[..., 8:-8, 8:-8]) of 16_maxpool.ipynb:13805-13809."""
+    return MseCropNorm.apply(y_hat, target)
+
+
+def nb16_autoencoder_f32(history, flow_pred, horizon, enc, dec):
+    """decoder_conv4(relu(decoder_conv3(... maxpool(relu(encoder_conv4(... relu(encoder_conv1(input))))))) of
+    16_maxpool.ipynb:13760-13801; enc = the four nn.Conv2d, dec = the four nn.ConvTranspose2d.  Every inner ReLU output has
+    one consumer, the next layer, whose data gradient leaves gated by it (x_is_relu_output), so its producer skips gating
+    the arriving gradient (dy_pregated).  The pooled output is 0 exactly where its window is dead, which the codes carry,
+    so decoder_conv1 leaves its dx ungated.  The pairing only holds inside this chain."""
+    y = CountsConvReLU.apply(history, flow_pred, horizon, enc[0].weight, enc[0].bias, True)
+    y = ConvReLU.apply(CONV2D_AE_OPS, y, enc[1].weight, enc[1].bias, True, True, True)
+    y = ConvReLU.apply(CONV2D_AE_OPS, y, enc[2].weight, enc[2].bias, True, True, True)
+    y = ConvReLUPool32.apply(y, enc[3].weight, enc[3].bias, True)
+    y = ConvTranspose2dReLU.apply(y, dec[0].weight, dec[0].bias, True, False, True)
+    y = ConvTranspose2dReLU.apply(y, dec[1].weight, dec[1].bias, True, True, True)
+    y = ConvTranspose2dReLU.apply(y, dec[2].weight, dec[2].bias, True, True, True)
+    return ConvTranspose2dReLU.apply(y, dec[3].weight, dec[3].bias, False, True, False)

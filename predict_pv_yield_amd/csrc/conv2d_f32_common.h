@@ -1,7 +1,8 @@
-// What the two exact-f32 Conv2d 3x3 files share: conv2d_f32.hip (experiments/002, 17 / 32 -> 32 / 4 channels) and
-// conv2d_pool_f32.hip (experiments/001, 144 channels with fused MaxPool2d(3)).  Their main loops stay in their own files;
-// this header holds the ordered slab sum of their weight gradients, the five synthesised input channels and the argument
-// checks both repeat.
+// What the three exact-f32 Conv2d 3x3 files share: conv2d_f32.hip (experiments/002, 17 / 32 -> 32 / 4 channels),
+// conv2d_pool_f32.hip (experiments/001, 144 channels with fused MaxPool2d(3)) and conv2d_ae_f32.hip (notebooks/16_maxpool:
+// Conv2d / ConvTranspose2d up to 128 wide).  Their main loops stay in their own files; this header holds the ordered slab
+// sum of their weight gradients (also in the ConvTranspose2d layout), the five synthesised input channels of the two
+// experiments and the argument checks all repeat.
 #pragma once
 #include "pv_common.h"
 
@@ -15,7 +16,9 @@ typedef __attribute__((ext_vector_type(4))) float acc4;
 // dw[co][j] = sum_s slabs[s][co][j] (j < k9), dbias[co] = sum_s slabs[s][co][k9] in a fixed order: block = 32 elements x 8
 // slab groups; group g adds slabs g, g + 8, ... into four interleaved partial sums (independent loads in flight), then
 // the four and the 8 groups' results are added in index order.  dw or db may be null (that part is not written).
+// TRANSPOSED: j = ci * 9 + tap' is stored as dw[ci][co][8 - tap'] (a ConvTranspose2d's [c_in][c_out][3][3] layout).
 constexpr int kSumElems = 32, kSumGroups = kBlock / kSumElems;
+template <bool TRANSPOSED>
 __global__ __launch_bounds__(kBlock) void conv2d_slab_sum_f32(const float* __restrict__ slabs, float* __restrict__ dw,
                                                               float* __restrict__ db, int c_out, int k9, int n_slabs) {
   __shared__ float part[kSumGroups][kSumElems];
@@ -38,17 +41,21 @@ __global__ __launch_bounds__(kBlock) void conv2d_slab_sum_f32(const float* __res
   for (int j = 1; j < kSumGroups; ++j) t += part[j][le];
   const int co = e / ncols, j = e - co * ncols;
   if (j < k9) {
-    if (dw) dw[co * k9 + j] = t;
+    if (!dw) return;
+    if (TRANSPOSED) dw[((j / 9) * c_out + co) * 9 + 8 - j % 9] = t;
+    else dw[co * k9 + j] = t;
   } else if (db) {
     db[co] = t;
   }
 }
 
 // launch of the slab sum over a [c_out][k9 + 1] gradient
-inline void launch_slab_sum(const void* ws, float* dw, float* db, int c_out, int k9, int n_slabs, hipStream_t st) {
+inline void launch_slab_sum(const void* ws, float* dw, float* db, int c_out, int k9, int n_slabs, hipStream_t st,
+                            bool transposed = false) {
   const int total = c_out * (k9 + 1);
-  conv2d_slab_sum_f32<<<dim3((unsigned)((total + kSumElems - 1) / kSumElems)), dim3(kBlock), 0, st>>>((const float*)ws, dw,
-                                                                                                     db, c_out, k9, n_slabs);
+  const dim3 grid((unsigned)((total + kSumElems - 1) / kSumElems)), block(kBlock);
+  if (transposed) conv2d_slab_sum_f32<true><<<grid, block, 0, st>>>((const float*)ws, dw, db, c_out, k9, n_slabs);
+  else conv2d_slab_sum_f32<false><<<grid, block, 0, st>>>((const float*)ws, dw, db, c_out, k9, n_slabs);
 }
 
 // The five synthesised channels of both experiments (k = 0..4: centre marker, geo x, geo y, pixel x, pixel y) at input row

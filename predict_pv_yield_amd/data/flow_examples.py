@@ -35,21 +35,30 @@ class ImageHasNansError(Exception):
     pass
 
 
-def load_super_batch(raw_counts: torch.Tensor, include_optical_flow: bool = True) -> Dict[str, torch.Tensor]:
-    """raw_counts: [T, H, W] 10-bit counts (int16 or float32) of consecutive 5-minute HRV images, on the device."""
+def load_super_batch(raw_counts: torch.Tensor, include_optical_flow: bool = True,
+                     normalise: bool = True) -> Dict[str, torch.Tensor]:
+    """raw_counts: [T, H, W] 10-bit counts (int16 or float32) of consecutive 5-minute HRV images, on the device.
+    normalise=False (notebooks/16_maxpool.ipynb, whose model normalises by itself): SAT_IMAGES stays the raw counts in
+    their own dtype and the predictions are the counts warped as float32 (NaN border as before); the flow is computed on
+    the raw counts either way."""
     if not raw_counts.is_cuda:
         raise RuntimeError("load_super_batch: the satellite stack must be on the MI355X (there is no CPU fallback)")
     from .. import hip_ops as K
     counts = raw_counts if raw_counts.dtype in (torch.int16, torch.float32) else raw_counts.float()
-    mean = torch.tensor([SAT_IMAGE_MEAN], device=counts.device)
-    std = torch.tensor([SAT_IMAGE_STD], device=counts.device)
     super_batch = {}
     if include_optical_flow:
         super_batch[OPTICAL_FLOW_FIELDS] = of.compute_optical_flow(counts)          # flow on the RAW counts
-    sat = K.normalise(counts.contiguous(), mean, std, inner=counts.numel())        # then normalise (:460-464)
+    if normalise:
+        mean = torch.tensor([SAT_IMAGE_MEAN], device=counts.device)
+        std = torch.tensor([SAT_IMAGE_STD], device=counts.device)
+        sat = K.normalise(counts.contiguous(), mean, std, inner=counts.numel())    # then normalise (:460-464)
+        warp_src = sat
+    else:
+        sat = counts.contiguous()
+        warp_src = sat.float()
     super_batch[SAT_IMAGES] = sat
     if include_optical_flow:
-        preds, index = of.compute_optical_flow_predictions(sat, super_batch[OPTICAL_FLOW_FIELDS])
+        preds, index = of.compute_optical_flow_predictions(warp_src, super_batch[OPTICAL_FLOW_FIELDS])
         super_batch[OPTICAL_FLOW_PREDICTIONS] = preds
         super_batch[PREDICTION_INDEX] = index
     return super_batch

@@ -1148,8 +1148,8 @@ def _grads_out(weight_shape, device):
             torch.empty((weight_shape[0],), dtype=torch.float32, device=device))
 
 
-# the plain passes of both families ("conv2d", "conv2d144"): check_channels(who, x_shape, weight_shape) is the family's
-# channel-count check, the rest is the same for both
+# the plain passes of the three families ("conv2d", "conv2d144", "conv2d_ae"): check_channels(who, x_shape, weight_shape) is the family's
+# channel-count check, the rest is the same for all
 def _conv_fwd(family, check_channels, x, weight, bias, relu):
     who = f"{family}_fwd_f32"
     check_channels(who, x.shape, weight.shape)
@@ -1350,6 +1350,227 @@ def conv2d144_sat_pool_bwd_weight_f32(sat, x_coords, y_coords, dy_pooled, codes,
                                                          ptr(dw), ptr(db), b, t, n_frames, h, w, C144, ptr(ws), nbytes,
                                                          current_stream_ptr()), "pv_conv2d144_sat_pool_bwd_weight_f32")
     return dw, db
+
+
+# ------------------------------------------------------------------------------------------------
+# notebooks/16_maxpool.ipynb: Conv2d 6 -> 16 -> 32 -> 32 -> 32 (+ MaxPool2d(3)), ConvTranspose2d 32 -> 32 -> 16 -> 16 -> 1,
+# cropped normalised MSE (csrc/conv2d_ae_f32.hip); planes up to 128 wide
+# ------------------------------------------------------------------------------------------------
+def _counts_contig(who, *ts):
+    for t in ts:
+        if t.dtype not in (torch.int16, torch.float32) or not t.is_contiguous():
+            raise TypeError(f"{who}: counts must be contiguous int16 or float32 tensors, got {t.dtype}")
+
+
+def _check_counts(who, history, flow_pred, horizon):
+    _shape_check(history.dim() == 4 and history.shape[1] == 4, who,
+                 f"history [N, 4, H, W] expected, got {tuple(history.shape)}")
+    n, _, h, w = history.shape
+    _shape_check(tuple(flow_pred.shape) == (n, h, w) and tuple(horizon.shape) == (n,), who,
+                 f"flow prediction [{n}, {h}, {w}] and horizon [{n}] expected, got {tuple(flow_pred.shape)} / "
+                 f"{tuple(horizon.shape)}")
+    require_cuda(history, flow_pred, horizon)
+    _counts_contig(who, history, flow_pred)
+    _f32_contig(horizon)
+    return n, h, w
+
+
+def _check_ae(who, x_shape, weight_shape):
+    _shape_check(len(x_shape) == 4 and len(weight_shape) == 4 and tuple(weight_shape[1:]) == (x_shape[1], 3, 3), who,
+                 f"x [N, C_in, H, W] and weight [C_out, C_in, 3, 3] expected, got {tuple(x_shape)} / {tuple(weight_shape)}")
+
+
+def _check_aet(who, x_shape, weight_shape):
+    _shape_check(len(x_shape) == 4 and len(weight_shape) == 4 and weight_shape[0] == x_shape[1]
+                 and tuple(weight_shape[2:]) == (3, 3), who,
+                 f"x [N, C_in, H, W] and weight [C_in, C_out, 3, 3] expected, got {tuple(x_shape)} / {tuple(weight_shape)}")
+
+
+def _pooled_shape_c(n, c, h, w):
+    if h < 5 or w < 5:
+        raise ValueError(f"images of at least 5 x 5 expected (one whole 3x3 pool window after the 3x3 conv), got {h} x {w}")
+    return (n, c, (h - 2) // 3, (w - 2) // 3)
+
+
+def conv2d_ae_counts_fwd_f32(history, flow_pred, horizon, weight, bias):
+    """relu(conv2d(cat(normalise(history), normalise(flow_pred)[:, None], horizon plane), weight) + bias): history
+    [N, 4, H, W] and flow_pred [N, H, W] as int16 or f32 counts, horizon [N] f32 -> [N, 16, H-2, W-2]."""
+    who = "conv2d_ae_counts_fwd_f32"
+    n, h, w = _check_counts(who, history, flow_pred, horizon)
+    co = weight.shape[0]
+    _shape_check(tuple(weight.shape) == (co, 6, 3, 3), who, f"weight [C_out, 6, 3, 3] expected, got {tuple(weight.shape)}")
+    _shape_check(bias is not None and tuple(bias.shape) == (co,), who, f"bias [{co}] expected")
+    require_cuda(weight, bias)
+    _f32_contig(weight, bias)
+    y = torch.empty((n, co, max(h - 2, 0), max(w - 2, 0)), dtype=torch.float32, device=history.device)
+    check(get_lib().pv_conv2d_ae_counts_fwd_f32(ptr(history), int(history.dtype == torch.int16), ptr(flow_pred),
+                                                int(flow_pred.dtype == torch.int16), ptr(horizon), ptr(weight), ptr(bias),
+                                                ptr(y), n, h, w, co, current_stream_ptr()), "pv_conv2d_ae_counts_fwd_f32")
+    return y
+
+
+def conv2d_ae_counts_bwd_weight_f32(history, flow_pred, horizon, dy, weight_shape):
+    """(dw [16, 6, 3, 3], dbias) of conv2d_ae_counts_fwd_f32's conv from its pre-activation gradient dy."""
+    who = "conv2d_ae_counts_bwd_weight_f32"
+    n, h, w = _check_counts(who, history, flow_pred, horizon)
+    co = weight_shape[0]
+    _shape_check(tuple(weight_shape) == (co, 6, 3, 3) and tuple(dy.shape) == (n, co, h - 2, w - 2), who,
+                 f"weight {(co, 6, 3, 3)} and dy {(n, co, h - 2, w - 2)} expected, got {tuple(weight_shape)} / "
+                 f"{tuple(dy.shape)}")
+    require_cuda(dy)
+    _f32_contig(dy)
+    ws, nbytes = _wgrad_ws("conv2d_ae", history.device, n, 6, co, h, w, 0)
+    dw, db = _grads_out(weight_shape, history.device)
+    check(get_lib().pv_conv2d_ae_counts_bwd_weight_f32(ptr(history), int(history.dtype == torch.int16), ptr(flow_pred),
+                                                       int(flow_pred.dtype == torch.int16), ptr(horizon), ptr(dy), ptr(dw),
+                                                       ptr(db), n, h, w, co, ptr(ws), nbytes, current_stream_ptr()),
+          "pv_conv2d_ae_counts_bwd_weight_f32")
+    return dw, db
+
+
+def conv2d_ae_fwd_f32(x, weight, bias, relu=True):
+    """conv2d(x, weight) + bias (+ ReLU) for (C_in, C_out) = (16, 32) or (32, 32), W <= 128."""
+    return _conv_fwd("conv2d_ae", _check_ae, x, weight, bias, relu)
+
+
+def conv2d_ae_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of conv2d_ae_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
+    return _conv_bwd_data("conv2d_ae", _check_ae, dy, dy_gate, weight, x_gate, x_shape)
+
+
+def conv2d_ae_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw, dbias) of conv2d_ae_fwd_f32; deterministic (fixed slabs summed in order)."""
+    return _conv_bwd_weight("conv2d_ae", _check_ae, x, dy, dy_gate, weight_shape, ws_args=(0,))
+
+
+def conv2d_ae_pool_fwd_f32(x, weight, bias):
+    """relu(max_pool2d(conv2d(x, weight) + bias, 3)) for x [N, 32, H, W] -> (pooled, codes uint8)."""
+    who = "conv2d_ae_pool_fwd_f32"
+    _check_ae(who, x.shape, weight.shape)
+    n, c, h, w = x.shape
+    co = weight.shape[0]
+    _shape_check(bias is not None and tuple(bias.shape) == (co,), who, f"bias [{co}] expected")
+    require_cuda(x, weight, bias)
+    _f32_contig(x, weight, bias)
+    y = torch.empty(_pooled_shape_c(n, co, h, w), dtype=torch.float32, device=x.device)
+    codes = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
+    nbytes = ctypes.c_size_t(0)
+    check(get_lib().pv_conv2d_ae_pool_fwd_workspace_bytes(n, c, co, h, w, ctypes.byref(nbytes)),
+          "pv_conv2d_ae_pool_fwd_workspace_bytes")
+    ws = _workspace("conv2d_ae_pool_fwd", nbytes.value, x.device) if nbytes.value else None
+    check(get_lib().pv_conv2d_ae_pool_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(codes), n, c, co, h, w, ptr(ws),
+                                              nbytes.value, current_stream_ptr()), "pv_conv2d_ae_pool_fwd_f32")
+    return y, codes
+
+
+def conv2d_ae_pool_bwd_data_f32(dy_pooled, codes, weight, x_gate, x_shape):
+    """dx of conv2d_ae_pool_fwd_f32 from the pooled gradient and the forward's codes; dx zeroed where x_gate <= 0."""
+    who = "conv2d_ae_pool_bwd_data_f32"
+    _check_ae(who, x_shape, weight.shape)
+    n, c, h, w = x_shape
+    p_shape = _pooled_shape_c(n, weight.shape[0], h, w)
+    _shape_check(tuple(dy_pooled.shape) == p_shape and tuple(codes.shape) == p_shape, who,
+                 f"dy_pooled / codes {p_shape} expected, got {tuple(dy_pooled.shape)} / {tuple(codes.shape)}")
+    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
+    require_cuda(dy_pooled, codes, weight, x_gate)
+    _f32_contig(dy_pooled, weight, x_gate)
+    _u8_contig(who, codes)
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy_pooled.device)
+    check(get_lib().pv_conv2d_ae_pool_bwd_data_f32(ptr(dy_pooled), ptr(codes), ptr(weight), ptr(dx), ptr(x_gate), n, c,
+                                                   weight.shape[0], h, w, current_stream_ptr()),
+          "pv_conv2d_ae_pool_bwd_data_f32")
+    return dx
+
+
+def conv2d_ae_pool_bwd_weight_f32(x, dy_pooled, codes, weight_shape):
+    """(dw, dbias) of conv2d_ae_pool_fwd_f32 from the pooled gradient and the codes; deterministic."""
+    who = "conv2d_ae_pool_bwd_weight_f32"
+    _check_ae(who, x.shape, weight_shape)
+    n, c, h, w = x.shape
+    co = weight_shape[0]
+    p_shape = _pooled_shape_c(n, co, h, w)
+    _shape_check(tuple(dy_pooled.shape) == p_shape and tuple(codes.shape) == p_shape, who,
+                 f"dy_pooled / codes {p_shape} expected, got {tuple(dy_pooled.shape)} / {tuple(codes.shape)}")
+    require_cuda(x, dy_pooled, codes)
+    _f32_contig(x, dy_pooled)
+    _u8_contig(who, codes)
+    ws, nbytes = _wgrad_ws("conv2d_ae", x.device, n, c, co, h, w, 1)
+    dw, db = _grads_out(tuple(weight_shape), x.device)
+    check(get_lib().pv_conv2d_ae_pool_bwd_weight_f32(ptr(x), ptr(dy_pooled), ptr(codes), ptr(dw), ptr(db), n, c, co, h, w,
+                                                     ptr(ws), nbytes, current_stream_ptr()),
+          "pv_conv2d_ae_pool_bwd_weight_f32")
+    return dw, db
+
+
+def convt2d_ae_fwd_f32(x, weight, bias, relu=True):
+    """conv_transpose2d(x, weight) + bias (+ ReLU): x [N, C_in, H, W], weight [C_in, C_out, 3, 3] -> [N, C_out, H+2, W+2]."""
+    who = "convt2d_ae_fwd_f32"
+    _check_aet(who, x.shape, weight.shape)
+    n, ci, h, w = x.shape
+    co = weight.shape[1]
+    _check_bias(who, bias, co)
+    require_cuda(x, weight, bias)
+    _f32_contig(x, weight, bias)
+    y = torch.empty((n, co, h + 2, w + 2), dtype=torch.float32, device=x.device)
+    check(get_lib().pv_convt2d_ae_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, int(relu),
+                                          current_stream_ptr()), "pv_convt2d_ae_fwd_f32")
+    return y
+
+
+def convt2d_ae_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of convt2d_ae_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
+    who = "convt2d_ae_bwd_data_f32"
+    _check_aet(who, x_shape, weight.shape)
+    n, ci, h, w = x_shape
+    co = weight.shape[1]
+    y_shape = (n, co, h + 2, w + 2)
+    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
+                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
+    require_cuda(dy, dy_gate, weight, x_gate)
+    _f32_contig(dy, dy_gate, weight, x_gate)
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
+    check(get_lib().pv_convt2d_ae_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci, co, h, w,
+                                               current_stream_ptr()), "pv_convt2d_ae_bwd_data_f32")
+    return dx
+
+
+def convt2d_ae_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw [C_in, C_out, 3, 3], dbias [C_out]) of convt2d_ae_fwd_f32; deterministic (fixed slabs summed in order)."""
+    who = "convt2d_ae_bwd_weight_f32"
+    _check_aet(who, x.shape, weight_shape)
+    n, ci, h, w = x.shape
+    co = weight_shape[1]
+    y_shape = (n, co, h + 2, w + 2)
+    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
+                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    require_cuda(x, dy, dy_gate)
+    _f32_contig(x, dy, dy_gate)
+    ws, nbytes = _wgrad_ws("convt2d_ae", x.device, n, ci, co, h, w)
+    dw = torch.empty(tuple(weight_shape), dtype=torch.float32, device=x.device)
+    db = torch.empty((co,), dtype=torch.float32, device=x.device)
+    check(get_lib().pv_convt2d_ae_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, ptr(ws),
+                                                 nbytes, current_stream_ptr()), "pv_convt2d_ae_bwd_weight_f32")
+    return dw, db
+
+
+def mse_crop_norm_f32(y_hat, target, need_grad=True):
+    """mse_loss(y_hat, normalise(target)[..., 8:-8, 8:-8]) for y_hat [N, P, Q] f32 and target [N, P+16, Q+16] counts (int16
+    or f32).  Returns (loss f32[1], dy_hat or None)."""
+    who = "mse_crop_norm_f32"
+    _shape_check(y_hat.dim() == 3 and target.dim() == 3 and target.shape[0] == y_hat.shape[0], who,
+                 f"y_hat [N, P, Q] and target [N, T, U] expected, got {tuple(y_hat.shape)} / {tuple(target.shape)}")
+    require_cuda(y_hat, target)
+    _f32_contig(y_hat)
+    _counts_contig(who, target)
+    n, oh, ow = y_hat.shape
+    loss = torch.empty((1,), dtype=torch.float32, device=y_hat.device)
+    grad = torch.empty_like(y_hat) if need_grad else None
+    ws = _workspace("mse_crop_norm", 4 * n, y_hat.device)
+    check(get_lib().pv_mse_crop_norm_f32(ptr(y_hat), ptr(target), int(target.dtype == torch.int16), n, oh, ow,
+                                         target.shape[1], target.shape[2], ptr(loss), ptr(grad), ptr(ws), 4 * n,
+                                         current_stream_ptr()), "pv_mse_crop_norm_f32")
+    return loss, grad
 
 
 def maxpool3d_fwd_f32(x, kernel=3, stride=None, padding=0):
