@@ -36,6 +36,10 @@ from . import hip_ops as K
 CONV2D_OPS = (K.conv2d_fwd_f32, K.conv2d_bwd_data_f32, K.conv2d_bwd_weight_f32)
 CONV2D144_OPS = (K.conv2d144_fwd_f32, K.conv2d144_bwd_data_f32, K.conv2d144_bwd_weight_f32)
 CONV2D_AE_OPS = (K.conv2d_ae_fwd_f32, K.conv2d_ae_bwd_data_f32, K.conv2d_ae_bwd_weight_f32)
+CONVT2D_AE_OPS = (K.convt2d_ae_fwd_f32, K.convt2d_ae_bwd_data_f32, K.convt2d_ae_bwd_weight_f32)
+# ... and of the conv with fused MaxPool2d(3): the forward returns (pooled, codes), the gradients take the codes
+CONV2D144_POOL_OPS = (K.conv2d144_pool_fwd_f32, K.conv2d144_pool_bwd_data_f32, K.conv2d144_pool_bwd_weight_f32)
+CONV2D_AE_POOL_OPS = (K.conv2d_ae_pool_fwd_f32, K.conv2d_ae_pool_bwd_data_f32, K.conv2d_ae_pool_bwd_weight_f32)
 
 
 class CoordsConv2dReLU(torch.autograd.Function):
@@ -61,8 +65,10 @@ class CoordsConv2dReLU(torch.autograd.Function):
 
 
 class ConvReLU(torch.autograd.Function):
-    """nn.Conv2d(C_in, C_out, 3) (+ ReLU) on NCHW f32 through one family of entry points, ops = CONV2D_OPS (32 -> 32 or 4)
-    or CONV2D144_OPS (144 -> 144)."""
+    """nn.Conv2d(C_in, C_out, 3) (+ ReLU) on NCHW f32 through one family of entry points, ops = CONV2D_OPS (32 -> 32 or 4),
+    CONV2D144_OPS (144 -> 144) or CONV2D_AE_OPS (16 or 32 -> 32, planes up to 128 wide); with CONVT2D_AE_OPS,
+    nn.ConvTranspose2d(C_in, C_out, 3) for (C_in, C_out) = (32, 32), (32, 16), (16, 16), (16, 1).  Saves the input, and the
+    output only where backward gates dy by it (relu and not dy_pregated)."""
 
     @staticmethod
     def forward(ctx, ops, x, weight, bias, relu, x_is_relu_output, dy_pregated):
@@ -104,25 +110,27 @@ class SatConvPool(torch.autograd.Function):
 
 
 class ConvPool(torch.autograd.Function):
-    """relu(max_pool2d(nn.Conv2d(144, 144, 3)(x), 3)) on NCHW f32."""
+    """relu(max_pool2d(nn.Conv2d(C, C, 3)(x), 3)) on NCHW f32, ops = CONV2D144_POOL_OPS (C = 144) or CONV2D_AE_POOL_OPS (C =
+    32, planes up to 128 wide); saves the input and the codes."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, x_is_relu_output):
+    def forward(ctx, ops, x, weight, bias, x_is_relu_output):
         x = x.contiguous()
-        y, codes = K.conv2d144_pool_fwd_f32(x, weight.contiguous(), bias.contiguous())
+        y, codes = ops[0](x, weight.contiguous(), bias.contiguous())
         ctx.save_for_backward(x, weight, codes)
-        ctx.x_is_relu_output = x_is_relu_output
+        ctx.ops, ctx.x_is_relu_output = ops, x_is_relu_output
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, weight, codes = ctx.saved_tensors
+        _, bwd_data, bwd_weight = ctx.ops
         dy, weight = dy.contiguous(), weight.contiguous()
         dx = None
-        if ctx.needs_input_grad[0]:
-            dx = K.conv2d144_pool_bwd_data_f32(dy, codes, weight, x if ctx.x_is_relu_output else None, tuple(x.shape))
-        dw, db = K.conv2d144_pool_bwd_weight_f32(x, dy, codes, tuple(weight.shape))
-        return dx, dw, db, None
+        if ctx.needs_input_grad[1]:
+            dx = bwd_data(dy, codes, weight, x if ctx.x_is_relu_output else None, tuple(x.shape))
+        dw, db = bwd_weight(x, dy, codes, tuple(weight.shape))
+        return None, dx, dw, db, None
 
 
 def coords_conv2d_relu(sat, x_coords, y_coords, weight, bias, t_per_example):
@@ -154,7 +162,7 @@ def sat_conv_pool_f32(sat, x_coords, y_coords, weight, bias, n_frames):
 
 def conv_pool_f32(x, weight, bias, x_is_relu_output=False):
     """maxpool(relu(nn.Conv2d(144, 144, 3)(x))).  x_is_relu_output: dx leaves gated by x > 0."""
-    return ConvPool.apply(x, weight, bias, bool(x_is_relu_output))
+    return ConvPool.apply(CONV2D144_POOL_OPS, x, weight, bias, bool(x_is_relu_output))
 
 
 def conv144_relu(x, weight, bias, relu=True, x_is_relu_output=False):
@@ -167,7 +175,7 @@ def sat_encoder001_f32(sat, x_coords, y_coords, conv1, conv2, conv3, n_frames):
     nn.Conv2d.  [B, 144, 11, 11] at 128 x 128.  conv2 and conv3 read pooled outputs, whose layers route the gradient through
     their codes, so their dx is not gated again."""
     y1 = SatConvPool.apply(sat, x_coords, y_coords, conv1.weight, conv1.bias, int(n_frames))
-    y2 = ConvPool.apply(y1, conv2.weight, conv2.bias, False)
+    y2 = ConvPool.apply(CONV2D144_POOL_OPS, y1, conv2.weight, conv2.bias, False)
     return ConvReLU.apply(CONV2D144_OPS, y2, conv3.weight, conv3.bias, True, False, False)
 
 
@@ -194,51 +202,6 @@ class CountsConvReLU(torch.autograd.Function):
             dy = K.relu_gate_f32(dy, y)
         dw, db = K.conv2d_ae_counts_bwd_weight_f32(history, flow_pred, horizon, dy, ctx.weight_shape)
         return None, None, None, dw, db, None
-
-
-class ConvReLUPool32(torch.autograd.Function):
-    """relu(max_pool2d(nn.Conv2d(32, 32, 3)(x), 3)) on NCHW f32, planes up to 128 wide; saves the input and the codes."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, x_is_relu_output):
-        x = x.contiguous()
-        y, codes = K.conv2d_ae_pool_fwd_f32(x, weight.contiguous(), bias.contiguous())
-        ctx.save_for_backward(x, weight, codes)
-        ctx.x_is_relu_output = x_is_relu_output
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight, codes = ctx.saved_tensors
-        dy, weight = dy.contiguous(), weight.contiguous()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = K.conv2d_ae_pool_bwd_data_f32(dy, codes, weight, x if ctx.x_is_relu_output else None, tuple(x.shape))
-        dw, db = K.conv2d_ae_pool_bwd_weight_f32(x, dy, codes, tuple(weight.shape))
-        return dx, dw, db, None
-
-
-class ConvTranspose2dReLU(torch.autograd.Function):
-    """nn.ConvTranspose2d(C_in, C_out, 3) (+ ReLU) on NCHW f32 for (C_in, C_out) = (32, 32), (32, 16), (16, 16), (16, 1).
-    Saves the input, and the output only where backward gates dy by it (relu and not dy_pregated)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, relu, x_is_relu_output, dy_pregated):
-        x = x.contiguous()
-        y = K.convt2d_ae_fwd_f32(x, weight.contiguous(), bias.contiguous() if bias is not None else None, relu)
-        ctx.save_for_backward(x, weight, y if (relu and not dy_pregated) else None)
-        ctx.has_bias, ctx.x_is_relu_output = bias is not None, x_is_relu_output
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight, y = ctx.saved_tensors
-        dy, weight = dy.contiguous(), weight.contiguous()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = K.convt2d_ae_bwd_data_f32(dy, y, weight, x if ctx.x_is_relu_output else None, tuple(x.shape))
-        dw, db = K.convt2d_ae_bwd_weight_f32(x, dy, y, tuple(weight.shape))
-        return dx, dw, (db if ctx.has_bias else None), None, None, None
 
 
 class MseCropNorm(torch.autograd.Function):
@@ -269,12 +232,12 @@ def conv2d_ae_relu(x, weight, bias, relu=True, x_is_relu_output=False):
 
 def conv_relu_pool32(x, weight, bias, x_is_relu_output=False):
     """maxpool(relu(nn.Conv2d(32, 32, 3)(x))).  x_is_relu_output: dx leaves gated by x > 0."""
-    return ConvReLUPool32.apply(x, weight, bias, bool(x_is_relu_output))
+    return ConvPool.apply(CONV2D_AE_POOL_OPS, x, weight, bias, bool(x_is_relu_output))
 
 
 def conv_transpose2d_relu(x, weight, bias, relu=True, x_is_relu_output=False):
     """nn.ConvTranspose2d(C_in, C_out, 3)(x) (+ ReLU).  x_is_relu_output: dx leaves gated by x > 0."""
-    return ConvTranspose2dReLU.apply(x, weight, bias, bool(relu), bool(x_is_relu_output), False)
+    return ConvReLU.apply(CONVT2D_AE_OPS, x, weight, bias, bool(relu), bool(x_is_relu_output), False)
 
 
 def mse_crop_norm(y_hat, target):
@@ -291,8 +254,8 @@ def nb16_autoencoder_f32(history, flow_pred, horizon, enc, dec):
     y = CountsConvReLU.apply(history, flow_pred, horizon, enc[0].weight, enc[0].bias, True)
     y = ConvReLU.apply(CONV2D_AE_OPS, y, enc[1].weight, enc[1].bias, True, True, True)
     y = ConvReLU.apply(CONV2D_AE_OPS, y, enc[2].weight, enc[2].bias, True, True, True)
-    y = ConvReLUPool32.apply(y, enc[3].weight, enc[3].bias, True)
-    y = ConvTranspose2dReLU.apply(y, dec[0].weight, dec[0].bias, True, False, True)
-    y = ConvTranspose2dReLU.apply(y, dec[1].weight, dec[1].bias, True, True, True)
-    y = ConvTranspose2dReLU.apply(y, dec[2].weight, dec[2].bias, True, True, True)
-    return ConvTranspose2dReLU.apply(y, dec[3].weight, dec[3].bias, False, True, False)
+    y = ConvPool.apply(CONV2D_AE_POOL_OPS, y, enc[3].weight, enc[3].bias, True)
+    y = ConvReLU.apply(CONVT2D_AE_OPS, y, dec[0].weight, dec[0].bias, True, False, True)
+    y = ConvReLU.apply(CONVT2D_AE_OPS, y, dec[1].weight, dec[1].bias, True, True, True)
+    y = ConvReLU.apply(CONVT2D_AE_OPS, y, dec[2].weight, dec[2].bias, True, True, True)
+    return ConvReLU.apply(CONVT2D_AE_OPS, y, dec[3].weight, dec[3].bias, False, True, False)

@@ -3,7 +3,8 @@
 // 32 -> 32 with MaxPool2d(3) fused into the fourth layer, ConvTranspose2d 3x3 (stride 1, no padding) 32 -> 32 -> 16 -> 16 ->
 // 1, and the cropped, normalised MSE.  Planes are up to 128 wide.
 //
-// Every convolution pass is one of two implicit GEMMs over a tile of tr x tc output positions of one image staged in LDS:
+// Every convolution pass is one of the two implicit GEMMs of conv2d_tile_f32.h over a tile of tr x tc output positions of
+// one image staged in LDS:
 //   forward-like  D[m][pos]  = sum_{tap, c} A[m][(tap, c)] * X[c][pos + tap]     A = weights, held in VGPRs
 //   wgrad-like    D[m][col]  = sum_{pos} G[m][pos] * X[c][pos + tap]             col = (c, tap), plus a ones column
 // Conv2d forward is the first with pad 0; its data gradient is the first over dy zero-padded by 2 with mirrored,
@@ -20,277 +21,31 @@
 // the staged halo tile within 64 KB (two blocks per CU): 5 rows x 64 columns at 32 channels, 8 x 64 at 16.  The weight
 // gradient also stages the tile's G rows, so its tiles are chosen by the smallest halo overhead that fits.
 // First layer: history [B][4][S][S] and the flow prediction [B][S][S] are read in place as int16 or f32 counts, normalised
-// ((v - 93.23458) / 115.34247: subtract, then a true f32 divide) while staged; the horizon plane is synthesised.
-// Pooling follows conv2d_pool_f32.hip: the forward pools the pre-activations of a tile of whole windows, applies ReLU to the
-// maxima, and writes one code byte per pooled output (0..8 = first maximum, row-major; 255 = maximum <= 0, no gradient);
-// backward passes expand the pooled gradient through the codes while staging.  Weight gradients: fixed slabs, each block
-// writing its partial sums to its own workspace slab, added in slab order (no atomics, identical bits run to run).
-#include "conv2d_f32_common.h"
+// ((v - 93.23458) / 115.34247: subtract, then a true f32 divide) while staged; the horizon plane is synthesised
+// (load_in<SRC_COUNTS>).  Pooling follows conv2d_pool_f32.hip through the shared pool3_relu / pool3_expand: the forward
+// pools the pre-activations of a tile of whole windows, applies ReLU to the maxima, and writes one code byte per pooled
+// output (0..8 = first maximum, row-major; 255 = maximum <= 0, no gradient); backward passes expand the pooled gradient
+// through the codes while staging.  Weight gradients: fixed slabs, each block writing its partial sums to its own
+// workspace slab, added in slab order (no atomics, identical bits run to run).
+#include "conv2d_tile_f32.h"
 
 namespace pv {
 namespace {
 
-constexpr uint8_t kDead = 255;
 constexpr float kCountMean = 93.23458f, kCountStd = 115.34247f;   // 16_maxpool.ipynb: normalise_images_in_model
 constexpr int kMaxWidth = 128, kCrop = 8, kMinSide = 11;
-constexpr int kLdsFloats = 16 * 1024;                             // 64 KB
-constexpr int kMaxSlabs = 512;
-
-enum Src { SRC_PLAIN = 0, SRC_COUNTS = 1, SRC_POOLED = 2 };
-
-struct In {
-  // SRC_PLAIN: x[n][c][h][w] f32, zeroed where gate <= 0 (gate may be null)
-  // SRC_COUNTS: x = history [n][4][h][w], flow [n][h][w] (int16 or f32 counts), horizon [n]: 6 channels
-  // SRC_POOLED: the pre-pool gradient [n][c][h][w] with element (r, col) = x[r / 3][col / 3] where the window's code is
-  //             (r % 3) * 3 + col % 3 (and r < 3 ph, col < 3 pw), else 0
-  const void* x;
-  const float* gate;
-  const uint8_t* codes;
-  const void* flow;
-  const float* horizon;
-  int c, h, w, ph, pw, x_i16, flow_i16;
-};
 
 __device__ __forceinline__ float count_at(const void* p, int is_i16, size_t off) {
   const float v = is_i16 ? (float)((const int16_t*)p)[off] : ((const float*)p)[off];
   return __fdiv_rn(v - kCountMean, kCountStd);
 }
 
-// input channel ch (0 <= ch < c) of image n at (r, col), inside [0, h) x [0, w)
-template <int SRC>
-__device__ __forceinline__ float load_in(const In& s, int n, int ch, int r, int col) {
-  if (SRC == SRC_COUNTS) {
-    if (ch < 4) return count_at(s.x, s.x_i16, (((size_t)n * 4 + ch) * s.h + r) * s.w + col);
-    if (ch == 4) return count_at(s.flow, s.flow_i16, ((size_t)n * s.h + r) * s.w + col);
-    return s.horizon[n];
-  } else if (SRC == SRC_POOLED) {
-    const int pr = r / 3, pc = col / 3;
-    if (pr >= s.ph || pc >= s.pw) return 0.0f;
-    const size_t off = (((size_t)n * s.c + ch) * s.ph + pr) * s.pw + pc;
-    return (int)s.codes[off] == (r - pr * 3) * 3 + (col - pc * 3) ? ((const float*)s.x)[off] : 0.0f;
-  } else {
-    const size_t off = (((size_t)n * s.c + ch) * s.h + r) * s.w + col;
-    const float v = ((const float*)s.x)[off];
-    return (s.gate && !(s.gate[off] > 0.0f)) ? 0.0f : v;
-  }
-}
-
-// Stage channels [0, cinp) x rows [r0, r0 + rows) x columns [c0, c0 + cols) of image n as lds[ch][r][col]; outside the
-// image (padding) and beyond the source's channels: 0.
-template <int SRC>
-__device__ void stage_in(float* lds, const In& s, int n, int cinp, int r0, int rows, int c0, int cols) {
-  const int tot = cinp * rows * cols;
-  for (int i = threadIdx.x; i < tot; i += kBlock) {
-    const int col = i % cols, r = (i / cols) % rows, ch = i / (cols * rows);
-    const int ir = r0 + r, ic = c0 + col;
-    float v = 0.0f;
-    if (ch < s.c && ir >= 0 && ir < s.h && ic >= 0 && ic < s.w) v = load_in<SRC>(s, n, ch, ir, ic);
-    lds[i] = v;
-  }
-}
-
-struct Fwd {
-  In in;
-  const float* w;          // element (m, c, tap) at w[m * w_sm + c * w_sc + (flip ? 8 - tap : tap)]
-  const float* bias;       // [m_out] or null
-  float* y;                // POOL: pooled [n][m_out][h_out / 3][w_out / 3]; else [n][m_out][h_out][w_out]
-  uint8_t* codes;          // POOL: same shape as y
-  const float* out_gate;   // y zeroed where out_gate <= 0 (same layout as y); may be null
-  int m_out, pad, h_out, w_out, tr, tc, n_rb, n_cb, w_sm, w_sc, flip, relu;
-};
-
-// Forward-like pass.  Block = (image, row band, column band): tr x tc output positions flattened row-major, wave w takes
-// the 16-position tiles w, w + 4, ...  CINP = input channels rounded up to 4 (one MFMA k-step = 4 channels of one tap), MT
-// = 16-row tiles of output channels.  Per tile: 9 * CINP / 4 k-steps, each one ds_read_b32 (B: 4 channels x 16 positions)
-// feeding MT MFMAs against weights resident in VGPRs (A: 16 output channels x 4 channels).  POOL: the tile is one row of
-// whole windows (3 x 3 k positions); pre-activations go to LDS behind the staged tile, then every thread takes (channel,
-// window) pairs: bias, max over the window in row-major order (first maximum wins), ReLU.
-template <int CINP, int MT, int SRC, bool POOL>
-__global__ __launch_bounds__(kBlock) void ae_conv_fwd(Fwd a) {
-  extern __shared__ float lds[];
-  constexpr int KS = CINP / 4;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int bid = blockIdx.x;
-  const int cb = bid % a.n_cb; bid /= a.n_cb;
-  const int rb = bid % a.n_rb;
-  const int n = bid / a.n_rb;
-  const int r0 = rb * a.tr, c0 = cb * a.tc;
-  const int rows = min(a.tr, a.h_out - r0), cols = min(a.tc, a.w_out - c0);
-  const int sw = cols + 2, cs = (rows + 2) * sw, npos = rows * cols;
-
-  // weights: lane holds A[m = mt * 16 + lane % 16][c = s * 4 + lane / 16] of every tap
-  float wa[MT][9][KS];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    const int m = mt * 16 + (lane & 15);
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        const int c = s * 4 + (lane >> 4);
-        wa[mt][tap][s] = (m < a.m_out && c < a.in.c) ? a.w[m * a.w_sm + c * a.w_sc + (a.flip ? 8 - tap : tap)] : 0.0f;
-      }
-    }
-  }
-
-  stage_in<SRC>(lds, a.in, n, CINP, r0 - a.pad, rows + 2, c0 - a.pad, sw);
-  __syncthreads();
-  float* pre = lds + CINP * cs;   // POOL: [MT * 16][npos]
-
-  const int tiles = (npos + 15) / 16;
-  for (int t = wave; t < tiles; t += 4) {
-    const int p = t * 16 + (lane & 15);
-    const bool valid = p < npos;
-    const int pp = valid ? p : 0;
-    const int oh = pp / cols, ow = pp - oh * cols;
-    const float* src = lds + (lane >> 4) * cs + oh * sw + ow;
-    acc4 acc[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt] = (acc4){0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const float* st = src + (tap / 3) * sw + (tap % 3);
-#pragma unroll
-      for (int s = 0; s < KS; ++s) {
-        const float b = st[s * 4 * cs];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[mt][tap][s], b, acc[mt], 0, 0, 0);
-      }
-    }
-    if (!valid) continue;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int m = mt * 16 + (lane >> 4) * 4 + i;
-        if (POOL) {
-          pre[m * npos + p] = acc[mt][i];
-        } else if (m < a.m_out) {
-          const size_t off = (((size_t)n * a.m_out + m) * a.h_out + r0 + oh) * a.w_out + c0 + ow;
-          float v = acc[mt][i] + (a.bias ? a.bias[m] : 0.0f);
-          if (a.relu) v = v > 0.0f ? v : 0.0f;
-          if (a.out_gate && !(a.out_gate[off] > 0.0f)) v = 0.0f;
-          a.y[off] = v;
-        }
-      }
-  }
-  if (!POOL) return;
-
-  __syncthreads();
-  const int pw_tile = cols / 3, ph = a.h_out / 3, pw = a.w_out / 3;
-  for (int e = threadIdx.x; e < MT * 16 * pw_tile; e += kBlock) {
-    const int m = e / pw_tile, wc = e - m * pw_tile;
-    if (m >= a.m_out) continue;
-    const float bm = a.bias ? a.bias[m] : 0.0f;
-    float best = -__builtin_inff();
-    int code = 0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const float v = pre[m * npos + (k / 3) * cols + wc * 3 + k % 3] + bm;
-      if (v > best || __builtin_isnan(v)) best = v, code = k;   // first maximum wins; NaN propagates (torch CPU)
-    }
-    const bool live = best > 0.0f || __builtin_isnan(best);
-    const size_t off = (((size_t)n * a.m_out + m) * ph + rb) * pw + c0 / 3 + wc;
-    a.y[off] = live ? best : 0.0f;
-    a.codes[off] = live ? (uint8_t)code : kDead;
-  }
-}
-
-// wgrad-like pass.  D[m][col] over the positions of every (image, tile) item of this block's slab; col = c * 9 + tap for
-// col < in.c * 9, col == in.c * 9 is a column of ones (dbias), the rest zero.  Wave w owns the 16-column tiles w, w + 4, ...
-// (NTW at most) against all MT row tiles; a k-step is 4 positions (A: g, 16 rows x 4 positions; B: 4 positions x 16
-// columns).  The tile's g lives in LDS as [MT * 16][dps] (zero beyond m_out and beyond the tile), x as [cinp][tr + 2][tc +
-// 2] read from (r0 - pad, c0 - pad), plus xo[pos] = the position's offset in the x tile.
-struct Wg {
-  In in;                    // the operand that slides under the taps
-  In g;                     // the operand at the output positions, c = m_out rows
-  float* slabs;             // [n_slabs][m_out][in.c * 9 + 1]
-  int pad, h_out, w_out, tr, tc, n_rb, n_cb, items, per, cinp;
-};
-
-template <int MT, int NTW, int XSRC, int GSRC>
-__global__ __launch_bounds__(kBlock) void ae_conv_wgrad(Wg q) {
-  extern __shared__ float lds[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int k9 = q.in.c * 9, ncols = k9 + 1, nt = (ncols + 15) / 16;
-  const int sw = q.tc + 2, cs = (q.tr + 2) * sw;
-  const int dps = (q.tr * q.tc + 3) & ~3;
-  float* xl = lds;
-  float* dl = xl + q.cinp * cs;
-  int* xo = (int*)(dl + MT * 16 * dps);
-
-  int coff[NTW];
-  float bmul[NTW], badd[NTW];
-#pragma unroll
-  for (int j = 0; j < NTW; ++j) {
-    const int col = (wave + 4 * j) * 16 + (lane & 15);
-    const bool real = col < k9;
-    const int ci = real ? col / 9 : 0, tap = real ? col % 9 : 0;
-    coff[j] = ci * cs + (tap / 3) * sw + tap % 3;
-    bmul[j] = real ? 1.0f : 0.0f;
-    badd[j] = col == k9 ? 1.0f : 0.0f;
-  }
-  acc4 acc[MT][NTW];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int j = 0; j < NTW; ++j) acc[mt][j] = (acc4){0.0f, 0.0f, 0.0f, 0.0f};
-
-  const int it0 = blockIdx.x * q.per, it1 = min(it0 + q.per, q.items);
-  for (int it = it0; it < it1; ++it) {
-    const int cb = it % q.n_cb, rb = (it / q.n_cb) % q.n_rb, n = it / (q.n_cb * q.n_rb);
-    const int r0 = rb * q.tr, c0 = cb * q.tc;
-    const int rows = min(q.tr, q.h_out - r0), cols = min(q.tc, q.w_out - c0), npos = rows * cols;
-    __syncthreads();   // the previous item's reads are done
-    stage_in<XSRC>(xl, q.in, n, q.cinp, r0 - q.pad, q.tr + 2, c0 - q.pad, sw);
-    for (int i = threadIdx.x; i < MT * 16 * dps; i += kBlock) {
-      const int m = i / dps, p = i - m * dps;
-      float v = 0.0f;
-      if (m < q.g.c && p < npos) {
-        const int oh = p / cols, ow = p - oh * cols;
-        v = load_in<GSRC>(q.g, n, m, r0 + oh, c0 + ow);
-      }
-      dl[i] = v;
-    }
-    for (int p = threadIdx.x; p < dps; p += kBlock) {
-      const int oh = p / cols, ow = p - oh * cols;
-      xo[p] = p < npos ? oh * sw + ow : 0;
-    }
-    __syncthreads();
-    if (wave < nt) {
-      const int steps = (npos + 3) / 4;
-      for (int s = 0; s < steps; ++s) {
-        const int p = s * 4 + (lane >> 4);
-        const int xoff = xo[p];
-        float av[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) av[mt] = dl[(mt * 16 + (lane & 15)) * dps + p];
-#pragma unroll
-        for (int j = 0; j < NTW; ++j) {
-          if (wave + 4 * j < nt) {
-            const float b = xl[coff[j] + xoff] * bmul[j] + badd[j];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], b, acc[mt][j], 0, 0, 0);
-          }
-        }
-      }
-    }
-  }
-  // this slab's partial sums: D row m = mt * 16 + (lane / 16) * 4 + i, column = tile * 16 + lane % 16
-  float* out = q.slabs + (size_t)blockIdx.x * q.g.c * ncols;
-#pragma unroll
-  for (int j = 0; j < NTW; ++j) {
-    const int col = (wave + 4 * j) * 16 + (lane & 15);
-    if (wave + 4 * j < nt && col < ncols) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int m = mt * 16 + (lane >> 4) * 4 + i;
-          if (m < q.g.c) out[m * ncols + col] = acc[mt][j][i];
-        }
-    }
-  }
+// SRC_COUNTS: the four history frames and the flow prediction normalised in place, then the horizon plane
+template <>
+__device__ __forceinline__ float load_in<SRC_COUNTS>(const In& s, int n, int ch, int r, int col) {
+  if (ch < 4) return count_at(s.x, s.x_i16, (((size_t)n * 4 + ch) * s.h + r) * s.w + col);
+  if (ch == 4) return count_at(s.flow, s.flow_i16, ((size_t)n * s.h + r) * s.w + col);
+  return s.horizon[n];
 }
 
 // Cropped, normalised MSE (16_maxpool.ipynb, _training_or_validation_step): block b takes example b; d = y_hat - (target[8
@@ -354,31 +109,10 @@ void fwd_tiles(Fwd& a, int cinp, bool pool) {
   a.tr = (a.h_out + a.n_rb - 1) / a.n_rb;
 }
 
-size_t fwd_lds_bytes(const Fwd& a, int cinp, int mt, bool pool) {
-  size_t f = (size_t)cinp * (a.tr + 2) * (a.tc + 2);
-  if (pool) f += (size_t)mt * 16 * a.tr * a.tc;
-  return f * sizeof(float);
-}
-
 template <int CINP, int MT, int SRC, bool POOL>
 int run_fwd(const char* who, Fwd a, int n, hipStream_t st) {
   fwd_tiles(a, CINP, POOL);
-  const size_t lds = fwd_lds_bytes(a, CINP, MT, POOL);
-  PV_REQUIRE(lds <= kLdsFloats * sizeof(float), PV_ESIZE, "%s: tile of %zu bytes beyond the LDS budget", who, lds);
-  const long long blocks = (long long)n * a.n_rb * a.n_cb;
-  PV_REQUIRE(blocks > 0 && blocks < (1LL << 31), PV_ESIZE, "%s: grid of %lld blocks", who, blocks);
-  ae_conv_fwd<CINP, MT, SRC, POOL><<<dim3((unsigned)blocks), dim3(kBlock), lds, st>>>(a);
-  return check_launch(who);
-}
-
-struct WgPlan {
-  int h_out, w_out, tr, tc, n_rb, n_cb, items, n_slabs, per, cinp, mt;
-  size_t lds, ws;
-};
-
-size_t wg_lds_floats(int cinp, int mt, int tr, int tc) {
-  const size_t dps = ((size_t)tr * tc + 3) & ~(size_t)3;
-  return (size_t)cinp * (tr + 2) * (tc + 2) + (size_t)mt * 16 * dps + dps;
+  return launch_fwd<CINP, MT, SRC, POOL>(who, a, n, st);
 }
 
 // (h_out, w_out) = the positions the sum runs over; rows = the D rows (c_out), c = the sliding operand's channels.  Among
@@ -399,55 +133,31 @@ WgPlan wg_plan(int n, int c, int rows, int h_out, int w_out) {
     if (cost < best) best = cost, p.tr = tr, p.tc = tc, p.n_rb = n_rb, p.n_cb = (w_out + tc - 1) / tc;
   }
   if (p.tr == 0) p.tr = 1, p.tc = std::min(w_out, 16), p.n_rb = h_out, p.n_cb = (w_out + p.tc - 1) / p.tc;
-  p.items = n * p.n_rb * p.n_cb;
-  const int want = std::min(p.items, kMaxSlabs);
-  p.per = (p.items + want - 1) / want;
-  p.n_slabs = (p.items + p.per - 1) / p.per;
-  p.lds = wg_lds_floats(p.cinp, p.mt, p.tr, p.tc) * sizeof(float);
-  p.ws = (size_t)p.n_slabs * rows * (c * 9 + 1) * sizeof(float);
+  slab_split(p, n, c, rows);
   return p;
 }
 
 template <int XSRC, int GSRC>
 int run_wgrad(const char* who, const In& in, const In& g, int pad, const WgPlan& p, float* dw, float* db, bool transposed,
               void* ws, size_t ws_bytes, hipStream_t st) {
-  int rc = check_workspace(who, ws, ws_bytes, p.ws);
-  if (rc) return rc;
-  PV_REQUIRE(p.lds <= kLdsFloats * sizeof(float), PV_ESIZE, "%s: tile of %zu bytes beyond the LDS budget", who, p.lds);
-  Wg q;
-  q.in = in, q.g = g, q.slabs = (float*)ws, q.pad = pad;
-  q.h_out = p.h_out, q.w_out = p.w_out, q.tr = p.tr, q.tc = p.tc, q.n_rb = p.n_rb, q.n_cb = p.n_cb;
-  q.items = p.items, q.per = p.per, q.cinp = p.cinp;
-  const dim3 grid((unsigned)p.n_slabs), block(kBlock);
   // column tiles ceil((9 c + 1) / 16) over 4 waves: 4 (c = 6), 10 (c = 16), 19 (c = 32)
-  const int ntw = ((in.c * 9 + 1 + 15) / 16 + 3) / 4;
-  if (p.mt == 2 && ntw == 5) ae_conv_wgrad<2, 5, XSRC, GSRC><<<grid, block, p.lds, st>>>(q);
-  else if (p.mt == 2 && ntw == 3) ae_conv_wgrad<2, 3, XSRC, GSRC><<<grid, block, p.lds, st>>>(q);
-  else if (p.mt == 1 && ntw == 5) ae_conv_wgrad<1, 5, XSRC, GSRC><<<grid, block, p.lds, st>>>(q);
-  else if (p.mt == 1 && ntw == 3) ae_conv_wgrad<1, 3, XSRC, GSRC><<<grid, block, p.lds, st>>>(q);
-  else if (p.mt == 1 && ntw == 1) ae_conv_wgrad<1, 1, XSRC, GSRC><<<grid, block, p.lds, st>>>(q);
-  else return fail(PV_ESIZE, "%s: no weight-gradient tile for %d rows x %d channels", who, g.c, in.c);
-  rc = check_launch(who);
-  if (rc) return rc;
-  launch_slab_sum(ws, dw, db, g.c, in.c * 9, p.n_slabs, st, transposed);
-  return check_launch(who);
-}
-
-In plain_in(const float* x, const float* gate, int c, int h, int w) {
-  In s = {};
-  s.x = x, s.gate = gate, s.c = c, s.h = h, s.w = w;
-  return s;
-}
-
-In pooled_in(const float* dyp, const uint8_t* codes, int c, int h, int w) {
-  In s = {};
-  s.x = dyp, s.codes = codes, s.c = c, s.h = h, s.w = w, s.ph = h / 3, s.pw = w / 3;
-  return s;
+  const int ntw = ((in.c_in * 9 + 1 + 15) / 16 + 3) / 4;
+#define PV_WG(MT, NTW) \
+  if (p.mt == MT && ntw == NTW) \
+  return launch_wgrad<MT, NTW, XSRC, GSRC>(who, in, g, pad, p, dw, db, transposed, ws, ws_bytes, st)
+  PV_WG(2, 5);
+  PV_WG(2, 3);
+  PV_WG(1, 5);
+  PV_WG(1, 3);
+  PV_WG(1, 1);
+#undef PV_WG
+  return fail(PV_ESIZE, "%s: no weight-gradient tile for %d rows x %d channels", who, g.c_in, in.c_in);
 }
 
 In counts_in(const void* hist, int hist_i16, const void* flow, int flow_i16, const float* horizon, int h, int w) {
   In s = {};
-  s.x = hist, s.x_i16 = hist_i16, s.flow = flow, s.flow_i16 = flow_i16, s.horizon = horizon, s.c = 6, s.h = h, s.w = w;
+  s.x = (const float*)hist, s.x_i16 = hist_i16, s.flow = flow, s.flow_i16 = flow_i16, s.horizon = horizon;
+  s.c_in = 6, s.h = h, s.w = w;
   return s;
 }
 
@@ -489,23 +199,6 @@ int check_counts(const char* who, int n, int h, int w, int c_out) {
   return PV_OK;
 }
 
-// forward-like Fwd of a plain conv [c_in] -> [c_out] over x (pad 0) ...
-Fwd conv_fwd_args(const float* w, const float* bias, float* y, int c_in, int c_out, int h_in, int w_in, int relu) {
-  Fwd a = {};
-  a.w = w, a.bias = bias, a.y = y, a.m_out = c_out, a.pad = 0, a.h_out = h_in - 2, a.w_out = w_in - 2;
-  a.w_sm = c_in * 9, a.w_sc = 9, a.flip = 0, a.relu = relu ? 1 : 0;
-  return a;
-}
-
-// ... and of the padded, mirrored form: out [m_out] over a (h_in + 2) x (w_in + 2) grid from a [c] x h_in x w_in source,
-// weights stored [c][m_out][3][3] (ConvTranspose2d forward) or [c][m_out] = [c_out][c_in] of a Conv2d (its data gradient)
-Fwd full_fwd_args(const float* w, const float* bias, float* y, int m_out, int h_src, int w_src, int relu) {
-  Fwd a = {};
-  a.w = w, a.bias = bias, a.y = y, a.m_out = m_out, a.pad = 2, a.h_out = h_src + 2, a.w_out = w_src + 2;
-  a.w_sm = 9, a.w_sc = m_out * 9, a.flip = 1, a.relu = relu ? 1 : 0;
-  return a;
-}
-
 // Routing by size.  Timed at B = 64, S = 128 (tools/time_nb16.py; profiles/nb16/NOTES.md keeps the rows of the two runs
 // made before each routing), this file's kernels lost to pv_conv3d_general_*_f32 on the same tensors as 1x3x3 convs with T
 // = 1 in: the data gradients of the 16 -> 32 / 32 -> 32 layers (0.39 / 0.57 against 0.26 / 0.45 ms), their weight gradients
@@ -521,8 +214,8 @@ constexpr long long kGeneralPositions = 32768;
 bool general_route(int n, int h_in, int w_in) { return (long long)n * (h_in - 2) * (w_in - 2) >= kGeneralPositions; }
 
 // The pooled layer on the general route: pv_conv3d_general_fwd_f32 writes the pre-activations z (bias included) to the
-// workspace, then one thread per pooled output takes its whole window in row-major order (first maximum wins, NaN
-// propagates), applies ReLU and writes the value and the code -- what ae_conv_fwd<.., POOL> does in its epilogue.
+// workspace, then one thread per pooled output puts its whole window through pool3_relu -- what conv2d_tile_fwd<.., POOL>
+// does in its epilogue.
 __global__ __launch_bounds__(kBlock) void pool3_relu_codes_f32(const float* __restrict__ z, float* __restrict__ y,
                                                               uint8_t* __restrict__ codes, int planes, int h, int w, int ph,
                                                               int pw) {
@@ -530,17 +223,8 @@ __global__ __launch_bounds__(kBlock) void pool3_relu_codes_f32(const float* __re
   for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < total; e += (long long)gridDim.x * kBlock) {
     const int pc = (int)(e % pw), pr = (int)((e / pw) % ph);
     const long long plane = e / ((long long)pw * ph);
-    const float* src = z + (plane * h + pr * 3) * w + pc * 3;
-    float best = -__builtin_inff();
-    int code = 0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const float v = src[(k / 3) * w + k % 3];
-      if (v > best || __builtin_isnan(v)) best = v, code = k;
-    }
-    const bool live = best > 0.0f || __builtin_isnan(best);
-    y[e] = live ? best : 0.0f;
-    codes[e] = live ? (uint8_t)code : kDead;
+    const float* win = z + (plane * h + pr * 3) * w + pc * 3;
+    y[e] = pool3_relu([&](int k) { return win[(k / 3) * w + k % 3]; }, codes[e]);
   }
 }
 
@@ -552,26 +236,13 @@ __global__ __launch_bounds__(kBlock) void pool3_expand_f32(const float* __restri
   for (long long e = (long long)blockIdx.x * kBlock + threadIdx.x; e < total; e += (long long)gridDim.x * kBlock) {
     const int c = (int)(e % w), r = (int)((e / w) % h);
     const long long plane = e / ((long long)w * h);
-    const int pr = r / 3, pc = c / 3;
-    float v = 0.0f;
-    if (pr < ph && pc < pw) {
-      const long long off = (plane * ph + pr) * pw + pc;
-      if ((int)codes[off] == (r - pr * 3) * 3 + (c - pc * 3)) v = dyp[off];
-    }
-    dz[e] = v;
+    dz[e] = pool3_expand(dyp + plane * ph * pw, codes + plane * ph * pw, ph, pw, r, c);
   }
 }
 
 // bytes of a [n][c][h_in - 2][w_in - 2] f32 scratch tensor, rounded up so that what follows it stays 256-byte aligned
 size_t pre_pool_bytes(int n, int c, int h_in, int w_in) {
   return (((size_t)n * c * (h_in - 2) * (w_in - 2) * sizeof(float)) + 255) & ~(size_t)255;
-}
-
-pv_conv3d_geom general_geom(int n, int c_in, int c_out, int h_in, int w_in) {
-  pv_conv3d_geom g = {};
-  g.batch = n, g.c_in = c_in, g.c_out = c_out, g.t_in = 1, g.h_in = h_in, g.w_in = w_in;
-  g.k_t = 1, g.k_h = 3, g.k_w = 3, g.stride_t = 1, g.stride_h = 1, g.stride_w = 1;
-  return g;
 }
 
 }  // namespace
@@ -600,7 +271,7 @@ int pv_conv2d_ae_fwd_f32(const float* x, const float* w, const float* bias, floa
   int rc = check_ae(who, n, c_in, c_out, h_in, w_in, KIND_CONV);
   if (rc) return rc;
   if (c_in == 32 && general_route(n, h_in, w_in)) {   // 32 -> 32 only: the 16 -> 32 forward is faster here (0.23 / 0.24 ms)
-    const pv_conv3d_geom g = general_geom(n, c_in, c_out, h_in, w_in);
+    const pv_conv3d_geom g = conv3d_geom_1x3x3(n, c_in, c_out, h_in, w_in);
     return pv_conv3d_general_fwd_f32(x, w, bias, y, &g, relu ? 1 : 0, stream);
   }
   Fwd a = conv_fwd_args(w, bias, y, c_in, c_out, h_in, w_in, relu);
@@ -629,7 +300,7 @@ int pv_conv2d_ae_pool_fwd_f32(const float* x, const float* w, const float* bias,
   if (general_route(n, h_in, w_in)) {
     rc = check_workspace(who, ws, ws_bytes, pre_pool_bytes(n, c_out, h_in, w_in));
     if (rc) return rc;
-    const pv_conv3d_geom g = general_geom(n, c_in, c_out, h_in, w_in);
+    const pv_conv3d_geom g = conv3d_geom_1x3x3(n, c_in, c_out, h_in, w_in);
     rc = pv_conv3d_general_fwd_f32(x, w, bias, (float*)ws, &g, 0, stream);
     if (rc) return rc;
     const int ph = (h_in - 2) / 3, pw = (w_in - 2) / 3;
@@ -650,7 +321,7 @@ int pv_conv2d_ae_bwd_data_f32(const float* dy, const float* dy_gate, const float
   int rc = check_ae(who, n, c_in, c_out, h_in, w_in, KIND_CONV);
   if (rc) return rc;
   if (general_route(n, h_in, w_in)) {
-    const pv_conv3d_geom g = general_geom(n, c_in, c_out, h_in, w_in);
+    const pv_conv3d_geom g = conv3d_geom_1x3x3(n, c_in, c_out, h_in, w_in);
     return pv_conv3d_general_bwd_data_f32(dy, dy_gate, w, dx, x_gate, &g, stream);
   }
   Fwd a = full_fwd_args(w, nullptr, dx, c_in, h_in - 2, w_in - 2, 0);
@@ -681,7 +352,7 @@ int pv_conv2d_ae_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_o
                      : check_ae(who, n, c_in, c_out, h_in, w_in, pooled ? KIND_POOL : KIND_CONV);
   if (rc) return rc;
   if (c_in != 6 && general_route(n, h_in, w_in)) {
-    const pv_conv3d_geom g = general_geom(n, c_in, c_out, h_in, w_in);
+    const pv_conv3d_geom g = conv3d_geom_1x3x3(n, c_in, c_out, h_in, w_in);
     rc = pv_conv3d_general_bwd_weight_workspace_bytes(&g, bytes);
     if (rc == PV_OK && pooled) *bytes += pre_pool_bytes(n, c_out, h_in, w_in);   // the expanded gradient comes first
     return rc;
@@ -713,7 +384,7 @@ int pv_conv2d_ae_bwd_weight_f32(const float* x, const float* dy, const float* dy
   int rc = check_ae(who, n, c_in, c_out, h_in, w_in, KIND_CONV);
   if (rc) return rc;
   if (general_route(n, h_in, w_in)) {
-    const pv_conv3d_geom g = general_geom(n, c_in, c_out, h_in, w_in);
+    const pv_conv3d_geom g = conv3d_geom_1x3x3(n, c_in, c_out, h_in, w_in);
     size_t need = 0;
     rc = pv_conv3d_general_bwd_weight_workspace_bytes(&g, &need);
     if (rc) return rc;
@@ -735,7 +406,7 @@ int pv_conv2d_ae_pool_bwd_weight_f32(const float* x, const float* dy_pooled, con
   int rc = check_ae(who, n, c_in, c_out, h_in, w_in, KIND_POOL);
   if (rc) return rc;
   if (general_route(n, h_in, w_in)) {
-    const pv_conv3d_geom g = general_geom(n, c_in, c_out, h_in, w_in);
+    const pv_conv3d_geom g = conv3d_geom_1x3x3(n, c_in, c_out, h_in, w_in);
     const size_t dz_bytes = pre_pool_bytes(n, c_out, h_in, w_in);
     size_t need = 0;
     rc = pv_conv3d_general_bwd_weight_workspace_bytes(&g, &need);

@@ -1,8 +1,10 @@
 // What the three exact-f32 Conv2d 3x3 files share: conv2d_f32.hip (experiments/002, 17 / 32 -> 32 / 4 channels),
 // conv2d_pool_f32.hip (experiments/001, 144 channels with fused MaxPool2d(3)) and conv2d_ae_f32.hip (notebooks/16_maxpool:
-// Conv2d / ConvTranspose2d up to 128 wide).  Their main loops stay in their own files; this header holds the ordered slab
-// sum of their weight gradients (also in the ConvTranspose2d layout), the five synthesised input channels of the two
-// experiments and the argument checks all repeat.
+// Conv2d / ConvTranspose2d up to 128 wide).  This header holds the ordered slab sum of their weight gradients (also in the
+// ConvTranspose2d layout), the MaxPool2d(3) + ReLU window rule and its backward, the descriptor of what a pass reads (In) with
+// its plain and pooled-gradient loads, the five synthesised input channels of the two experiments and the argument checks
+// they all repeat.  The 144-channel main loops (weights in LDS, K streamed in chunks) stay in their file; the two files whose
+// weights fit the VGPRs share theirs in conv2d_tile_f32.h.
 #pragma once
 #include "pv_common.h"
 
@@ -73,7 +75,86 @@ __device__ __forceinline__ float synth_channel(int k, int r, int c, int centre_r
   }
 }
 
+// MaxPool2d(3) fused with ReLU, one rule for every site.  pool3_relu: at(k) = the pre-activation at window position k =
+// 0..8 (row-major); the first maximum wins and NaN propagates (torch CPU); returns relu(max) and the code byte kept per
+// pooled output: the winning position, or kDead where the maximum is <= 0 (the window passes no gradient).
+constexpr uint8_t kDead = 255;
+
+template <class At>
+__device__ __forceinline__ float pool3_relu(At at, uint8_t& code) {
+  float best = -__builtin_inff();
+  int k_best = 0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const float v = at(k);
+    if (v > best || __builtin_isnan(v)) best = v, k_best = k;
+  }
+  const bool live = best > 0.0f || __builtin_isnan(best);
+  code = live ? (uint8_t)k_best : kDead;
+  return live ? best : 0.0f;
+}
+
+// ... and its backward: element (r, c) of the pre-pool gradient of one plane from the plane's pooled gradient dyp[ph][pw]
+// and codes: the pooled gradient where the window's code names (r % 3, c % 3), else (and beyond the whole windows) 0.
+__device__ __forceinline__ float pool3_expand(const float* dyp, const uint8_t* codes, int ph, int pw, int r, int c) {
+  const int pr = r / 3, pc = c / 3;
+  if (pr >= ph || pc >= pw) return 0.0f;
+  const int off = pr * pw + pc;
+  return (int)codes[off] == (r - pr * 3) * 3 + (c - pc * 3) ? dyp[off] : 0.0f;
+}
+
+// What a pass reads, by source kind.  Each file's first layer synthesises its input while staging (its own load_in /
+// stage_in arm); the other two kinds are the same everywhere.
+enum Src { SRC_PLAIN, SRC_POOLED, SRC_SAT, SRC_COUNTS };
+
+struct In {
+  // SRC_PLAIN: x[n][c_in][h][w], zeroed where gate <= 0 (gate may be null)
+  // SRC_POOLED: the pre-pool gradient of a pooled layer, [n][c_in][h][w] = pool3_expand of x = dyp[n][c_in][ph][pw]
+  // SRC_SAT: satellite frames behind x plus centre marker, geo x, geo y, pixel x, pixel y: experiments/001 reads sat[b]
+  //          [t_total][h][w] frames 0..n_frames-1, experiments/002 sat[n][h][w][12] with n / t_per_ex the coords' example
+  // SRC_COUNTS: x = history [n][4][h][w], flow [n][h][w] (int16 where *_i16, else f32 counts), horizon [n]: 6 channels
+  const float* x;
+  const float* gate;
+  const uint8_t* codes;    // SRC_POOLED: [n][c_in][ph][pw]
+  const float* xc;         // SRC_SAT: [b][w] geo x (varies along the last axis)
+  const float* yc;         // SRC_SAT: [b][h] geo y (varies along rows)
+  const void* flow;
+  const float* horizon;
+  int c_in, h, w, ph, pw, t_total, n_frames, t_per_ex, x_i16, flow_i16;
+};
+
+__device__ __forceinline__ float load_plain(const In& s, int n, int ch, int r, int c) {
+  const size_t off = (((size_t)n * s.c_in + ch) * s.h + r) * s.w + c;
+  const float v = s.x[off];
+  return (s.gate && !(s.gate[off] > 0.0f)) ? 0.0f : v;
+}
+
+__device__ __forceinline__ float load_pooled(const In& s, int n, int ch, int r, int c) {
+  const size_t plane = ((size_t)n * s.c_in + ch) * s.ph * s.pw;
+  return pool3_expand(s.x + plane, s.codes + plane, s.ph, s.pw, r, c);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
+
+inline In plain_in(const float* x, const float* gate, int c, int h, int w) {
+  In s = {};
+  s.x = x, s.gate = gate, s.c_in = c, s.h = h, s.w = w;
+  return s;
+}
+
+inline In pooled_in(const float* dyp, const uint8_t* codes, int c, int h, int w) {
+  In s = {};
+  s.x = dyp, s.codes = codes, s.c_in = c, s.h = h, s.w = w, s.ph = h / 3, s.pw = w / 3;
+  return s;
+}
+
+// the same NCHW conv as a 1x3x3 Conv3d with T = 1, for the launches that take pv_conv3d_general_*_f32
+inline pv_conv3d_geom conv3d_geom_1x3x3(int n, int c_in, int c_out, int h_in, int w_in) {
+  pv_conv3d_geom g = {};
+  g.batch = n, g.c_in = c_in, g.c_out = c_out, g.t_in = 1, g.h_in = h_in, g.w_in = w_in;
+  g.k_t = 1, g.k_h = 3, g.k_w = 3, g.stride_t = 1, g.stride_h = 1, g.stride_w = 1;
+  return g;
+}
 
 // positive extents, a 3x3 kernel that fits, every tensor of the conv within 32-bit indexing
 inline int check_conv_dims(const char* who, int n, int c_in, int c_out, int h_in, int w_in) {

@@ -17,37 +17,22 @@
 // epilogue may gate dx by the layer input (> 0).  The first layer reads frames 0..n_frames-1 of sat_data [B][T][H][W][1]
 // in place and computes the five extra channels while staging (forward and weight gradient).  wgrad splits the tiles
 // into fixed slabs, each block writing its partial sums to its own workspace slab, then adds the slabs in index order:
-// no atomics, identical bits run to run.  The slab sum, the synthesised channels and the shared argument checks are in
-// conv2d_f32_common.h.
+// no atomics, identical bits run to run.  The slab sum, the pooling rule (pool3_relu, pool3_expand), the input descriptor,
+// the synthesised channels and the shared argument checks are in conv2d_f32_common.h.
 #include "conv2d_f32_common.h"
 
 namespace pv {
 namespace {
 
 constexpr int kM = 144;       // output channels of every layer
-constexpr uint8_t kDead = 255;
 
 // forward / dgrad tiles: MT 16-channel tiles of the output channels per block, NTW 16-position tiles per wave
 constexpr int kFwdMT = 3, kFwdNTW = 2, kFwdCC = 12, kFwdPos = 4 * kFwdNTW * 16;   // 128 positions per block
 // wgrad: CC input channels per chunk -> 126 (ci, tap) columns + a ones column + a zero column = 8 tiles, 2 per wave
 constexpr int kWgCC = 14, kWgNTW = 2, kWgMT = kM / 16, kWgPos = 84;
 
-enum Src { SRC_PLAIN = 0, SRC_SAT = 1, SRC_POOLED = 2 };
-
-struct In {
-  // SRC_PLAIN: x[n][c_in][h][w], zeroed where gate <= 0 (gate may be null)
-  // SRC_SAT: sat[b][t_total][h][w] frames 0..n_frames-1, then centre marker, geo x, geo y, pixel x, pixel y
-  // SRC_POOLED: the pre-pool gradient of a pooled layer, [n][c_in][h][w] with element (r, c) = dyp[r / 3][c / 3] where the
-  //             window's code is (r % 3) * 3 + c % 3 (and r < 3 ph, c < 3 pw), else 0
-  const float* x;
-  const float* gate;
-  const uint8_t* codes;    // SRC_POOLED: [n][c_in][ph][pw]
-  const float* xc;         // SRC_SAT: [b][w] geo x (varies along the last axis)
-  const float* yc;         // SRC_SAT: [b][h] geo y (varies along rows)
-  int c_in, h, w, ph, pw, t_total, n_frames;
-};
-
-// input channel ch (0 <= ch < c_in) of image n at (r, c), which the caller has checked lies inside [0, h) x [0, w)
+// input channel ch (0 <= ch < c_in) of image n at (r, c), which the caller has checked lies inside [0, h) x [0, w).  SRC_SAT
+// here: sat[b][t_total][h][w] frames 0..n_frames-1 stacked as channels, then the five synthesised channels.
 template <int SRC>
 __device__ __forceinline__ float load_in(const In& s, int n, int ch, int r, int c) {
   if (SRC == SRC_SAT) {
@@ -55,16 +40,8 @@ __device__ __forceinline__ float load_in(const In& s, int n, int ch, int r, int 
     // the channels of experiments/001...py:278-301.  The reference takes the centre and the pixel ramps from the row count
     // (`width`, :266-267) on both axes, so the centre is (h / 2, h / 2).
     return synth_channel(ch - s.n_frames, r, c, s.h / 2, s.h / 2, s.xc + (size_t)n * s.w, s.yc + (size_t)n * s.h);
-  } else if (SRC == SRC_POOLED) {
-    const int pr = r / 3, pc = c / 3;
-    if (pr >= s.ph || pc >= s.pw) return 0.0f;
-    const size_t off = (((size_t)n * s.c_in + ch) * s.ph + pr) * s.pw + pc;
-    return (int)s.codes[off] == (r - pr * 3) * 3 + (c - pc * 3) ? s.x[off] : 0.0f;
-  } else {
-    const size_t off = (((size_t)n * s.c_in + ch) * s.h + r) * s.w + c;
-    const float v = s.x[off];
-    return (s.gate && !(s.gate[off] > 0.0f)) ? 0.0f : v;
   }
+  return SRC == SRC_POOLED ? load_pooled(s, n, ch, r, c) : load_plain(s, n, ch, r, c);
 }
 
 // Stage channels [c0, c0 + cc) x rows [r0, r0 + rows) x columns [col0, col0 + cols) of image n as lds[c][r][col];
@@ -203,17 +180,9 @@ __global__ __launch_bounds__(kBlock) void conv144_fwd(Fwd a) {
     const int m = m0 + ml;
     if (m >= a.m_out) continue;
     const float bm = a.bias ? a.bias[m] : 0.0f;
-    float best = -__builtin_inff();
-    int code = 0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const float v = pre[ml * kFwdPos + (k / 3) * cols + wc * 3 + k % 3] + bm;
-      if (v > best || __builtin_isnan(v)) best = v, code = k;   // first maximum wins; NaN propagates (torch CPU)
-    }
-    const bool live = best > 0.0f || __builtin_isnan(best);
+    const float* win = pre + ml * kFwdPos + wc * 3;
     const size_t off = (((size_t)n * a.m_out + m) * ph + rb) * pw + cb * (a.tc / 3) + wc;
-    a.y[off] = live ? best : 0.0f;
-    a.codes[off] = live ? (uint8_t)code : kDead;
+    a.y[off] = pool3_relu([&](int k) { return win[(k / 3) * cols + k % 3] + bm; }, a.codes[off]);
   }
 }
 
@@ -400,18 +369,6 @@ int check_sat(const char* who, int b, int t_total, int n_frames, int h, int w, i
 In sat_in(const float* sat, const float* xc, const float* yc, int t_total, int n_frames, int h, int w) {
   In s = {};
   s.x = sat, s.xc = xc, s.yc = yc, s.c_in = n_frames + 5, s.h = h, s.w = w, s.t_total = t_total, s.n_frames = n_frames;
-  return s;
-}
-
-In plain_in(const float* x, const float* gate, int c, int h, int w) {
-  In s = {};
-  s.x = x, s.gate = gate, s.c_in = c, s.h = h, s.w = w;
-  return s;
-}
-
-In pooled_in(const float* dyp, const uint8_t* codes, int c, int h, int w) {
-  In s = {};
-  s.x = dyp, s.codes = codes, s.c_in = c, s.h = h, s.w = w, s.ph = h / 3, s.pw = w / 3;
   return s;
 }
 
