@@ -1,8 +1,8 @@
-// fp32 fully-connected head, forecast losses and Adam.
+// fp32 fully-connected head, forecast losses and Adam (the update itself and its step scalars: adam.h, their one statement).
 // replaces: F.linear / torch.cat-fed FC stack (predict_pv_yield/models/conv3d/model.py:92-103,125-152),
 //           F.mse_loss, (y_hat - y).abs().mean(), WeightedLosses (base_model.py:98-103),
 //           torch.optim.Adam(lr=5e-4) (base_model.py:255-257).
-#include "pv_common.h"
+#include "adam.h"
 
 namespace pv {
 
@@ -416,13 +416,12 @@ __global__ __launch_bounds__(256) void forecast_losses_f32(const float* __restri
   }
 }
 
-// ---- Adam: torch._single_tensor_adam order of operations, f32 ------------------------------------
+// ---- Adam: torch._single_tensor_adam order of operations, f32 (adam_update, adam.h) ---------------
 template <typename GT>  // gradient type: float, or uint16_t holding bf16 (data-parallel wire format)
 __global__ __launch_bounds__(256) void adam_step_f32(float* __restrict__ p, const GT* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ v,
-                                                      uint16_t* __restrict__ shadow, size_t n, float one_minus_b1,
-                                                      float beta2, float one_minus_b2, float bc2_sqrt, float eps,
-                                                      float neg_step_size, float grad_scale) {
+                                                      uint16_t* __restrict__ shadow, size_t n, AdamScalars ad,
+                                                      float grad_scale) {
   size_t stride = (size_t)gridDim.x * blockDim.x * 4;
   for (size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
     if (i + 4 <= n) {
@@ -440,11 +439,8 @@ __global__ __launch_bounds__(256) void adam_step_f32(float* __restrict__ p, cons
       uint16_t sh[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float gr = gv4[j] * grad_scale;
-        float mm = mv4[j] + one_minus_b1 * (gr - mv4[j]);        // exp_avg.lerp_(grad, 1 - beta1)
-        float vv = vv4[j] * beta2 + (one_minus_b2 * gr) * gr;     // mul_(beta2).addcmul_(g, g, 1 - beta2)
-        float denom = sqrtf(vv) / bc2_sqrt + eps;
-        float pp = pv4[j] + neg_step_size * (mm / denom);        // addcdiv_(exp_avg, denom, -step_size)
+        float mm = mv4[j], vv = vv4[j], pp = pv4[j];
+        adam_update(pp, mm, vv, gv4[j] * grad_scale, ad);
         mv4[j] = mm; vv4[j] = vv; pv4[j] = pp;
         sh[j] = f32_to_bf16_bits(pp);
       }
@@ -459,11 +455,8 @@ __global__ __launch_bounds__(256) void adam_step_f32(float* __restrict__ p, cons
       for (size_t q = i; q < n; ++q) {
         float gq;
         if constexpr (sizeof(GT) == 4) gq = (float)g[q]; else gq = bf16_bits_to_f32((uint16_t)g[q]);
-        float gr = gq * grad_scale;
-        float mm = m[q] + one_minus_b1 * (gr - m[q]);
-        float vv = v[q] * beta2 + (one_minus_b2 * gr) * gr;
-        float denom = sqrtf(vv) / bc2_sqrt + eps;
-        float pp = p[q] + neg_step_size * (mm / denom);
+        float mm = m[q], vv = v[q], pp = p[q];
+        adam_update(pp, mm, vv, gq * grad_scale, ad);
         m[q] = mm; v[q] = vv; p[q] = pp;
         if (shadow) shadow[q] = f32_to_bf16_bits(pp);
       }
@@ -532,22 +525,12 @@ __global__ void adam_scalars_advance_kernel(float* __restrict__ scalars, int* __
                                             double beta2, double eps) {
   const int s = *step + 1;
   *step = s;
-  const double bc1 = 1.0 - pow(beta1, (double)s), bc2 = 1.0 - pow(beta2, (double)s);
-  scalars[0] = (float)(1.0 - beta1);
-  scalars[1] = (float)beta2;
-  scalars[2] = (float)(1.0 - beta2);
-  scalars[3] = (float)sqrt(bc2);
-  scalars[4] = (float)eps;
-  scalars[5] = (float)(-(lr / bc1));
+  adam_scalars_store(scalars, adam_scalars(lr, beta1, beta2, eps, s));
 }
 
-__global__ __launch_bounds__(256) void adam_step_multi_f32(AdamTable tab, float one_minus_b1, float beta2, float one_minus_b2,
-                                                            float bc2_sqrt, float eps, float neg_step_size, float grad_scale,
+__global__ __launch_bounds__(256) void adam_step_multi_f32(AdamTable tab, AdamScalars ad, float grad_scale,
                                                             const float* __restrict__ ad_dev) {
-  if (ad_dev) {   // scalars of this step from device memory (pv_adam_scalars_advance): the graph-replayable form
-    one_minus_b1 = ad_dev[0], beta2 = ad_dev[1], one_minus_b2 = ad_dev[2], bc2_sqrt = ad_dev[3], eps = ad_dev[4];
-    neg_step_size = ad_dev[5];
-  }
+  if (ad_dev) ad = adam_scalars_load(ad_dev);   // this step's scalars from device memory (pv_adam_scalars_advance): the graph-replayable form
   int ti = 0;
   while (ti + 1 < tab.n_tensors && (int)blockIdx.x >= tab.blk0[ti + 1]) ++ti;
   const pv_adam_tensor T = tab.t[ti];
@@ -569,12 +552,9 @@ __global__ __launch_bounds__(256) void adam_step_multi_f32(AdamTable tab, float 
   }
   uint16_t sh[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {  // same operation order as adam_step_f32
-    const float gr = gv[j] * grad_scale;
-    const float mm = mv[j] + one_minus_b1 * (gr - mv[j]);
-    const float v2 = vv[j] * beta2 + (one_minus_b2 * gr) * gr;
-    const float denom = sqrtf(v2) / bc2_sqrt + eps;
-    const float pp = pv[j] + neg_step_size * (mm / denom);
+  for (int j = 0; j < 4; ++j) {
+    float mm = mv[j], v2 = vv[j], pp = pv[j];
+    adam_update(pp, mm, v2, gv[j] * grad_scale, ad);
     mv[j] = mm, vv[j] = v2, pv[j] = pp;
     sh[j] = f32_to_bf16_bits(pp);
   }
@@ -769,14 +749,8 @@ int pv_adam_step_f32(float* param, const float* grad, float* exp_avg, float* exp
                  ((uintptr_t)exp_avg_sq % 16 == 0) && ((uintptr_t)bf16_shadow % 8 == 0),
              PV_EINVAL, "pv_adam_step_f32: buffers must be 16-byte aligned");
   if (n == 0) return PV_OK;
-  // python-float (double) scalars exactly as torch computes them, then narrowed to f32 at the kernel boundary
-  double bc1 = 1.0 - pow(beta1, (double)step);
-  double bc2 = 1.0 - pow(beta2, (double)step);
-  double step_size = lr / bc1;
-  double bc2_sqrt = sqrt(bc2);
   hipLaunchKernelGGL(adam_step_f32<float>, dim3(stream_grid((n + 3) / 4, 256)), dim3(256), 0, as_stream(stream), param, grad,
-                     exp_avg, exp_avg_sq, bf16_shadow, n, (float)(1.0 - beta1), (float)beta2,
-                     (float)(1.0 - beta2), (float)bc2_sqrt, (float)eps, (float)(-step_size), grad_scale);
+                     exp_avg, exp_avg_sq, bf16_shadow, n, adam_scalars(lr, beta1, beta2, eps, step), grad_scale);
   return check_launch("pv_adam_step_f32");
 }
 
@@ -811,10 +785,8 @@ int pv_adam_step_multi_f32(const pv_adam_tensor* tensors, int32_t n_tensors, dou
   int rc = adam_multi_table(tensors, n_tensors, &tab, &blocks, "pv_adam_step_multi_f32");
   if (rc) return rc;
   if (tab.n_tensors == 0) return PV_OK;
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  hipLaunchKernelGGL(adam_step_multi_f32, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), tab, (float)(1.0 - beta1),
-                     (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps, (float)(-(lr / bc1)), grad_scale,
-                     (const float*)nullptr);
+  hipLaunchKernelGGL(adam_step_multi_f32, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), tab,
+                     adam_scalars(lr, beta1, beta2, eps, step), grad_scale, (const float*)nullptr);
   return check_launch("pv_adam_step_multi_f32");
 }
 
@@ -834,8 +806,8 @@ int pv_adam_step_multi_dev_f32(const pv_adam_tensor* tensors, int32_t n_tensors,
   int rc = adam_multi_table(tensors, n_tensors, &tab, &blocks, "pv_adam_step_multi_dev_f32");
   if (rc) return rc;
   if (tab.n_tensors == 0) return PV_OK;
-  hipLaunchKernelGGL(adam_step_multi_f32, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), tab, 0.f, 0.f, 0.f, 1.f, 0.f,
-                     0.f, grad_scale, scalars_dev);
+  hipLaunchKernelGGL(adam_step_multi_f32, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), tab, AdamScalars{}, grad_scale,
+                     scalars_dev);
   return check_launch("pv_adam_step_multi_dev_f32");
 }
 
@@ -848,11 +820,8 @@ int pv_adam_step_bf16grad(float* param, const uint16_t* grad_bf16, float* exp_av
                  ((uintptr_t)exp_avg_sq % 16 == 0) && ((uintptr_t)bf16_shadow % 8 == 0),
              PV_EINVAL, "pv_adam_step_bf16grad: buffers must be 16-byte aligned");
   if (n == 0) return PV_OK;
-  double bc1 = 1.0 - pow(beta1, (double)step);
-  double bc2 = 1.0 - pow(beta2, (double)step);
   hipLaunchKernelGGL(adam_step_f32<uint16_t>, dim3(stream_grid((n + 3) / 4, 256)), dim3(256), 0, as_stream(stream), param,
-                     grad_bf16, exp_avg, exp_avg_sq, bf16_shadow, n, (float)(1.0 - beta1), (float)beta2,
-                     (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps, (float)(-(lr / bc1)), grad_scale);
+                     grad_bf16, exp_avg, exp_avg_sq, bf16_shadow, n, adam_scalars(lr, beta1, beta2, eps, step), grad_scale);
   return check_launch("pv_adam_step_bf16grad");
 }
 

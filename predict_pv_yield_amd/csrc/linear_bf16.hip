@@ -6,7 +6,7 @@
 //   fwd : y[M,N]  = x[M,K] . w[N,K]^T   split-K over workgroups, f32 slabs + fixed-order reduce
 //   bwd : dx[M,K] = g[M,N] . w[N,K]     (bf16 out);  dw[N,K] = g^T . x (f32 out);  db[N] = colsum(g)
 //         with g = dy ⊙ (y > 0)
-#include "pv_common.h"
+#include "adam.h"
 #include <string.h>
 
 namespace pv {
@@ -221,10 +221,7 @@ __global__ __launch_bounds__(256) void linear_bwd_dx_bf16_kernel(const uint16_t*
 
 // dw[n0..n0+7][k..k+7] = sum_m g[m][n] * x[m][k..k+7]
 // FUSE_ADAM: the gradient tile never leaves registers -- the Adam update of the same 8 x 8 weights (and of the bf16
-// shadow) is applied in place: one pass over p, m, v instead of writing 0.5 GB of dw and reading it back.
-struct AdamScalars {
-  float one_minus_b1, beta2, one_minus_b2, bc2_sqrt, eps, neg_step_size;
-};
+// shadow) is applied in place (adam_update, adam.h): one pass over p, m, v instead of writing 0.5 GB of dw and reading it back.
 
 // XT: uint16_t = x in bf16 (the bf16 model); float = x in f32 (precision="fp32": exact f32 products, f32 accumulation in batch
 // order -- the fused form of that model's fc1 weight gradient + Adam, pv_linear_wgrad_adam_f32)
@@ -309,7 +306,7 @@ __global__ __launch_bounds__(256) void linear_bwd_dw_bf16_kernel(const XT* __res
       }
     }
   } else {
-    // dw here is the PARAMETER (updated in place); same operation order as adam_step_f32 / torch.  The correctly rounded
+    // dw here is the PARAMETER (updated in place); the same adam_update as adam_step_f32.  The correctly rounded
     // sqrt and the two divisions expand to ~40 VALU instructions per element (a few thousand cycles per row of the
     // tile), so the NEXT row's p / m / v are fetched before the current row's arithmetic: without that a wave has its
     // 6 loads in flight only between rows and the HBM pipe drains while it computes.
@@ -339,12 +336,8 @@ __global__ __launch_bounds__(256) void linear_bwd_dw_bf16_kernel(const XT* __res
         uint32_t sh[4];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const float gr = acc[i][j];
-          const float mm = mv[j] + ad.one_minus_b1 * (gr - mv[j]);
-          const float v2 = vv[j] * ad.beta2 + (ad.one_minus_b2 * gr) * gr;
-          const float denom = sqrtf(v2) / ad.bc2_sqrt + ad.eps;
-          const float pp = pv[j] + ad.neg_step_size * (mm / denom);
-          mv[j] = mm; vv[j] = v2; pv[j] = pp;
+          adam_update(pv[j], mv[j], vv[j], acc[i][j], ad);
+          const float pp = pv[j];
           if (j & 1) sh[j >> 1] |= (uint32_t)f32_to_bf16_bits(pp) << 16; else sh[j >> 1] = f32_to_bf16_bits(pp);
         }
         *reinterpret_cast<f32x4*>(dw + off) = *reinterpret_cast<const f32x4*>(pv);
@@ -392,7 +385,7 @@ __global__ __launch_bounds__(256, 3) void linear_bwd_dw_dx_adam_kernel(
     int mv_tiled) {
   // ad_dev (may be NULL): the six Adam scalars in device memory (pv_adam_scalars_advance) -- the form a captured HIP graph
   // replays, where the bias corrections must change from replay to replay and kernel arguments cannot
-  if (ad_dev) ad = AdamScalars{ad_dev[0], ad_dev[1], ad_dev[2], ad_dev[3], ad_dev[4], ad_dev[5]};
+  if (ad_dev) ad = adam_scalars_load(ad_dev);
   __shared__ __attribute__((aligned(16))) float gs[32 * 128];               // g = dy (.) relu'  [b][n], zero padded
   __shared__ __attribute__((aligned(16))) uint16_t wt[FD_KT * FD_WLD];      // pre-update weights, bf16, [k][n]
   // the x tile [b][k] lives in the first 8.5 KB of wt until the gradient tile is formed (wt is written after that), and the
@@ -505,12 +498,8 @@ __global__ __launch_bounds__(256, 3) void linear_bwd_dw_dx_adam_kernel(
       uint32_t sh[4];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float gr = acc2[i % GR][j >> 1][j & 1];
-        const float mm = mv[j] + ad.one_minus_b1 * (gr - mv[j]);
-        const float v2 = vv[j] * ad.beta2 + (ad.one_minus_b2 * gr) * gr;
-        const float denom = sqrtf(v2) / ad.bc2_sqrt + ad.eps;
-        const float pp = pv[j] + ad.neg_step_size * (mm / denom);
-        mv[j] = mm; vv[j] = v2; pv[j] = pp;
+        adam_update(pv[j], mv[j], vv[j], acc2[i % GR][j >> 1][j & 1], ad);
+        const float pp = pv[j];
         if (j & 1) sh[j >> 1] |= (uint32_t)f32_to_bf16_bits(pp) << 16; else sh[j >> 1] = f32_to_bf16_bits(pp);
       }
       *reinterpret_cast<f32x4*>(w + off) = *reinterpret_cast<const f32x4*>(pv);
@@ -798,11 +787,8 @@ __global__ __launch_bounds__(256, 2) void linear_bwd_dw_dx_adam_tall_kernel(
       uint32_t sh[4];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float gr = __fmul_rn(acc2[i][j >> 1][j & 1], grad_scale);
-        const float mm = mv[j] + ad.one_minus_b1 * (gr - mv[j]);
-        const float v2 = vv[j] * ad.beta2 + (ad.one_minus_b2 * gr) * gr;
-        const float denom = sqrtf(v2) / ad.bc2_sqrt + ad.eps;
-        const float pp = pv[j] + ad.neg_step_size * (mm / denom);
+        float mm = mv[j], v2 = vv[j], pp = pv[j];
+        adam_update(pp, mm, v2, __fmul_rn(acc2[i][j >> 1][j & 1], grad_scale), ad);
         mv[j] = mm; vv[j] = v2; pv[j] = pp;
         if (j & 1) sh[j >> 1] |= (uint32_t)f32_to_bf16_bits(pp) << 16; else sh[j >> 1] = f32_to_bf16_bits(pp);
       }
@@ -1456,9 +1442,7 @@ int pv_linear_wgrad_adam_bf16(const uint16_t* x, const float* dy, const float* y
   PV_REQUIRE(step >= 1, PV_EINVAL, "pv_linear_wgrad_adam_bf16: step must be >= 1");
   size_t lds = (size_t)m * BT * sizeof(float);
   PV_REQUIRE(lds <= 64 * 1024, PV_ESIZE, "pv_linear_wgrad_adam_bf16: m=%d too large", m);
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  AdamScalars ad{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps,
-                 (float)(-(lr / bc1))};
+  const AdamScalars ad = adam_scalars(lr, beta1, beta2, eps, step);
   unsigned kb = (unsigned)((k / 8 + 255) / 256);
   hipLaunchKernelGGL(linear_bwd_dw_bf16_kernel<1>, dim3(xcd_grid(kb, (unsigned)((n + BT - 1) / BT))), dim3(256), lds,
                      as_stream(stream), x, dy, y_relu_mask, param, m, n, (long long)k, exp_avg, exp_avg_sq, bf16_shadow, ad);
@@ -1475,9 +1459,7 @@ int pv_linear_wgrad_adam_f32(const float* x, const float* dy, const float* y_rel
   PV_REQUIRE(step >= 1, PV_EINVAL, "pv_linear_wgrad_adam_f32: step must be >= 1");
   size_t lds = (size_t)m * BT * sizeof(float);
   PV_REQUIRE(lds <= 64 * 1024, PV_ESIZE, "pv_linear_wgrad_adam_f32: m=%d too large", m);
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  AdamScalars ad{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps,
-                 (float)(-(lr / bc1))};
+  const AdamScalars ad = adam_scalars(lr, beta1, beta2, eps, step);
   unsigned kb = (unsigned)((k / 8 + 255) / 256);
   hipLaunchKernelGGL((linear_bwd_dw_bf16_kernel<1, float>), dim3(xcd_grid(kb, (unsigned)((n + BT - 1) / BT))), dim3(256), lds,
                      as_stream(stream), x, dy, y_relu_mask, param, m, n, (long long)k, exp_avg, exp_avg_sq, (uint16_t*)nullptr, ad);
@@ -1510,9 +1492,7 @@ int pv_linear_wgrad_dx_adam_bf16(const uint16_t* x, const float* dy, const float
   PV_REQUIRE(k > 0 && k % 8 == 0, PV_ESIZE, "pv_linear_wgrad_dx_adam_bf16: k must be a multiple of 8");
   PV_REQUIRE(step >= 1, PV_EINVAL, "pv_linear_wgrad_dx_adam_bf16: step must be >= 1");
   PV_REQUIRE(!moments_tiled || k % FD_KT == 0, PV_ESIZE, "pv_linear_wgrad_dx_adam_bf16: tiled moments need k %% %d == 0", FD_KT);
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  AdamScalars ad{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps,
-                 (float)(-(lr / bc1))};
+  const AdamScalars ad = adam_scalars(lr, beta1, beta2, eps, step);
   const unsigned grid = (unsigned)((k + FD_KT - 1) / FD_KT);
   PV_LAUNCH_FC1_ONE_PASS(grid, as_stream(stream), x, dy, y_relu_mask, param, m, n,
                      (long long)k, exp_avg, exp_avg_sq, bf16_shadow, dx, db, ad, gate_dx_by_x, (const float*)nullptr,
@@ -1543,9 +1523,7 @@ int pv_linear_wgrad_dx_adam_tall_bf16(const uint16_t* x, const float* dy, float*
   const int nblk = (m + 31) / 32;
   PV_REQUIRE(workspace_bytes >= (size_t)nblk * (TL_GA + TL_GD) * 16, PV_ESIZE,
              "pv_linear_wgrad_dx_adam_tall_bf16: workspace too small (pv_linear_wgrad_dx_adam_tall_bf16_workspace_bytes)");
-  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-  AdamScalars ad{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)sqrt(bc2), (float)eps,
-                 (float)(-(lr / bc1))};
+  const AdamScalars ad = adam_scalars(lr, beta1, beta2, eps, step);
   u32x4* ga = static_cast<u32x4*>(workspace);
   u32x4* gd = ga + (size_t)nblk * TL_GA;
   hipLaunchKernelGGL(tall_split_g_kernel, dim3((unsigned)((nblk * (TL_GA + TL_GD) + 255) / 256)), dim3(256), 0, as_stream(stream), dy,

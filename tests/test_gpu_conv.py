@@ -968,6 +968,63 @@ def test_adam_multi_tensor_equals_single(device):
         assert sa is None or torch.equal(sa, sb)
 
 
+def _adam_scalars_f32(s, lr=3e-3, b1=0.9, b2=0.999, eps=1e-8):
+    """The six per-step scalars in the order of the device array: python doubles narrowed to float32."""
+    import math
+    return torch.tensor([1 - b1, b2, 1 - b2, math.sqrt(1 - b2 ** s), eps, -(lr / (1 - b1 ** s))], dtype=torch.float32)
+
+
+def test_adam_device_scalar_forms_equal_the_host_scalar_forms(device):
+    """The forms a captured graph replays read the step's scalars from device memory: pv_adam_step_multi_dev_f32 and
+    pv_linear_wgrad_dx_adam_dev_bf16 fed with host-built scalars equal their by-value twins bit for bit, and
+    pv_adam_scalars_advance writes those scalars (the two that go through pow to one float32 ulp: device and host pow are
+    each good to a few double ulps, so after narrowing they can differ only across one f32 rounding boundary)."""
+    K, _ = _mods()
+    steps = (1, 2, 7)
+    # multi-tensor form: ragged sizes, a shadow on every other tensor
+    sizes = [1, 3, 1027, 4101]
+    g = torch.Generator().manual_seed(21)
+    grads = [torch.randn(n, generator=g).to(device) for n in sizes]
+    def fresh():
+        gg = torch.Generator().manual_seed(22)
+        return [(torch.randn(n, generator=gg).to(device), gr, torch.randn(n, generator=gg).to(device),
+                 torch.rand(n, generator=gg).to(device) * 1e-3,
+                 torch.zeros(n, dtype=torch.bfloat16, device=device) if i % 2 == 0 else None)
+                for i, (n, gr) in enumerate(zip(sizes, grads))]
+    a, b = fresh(), fresh()
+    for s in steps:
+        K.adam_step_multi_dev(a, _adam_scalars_f32(s).to(device), grad_scale=0.5)
+        K.adam_step_multi(b, s, lr=3e-3, grad_scale=0.5)
+        for (pa, _, ma, va, sa), (pb, _, mb, vb, sb) in zip(a, b):
+            assert torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb), s
+            assert sa is None or torch.equal(sa, sb), s
+    # fc1 one-pass form: a ragged last 128-column tile, short m, short n
+    for m, n, k in [(7, 128, 1032), (32, 16, 4096)]:
+        g = torch.Generator().manual_seed(23 + m)
+        x = torch.randn(m, k, generator=g).to(torch.bfloat16).to(device)
+        dy = torch.randn(m, n, generator=g).to(device)
+        y = torch.relu(torch.randn(m, n, generator=g)).to(device)
+        p0 = (torch.randn(n, k, generator=g) * 0.01).to(device)
+        pa, ma, va, sa = p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0), p0.to(torch.bfloat16)
+        pb, mb, vb, sb = p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0), p0.to(torch.bfloat16)
+        for s in steps:
+            dxa = K.linear_wgrad_dx_adam_dev_bf16(x, dy, y, pa, ma, va, sa, _adam_scalars_f32(s).to(device))
+            dxb = K.linear_wgrad_dx_adam_bf16(x, dy, y, pb, mb, vb, sb, s, lr=3e-3)
+            assert torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb) and torch.equal(sa, sb), (m, n, k, s)
+            assert torch.equal(dxa, dxb), (m, n, k, s)
+    # the advance kernel: three calls from step 0
+    scal = torch.zeros(6, device=device)
+    step = torch.zeros(1, dtype=torch.int32, device=device)
+    for _ in range(3):
+        K.adam_scalars_advance(scal, step, lr=3e-3)
+    assert int(step.item()) == 3
+    got, want = scal.cpu(), _adam_scalars_f32(3)
+    print("adam_scalars_advance:", got.tolist(), "host:", want.tolist())
+    assert torch.equal(got[[0, 1, 2, 4]], want[[0, 1, 2, 4]])
+    ulps = (got[[3, 5]].view(torch.int32) - want[[3, 5]].view(torch.int32)).abs()      # same sign: adjacent floats differ by 1
+    assert int(ulps.max()) <= 1, ulps.tolist()
+
+
 def test_pack_weights_multi_equals_single_and_cache_invalidation(device):
     K, Fn = _mods()
     g = torch.Generator().manual_seed(14)
