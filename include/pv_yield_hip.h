@@ -392,6 +392,68 @@ int pv_convt2d_ae_bwd_weight_f32(const float* x, const float* dy, const float* d
 int pv_mse_crop_norm_f32(const float* y_hat, const void* target, int32_t target_is_i16, int32_t n, int32_t out_h,
                          int32_t out_w, int32_t target_h, int32_t target_w, float* loss, float* dy_hat, void* ws,
                          size_t ws_bytes, void* stream);
+/* The same loss over a window of the target that starts at (row0, col0): y = normalise_images_in_model(target)[..., row0 :
+ * row0 + out_h, col0 : col0 + out_w].  replaces: y = normalise_images_in_model(y, self.device); y = y[..., :-1, :-1];
+ * F.mse_loss(y_hat, y), 15_int16.ipynb:13784-13788 (row0 = col0 = 0, target one larger than the output) and, with (8, 8),
+ * what pv_mse_crop_norm_f32 computes (same kernels, same bits).  A window that leaves the target returns PV_ESIZE. */
+int pv_mse_window_norm_f32(const float* y_hat, const void* target, int32_t target_is_i16, int32_t n, int32_t out_h,
+                           int32_t out_w, int32_t target_h, int32_t target_w, int32_t row0, int32_t col0, float* loss,
+                           float* dy_hat, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- notebooks/14_back_to_2d_conv_AE.ipynb, 15_int16.ipynb: Conv2d / ConvTranspose2d 3x3, stride 2, no padding ---- */
+/* (line numbers: the raw 15_int16.ipynb file; the LitAutoEncoder cell starts at 13737, normalise_images_in_model at 13721;
+ * notebook 14's cell is the same stack.)  NCHW f32, exact f32 on the matrix cores; counts, gates (NULL = none) and
+ * weight-gradient slabs follow the conventions of the pv_conv2d_ae_* entry points above.  A Conv2d maps h -> (h - 3) / 2 + 1,
+ * a ConvTranspose2d h -> 2 h + 1; planes are at most 128 wide on the wide side (Conv2d input, ConvTranspose2d output).
+ * (h_in, w_in) is always the extent of the layer's input x.  Unsupported shapes return PV_ESIZE before any launch. */
+/* replaces: torch.cat((x[HISTORICAL_SAT_IMAGES], x[OPTICAL_FLOW_PREDICTIONS].unsqueeze(1)), dim=1);
+ * normalise_images_in_model(images); torch.cat((images, forecast_horizon), dim=1); nn.Conv2d(6, 16, 3, stride=2); nn.ReLU(),
+ * 15_int16.ipynb:13748-13749, 13766-13779.  history [n][4][h][w], flow_pred [n][h][w], horizon [n]; c_out = 16; 31 <= h, w
+ * and w <= 128. */
+int pv_conv2d_s2_counts_fwd_f32(const void* history, int32_t history_is_i16, const void* flow_pred, int32_t flow_is_i16,
+                                const float* horizon, const float* w, const float* bias, float* y, int32_t n, int32_t h,
+                                int32_t w_img, int32_t c_out, void* stream);
+/* replaces: the weight and bias gradients of conv.0 (autograd of 15_int16.ipynb:13748), re-reading and re-normalising the
+ * counts as the forward does; dy is the pre-activation gradient.  dw [16][6][3][3]. */
+int pv_conv2d_s2_counts_bwd_weight_f32(const void* history, int32_t history_is_i16, const void* flow_pred,
+                                       int32_t flow_is_i16, const float* horizon, const float* dy, float* dw, float* dbias,
+                                       int32_t n, int32_t h, int32_t w_img, int32_t c_out, void* ws, size_t ws_bytes,
+                                       void* stream);
+/* replaces: nn.Conv2d(c_in, c_out, 3, stride=2) (+ nn.ReLU() if relu), conv.2 / conv.4 / conv.6 of
+ * 15_int16.ipynb:13750-13755.  (c_in, c_out) = (16, 32) or (32, 32); 3 <= h_in, w_in and w_in <= 128; bias may be NULL. */
+int pv_conv2d_s2_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                         int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of conv.2 / conv.4 / conv.6.  dy zeroed where dy_gate <= 0, dx [n][c_in][h_in][w_in] zeroed
+ * where x_gate <= 0.  Every element of dx is written; the last row / column of an even h_in / w_in, which the forward
+ * never reads, is exactly 0. */
+int pv_conv2d_s2_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                              int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+/* bytes of the weight-gradient workspace of the two Conv2d weight gradients: c_in = 6 (counts layer, c_out = 16), 16 or 32 */
+int pv_conv2d_s2_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                            size_t* bytes);
+/* replaces: the weight and bias gradients of conv.2 / conv.4 / conv.6.  dw [c_out][c_in][3][3] and dbias [c_out] are
+ * overwritten; slab partials summed in slab order (deterministic). */
+int pv_conv2d_s2_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias, int32_t n,
+                                int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
+                                void* stream);
+/* replaces: nn.ConvTranspose2d(c_in, c_out, 3, stride=2) (+ nn.ReLU() if relu), conv.8 / conv.10 / conv.12 of
+ * 15_int16.ipynb:13758-13762.  x [n][c_in][h][w] -> y [n][c_out][2 h + 1][2 w + 1]; w [c_in][c_out][3][3]; (c_in, c_out) =
+ * (32, 32), (32, 16) or (16, 1); 2 w + 1 <= 128; bias may be NULL. */
+int pv_convt2d_s2_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                          int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of conv.8 / conv.10 / conv.12: a stride-2 valid correlation of dy [n][c_out][2 h + 1][2 w + 1]
+ * (zeroed where dy_gate <= 0) with the unmirrored weights; dx [n][c_in][h][w] zeroed where x_gate <= 0. */
+int pv_convt2d_s2_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                               int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+/* bytes of the workspace of pv_convt2d_s2_bwd_weight_f32: one partial [c_in][c_out * 9 + 1] per slab of tiles, then one
+ * partial [c_out] per slab of images for the bias gradient */
+int pv_convt2d_s2_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                             size_t* bytes);
+/* replaces: the weight and bias gradients of conv.8 / conv.10 / conv.12: dw[ci][co][tap] = sum x[ci][p] dy[co][2 p + tap] in
+ * the [c_in][c_out][3][3] layout, dbias[co] = sum of dy[co] (both with dy zeroed where dy_gate <= 0); deterministic. */
+int pv_convt2d_s2_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias, int32_t n,
+                                 int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
+                                 void* stream);
 
 /* MaxPool3d over x[B*C planes][Ti,Hi,Wi]; argmax (may be NULL) = flat winner offset inside the plane stack, first
  * maximum wins, NaN propagates (torch CPU semantics).  bwd overwrites dx by gathering dy through argmax. */

@@ -184,6 +184,19 @@ SIGNATURES = {
     "pv_convt2d_ae_bwd_weight_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)],
     "pv_convt2d_ae_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
     "pv_mse_crop_norm_f32": [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp],
+    "pv_mse_window_norm_f32": [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz,
+                               c_vp],
+    "pv_conv2d_s2_counts_fwd_f32": [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "pv_conv2d_s2_counts_bwd_weight_f32": [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32,
+                                           c_vp, c_sz, c_vp],
+    "pv_conv2d_s2_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "pv_conv2d_s2_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "pv_conv2d_s2_bwd_weight_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)],
+    "pv_conv2d_s2_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
+    "pv_convt2d_s2_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "pv_convt2d_s2_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
+    "pv_convt2d_s2_bwd_weight_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)],
+    "pv_convt2d_s2_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
     "pv_maxpool3d_fwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_maxpool3d_bwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_mse_loss_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp],

@@ -1,6 +1,7 @@
 """torch.autograd.Function wrappers over the exact-f32 Conv2d 3x3 "valid" kernels: csrc/conv2d_f32.hip (experiments/002) and
 the 144-channel kernels with fused MaxPool2d(3) of csrc/conv2d_pool_f32.hip (experiments/001) and the encoder / decoder
-kernels of csrc/conv2d_ae_f32.hip (notebooks/16_maxpool.ipynb: Conv2d up to 128 wide, ConvTranspose2d, cropped MSE).
+kernels of csrc/conv2d_ae_f32.hip (notebooks/16_maxpool.ipynb: Conv2d up to 128 wide, ConvTranspose2d, cropped MSE) and the
+stride-2 Conv2d / ConvTranspose2d kernels of csrc/conv2d_s2_f32.hip (notebooks/14_back_to_2d_conv_AE.ipynb, 15_int16.ipynb).
 
 Reference operators replaced:
   experiments/002_cnn_processes_single_sat_image_then_rnn.py
@@ -16,6 +17,10 @@ Reference operators replaced:
     self.maxpool(F.relu(self.encoder_conv4(out)))                                                             :13788-13789
     F.relu(self.decoder_conv1..3(out)), self.decoder_conv4(out)                                               :13793-13801
     F.mse_loss(y_hat.squeeze(), normalise_images_in_model(y)[..., 8:-8, 8:-8])                                :13805-13809
+  notebooks/15_int16.ipynb (raw lines of the .ipynb file; notebook 14 has the same stack)
+    self.conv(cat(normalise_images_in_model(cat(history, flow)), horizon plane)): nn.Sequential of Conv2d 6 -> 16 -> 32 -> 32
+    -> 32 and ConvTranspose2d 32 -> 32 -> 16 -> 1, all 3x3 stride 2, ReLU between                              :13746-13780
+    F.mse_loss(y_hat.squeeze(), normalise_images_in_model(y)[..., :-1, :-1])                                  :13783-13788
 
 Gating.  As in functional.Conv3dGeneralF32, the ReLU gating of an activation gradient is moved into the kernel that
 produces it.  x_is_relu_output -> this layer's dx leaves already zeroed where x <= 0 (the lower layer's pre-activation
@@ -37,6 +42,11 @@ CONV2D_OPS = (K.conv2d_fwd_f32, K.conv2d_bwd_data_f32, K.conv2d_bwd_weight_f32)
 CONV2D144_OPS = (K.conv2d144_fwd_f32, K.conv2d144_bwd_data_f32, K.conv2d144_bwd_weight_f32)
 CONV2D_AE_OPS = (K.conv2d_ae_fwd_f32, K.conv2d_ae_bwd_data_f32, K.conv2d_ae_bwd_weight_f32)
 CONVT2D_AE_OPS = (K.convt2d_ae_fwd_f32, K.convt2d_ae_bwd_data_f32, K.convt2d_ae_bwd_weight_f32)
+CONV2D_S2_OPS = (K.conv2d_s2_fwd_f32, K.conv2d_s2_bwd_data_f32, K.conv2d_s2_bwd_weight_f32)
+CONVT2D_S2_OPS = (K.convt2d_s2_fwd_f32, K.convt2d_s2_bwd_data_f32, K.convt2d_s2_bwd_weight_f32)
+# ... of the raw-counts first layer: (forward, weight gradient)
+COUNTS_AE_OPS = (K.conv2d_ae_counts_fwd_f32, K.conv2d_ae_counts_bwd_weight_f32)
+COUNTS_S2_OPS = (K.conv2d_s2_counts_fwd_f32, K.conv2d_s2_counts_bwd_weight_f32)
 # ... and of the conv with fused MaxPool2d(3): the forward returns (pooled, codes), the gradients take the codes
 CONV2D144_POOL_OPS = (K.conv2d144_pool_fwd_f32, K.conv2d144_pool_bwd_data_f32, K.conv2d144_pool_bwd_weight_f32)
 CONV2D_AE_POOL_OPS = (K.conv2d_ae_pool_fwd_f32, K.conv2d_ae_pool_bwd_data_f32, K.conv2d_ae_pool_bwd_weight_f32)
@@ -67,8 +77,9 @@ class CoordsConv2dReLU(torch.autograd.Function):
 class ConvReLU(torch.autograd.Function):
     """nn.Conv2d(C_in, C_out, 3) (+ ReLU) on NCHW f32 through one family of entry points, ops = CONV2D_OPS (32 -> 32 or 4),
     CONV2D144_OPS (144 -> 144) or CONV2D_AE_OPS (16 or 32 -> 32, planes up to 128 wide); with CONVT2D_AE_OPS,
-    nn.ConvTranspose2d(C_in, C_out, 3) for (C_in, C_out) = (32, 32), (32, 16), (16, 16), (16, 1).  Saves the input, and the
-    output only where backward gates dy by it (relu and not dy_pregated)."""
+    nn.ConvTranspose2d(C_in, C_out, 3) for (C_in, C_out) = (32, 32), (32, 16), (16, 16), (16, 1); CONV2D_S2_OPS and
+    CONVT2D_S2_OPS are the stride-2 layers of notebooks 14 / 15 ((16 or 32) -> 32; (32, 32), (32, 16), (16, 1)).  Saves the
+    input, and the output only where backward gates dy by it (relu and not dy_pregated)."""
 
     @staticmethod
     def forward(ctx, ops, x, weight, bias, relu, x_is_relu_output, dy_pregated):
@@ -181,17 +192,17 @@ def sat_encoder001_f32(sat, x_coords, y_coords, conv1, conv2, conv3, n_frames):
 
 # ---- notebooks/16_maxpool.ipynb ----------------------------------------------------------------------------------------
 class CountsConvReLU(torch.autograd.Function):
-    """First layer of notebook 16: history [N, 4, H, W] and flow prediction [N, H, W] as raw counts (int16 or f32), horizon
-    [N]; the normalised 6-channel input is built inside the kernels (forward and weight gradient), never stored.  No
-    gradient flows to the inputs."""
+    """First layer of notebooks 14-16: history [N, 4, H, W] and flow prediction [N, H, W] as raw counts (int16 or f32),
+    horizon [N]; the normalised 6-channel input is built inside the kernels (forward and weight gradient), never stored.
+    ops = COUNTS_AE_OPS (stride 1, notebook 16) or COUNTS_S2_OPS (stride 2).  No gradient flows to the inputs."""
 
     @staticmethod
-    def forward(ctx, history, flow_pred, horizon, weight, bias, dy_pregated):
+    def forward(ctx, ops, history, flow_pred, horizon, weight, bias, dy_pregated):
         history, flow_pred = history.contiguous(), flow_pred.contiguous()
         horizon = horizon.to(torch.float32).contiguous()
-        y = K.conv2d_ae_counts_fwd_f32(history, flow_pred, horizon, weight.contiguous(), bias.contiguous())
+        y = ops[0](history, flow_pred, horizon, weight.contiguous(), bias.contiguous())
         ctx.save_for_backward(history, flow_pred, horizon, None if dy_pregated else y)
-        ctx.weight_shape = tuple(weight.shape)
+        ctx.ops, ctx.weight_shape = ops, tuple(weight.shape)
         return y
 
     @staticmethod
@@ -200,8 +211,8 @@ class CountsConvReLU(torch.autograd.Function):
         dy = dy.contiguous()
         if y is not None:
             dy = K.relu_gate_f32(dy, y)
-        dw, db = K.conv2d_ae_counts_bwd_weight_f32(history, flow_pred, horizon, dy, ctx.weight_shape)
-        return None, None, None, dw, db, None
+        dw, db = ctx.ops[1](history, flow_pred, horizon, dy, ctx.weight_shape)
+        return None, None, None, None, dw, db, None
 
 
 class MseCropNorm(torch.autograd.Function):
@@ -220,9 +231,25 @@ class MseCropNorm(torch.autograd.Function):
         return grad * g, None
 
 
+class MseWindowNorm(torch.autograd.Function):
+    """F.mse_loss(y_hat, normalise(target)[..., row0:row0 + P, col0:col0 + Q]): y_hat [N, P, Q] f32, target [N, T, U] raw
+    counts; the gradient 2 (y_hat - y) / count is produced in the same pass."""
+
+    @staticmethod
+    def forward(ctx, y_hat, target, row0, col0):
+        out, grad = K.mse_window_norm_f32(y_hat.contiguous(), target.contiguous(), row0, col0, need_grad=True)
+        ctx.save_for_backward(grad)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None
+
+
 def counts_conv_relu(history, flow_pred, horizon, weight, bias):
     """relu(encoder_conv1(normalised 6-channel input of 16_maxpool.ipynb:13760-13779)); gradients to weight and bias only."""
-    return CountsConvReLU.apply(history, flow_pred, horizon, weight, bias, False)
+    return CountsConvReLU.apply(COUNTS_AE_OPS, history, flow_pred, horizon, weight, bias, False)
 
 
 def conv2d_ae_relu(x, weight, bias, relu=True, x_is_relu_output=False):
@@ -251,7 +278,7 @@ def nb16_autoencoder_f32(history, flow_pred, horizon, enc, dec):
     one consumer, the next layer, whose data gradient leaves gated by it (x_is_relu_output), so its producer skips gating
     the arriving gradient (dy_pregated).  The pooled output is 0 exactly where its window is dead, which the codes carry,
     so decoder_conv1 leaves its dx ungated.  The pairing only holds inside this chain."""
-    y = CountsConvReLU.apply(history, flow_pred, horizon, enc[0].weight, enc[0].bias, True)
+    y = CountsConvReLU.apply(COUNTS_AE_OPS, history, flow_pred, horizon, enc[0].weight, enc[0].bias, True)
     y = ConvReLU.apply(CONV2D_AE_OPS, y, enc[1].weight, enc[1].bias, True, True, True)
     y = ConvReLU.apply(CONV2D_AE_OPS, y, enc[2].weight, enc[2].bias, True, True, True)
     y = ConvPool.apply(CONV2D_AE_POOL_OPS, y, enc[3].weight, enc[3].bias, True)
@@ -259,3 +286,39 @@ def nb16_autoencoder_f32(history, flow_pred, horizon, enc, dec):
     y = ConvReLU.apply(CONVT2D_AE_OPS, y, dec[1].weight, dec[1].bias, True, True, True)
     y = ConvReLU.apply(CONVT2D_AE_OPS, y, dec[2].weight, dec[2].bias, True, True, True)
     return ConvReLU.apply(CONVT2D_AE_OPS, y, dec[3].weight, dec[3].bias, False, True, False)
+
+
+# ---- notebooks/14_back_to_2d_conv_AE.ipynb, 15_int16.ipynb -------------------------------------------------------------
+def counts_conv_s2_relu(history, flow_pred, horizon, weight, bias):
+    """relu(conv.0(normalised 6-channel input of 15_int16.ipynb:13766-13779)), stride 2; gradients to weight and bias only."""
+    return CountsConvReLU.apply(COUNTS_S2_OPS, history, flow_pred, horizon, weight, bias, False)
+
+
+def conv2d_s2_relu(x, weight, bias, relu=True, x_is_relu_output=False):
+    """nn.Conv2d(16 or 32, 32, 3, stride=2)(x) (+ ReLU), planes up to 128 wide.  x_is_relu_output: dx leaves gated by x > 0."""
+    return ConvReLU.apply(CONV2D_S2_OPS, x, weight, bias, bool(relu), bool(x_is_relu_output), False)
+
+
+def conv_transpose2d_s2_relu(x, weight, bias, relu=True, x_is_relu_output=False):
+    """nn.ConvTranspose2d(C_in, C_out, 3, stride=2)(x) (+ ReLU).  x_is_relu_output: dx leaves gated by x > 0."""
+    return ConvReLU.apply(CONVT2D_S2_OPS, x, weight, bias, bool(relu), bool(x_is_relu_output), False)
+
+
+def mse_window_norm(y_hat, target, row0=0, col0=0):
+    """F.mse_loss(y_hat, normalise_images_in_model(target)[..., row0:row0 + P, col0:col0 + Q]); (0, 0) with a target one
+    larger than y_hat is y[..., :-1, :-1] of 15_int16.ipynb:13783-13788."""
+    return MseWindowNorm.apply(y_hat, target, int(row0), int(col0))
+
+
+def nb15_autoencoder_f32(history, flow_pred, horizon, conv):
+    """self.conv(images) of 15_int16.ipynb:13746-13780; conv = the notebook's nn.Sequential (modules 0, 2, 4, 6 nn.Conv2d and
+    8, 10, 12 nn.ConvTranspose2d, all stride 2; the nn.ReLU modules between them are fused into the layers' kernels).  Every
+    inner ReLU output has one consumer, the next layer, whose data gradient leaves gated by it (x_is_relu_output), so its
+    producer skips gating the arriving gradient (dy_pregated): no ReLU or mask kernel runs on its own.  The pairing only
+    holds inside this chain."""
+    y = CountsConvReLU.apply(COUNTS_S2_OPS, history, flow_pred, horizon, conv[0].weight, conv[0].bias, True)
+    for i in (2, 4, 6):
+        y = ConvReLU.apply(CONV2D_S2_OPS, y, conv[i].weight, conv[i].bias, True, True, True)
+    for i in (8, 10):
+        y = ConvReLU.apply(CONVT2D_S2_OPS, y, conv[i].weight, conv[i].bias, True, True, True)
+    return ConvReLU.apply(CONVT2D_S2_OPS, y, conv[12].weight, conv[12].bias, False, True, False)

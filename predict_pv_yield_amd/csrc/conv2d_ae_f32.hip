@@ -22,44 +22,32 @@
 // gradient also stages the tile's G rows, so its tiles are chosen by the smallest halo overhead that fits.
 // First layer: history [B][4][S][S] and the flow prediction [B][S][S] are read in place as int16 or f32 counts, normalised
 // ((v - 93.23458) / 115.34247: subtract, then a true f32 divide) while staged; the horizon plane is synthesised
-// (load_in<SRC_COUNTS>).  Pooling follows conv2d_pool_f32.hip through the shared pool3_relu / pool3_expand: the forward
+// (load_in<SRC_COUNTS> of conv2d_counts_f32.h, shared with conv2d_s2_f32.hip).  Pooling follows conv2d_pool_f32.hip
+// through the shared pool3_relu / pool3_expand: the forward
 // pools the pre-activations of a tile of whole windows, applies ReLU to the maxima, and writes one code byte per pooled
 // output (0..8 = first maximum, row-major; 255 = maximum <= 0, no gradient); backward passes expand the pooled gradient
 // through the codes while staging.  Weight gradients: fixed slabs, each block writing its partial sums to its own
 // workspace slab, added in slab order (no atomics, identical bits run to run).
-#include "conv2d_tile_f32.h"
+#include "conv2d_counts_f32.h"
 
 namespace pv {
 namespace {
 
-constexpr float kCountMean = 93.23458f, kCountStd = 115.34247f;   // 16_maxpool.ipynb: normalise_images_in_model
 constexpr int kMaxWidth = 128, kCrop = 8, kMinSide = 11;
 
-__device__ __forceinline__ float count_at(const void* p, int is_i16, size_t off) {
-  const float v = is_i16 ? (float)((const int16_t*)p)[off] : ((const float*)p)[off];
-  return __fdiv_rn(v - kCountMean, kCountStd);
-}
-
-// SRC_COUNTS: the four history frames and the flow prediction normalised in place, then the horizon plane
-template <>
-__device__ __forceinline__ float load_in<SRC_COUNTS>(const In& s, int n, int ch, int r, int col) {
-  if (ch < 4) return count_at(s.x, s.x_i16, (((size_t)n * 4 + ch) * s.h + r) * s.w + col);
-  if (ch == 4) return count_at(s.flow, s.flow_i16, ((size_t)n * s.h + r) * s.w + col);
-  return s.horizon[n];
-}
-
-// Cropped, normalised MSE (16_maxpool.ipynb, _training_or_validation_step): block b takes example b; d = y_hat - (target[8
-// + r][8 + c] - mean) / std, dy_hat = 2 d / count, partial[b] = sum d^2 (tree sum in LDS: fixed order); then one block
-// adds the partials in index order.
-__global__ __launch_bounds__(kBlock) void mse_crop_norm_partial(const float* __restrict__ y_hat, const void* target,
-                                                               int t_i16, int oh, int ow, int th, int tw, float inv_count,
-                                                               float* __restrict__ dy_hat, float* __restrict__ partials) {
+// Windowed, normalised MSE (16_maxpool.ipynb, _training_or_validation_step: the window starts at (8, 8); 15_int16.ipynb: at
+// (0, 0)): block b takes example b; d = y_hat - (target[row0 + r][col0 + c] - mean) / std, dy_hat = 2 d / count, partial[b]
+// = sum d^2 (tree sum in LDS: fixed order); then one block adds the partials in index order.
+__global__ __launch_bounds__(kBlock) void mse_window_norm_partial(const float* __restrict__ y_hat, const void* target,
+                                                                 int t_i16, int oh, int ow, int th, int tw, int row0,
+                                                                 int col0, float inv_count, float* __restrict__ dy_hat,
+                                                                 float* __restrict__ partials) {
   __shared__ float part[kBlock];
   const int b = blockIdx.x, tot = oh * ow;
   float s = 0.0f;
   for (int i = threadIdx.x; i < tot; i += kBlock) {
     const int r = i / ow, c = i - r * ow;
-    const float t = count_at(target, t_i16, ((size_t)b * th + kCrop + r) * tw + kCrop + c);
+    const float t = count_at(target, t_i16, ((size_t)b * th + row0 + r) * tw + col0 + c);
     const float d = y_hat[(size_t)b * tot + i] - t;
     if (dy_hat) dy_hat[(size_t)b * tot + i] = 2.0f * d * inv_count;
     s += d * d;
@@ -73,7 +61,7 @@ __global__ __launch_bounds__(kBlock) void mse_crop_norm_partial(const float* __r
   if (threadIdx.x == 0) partials[b] = part[0];
 }
 
-__global__ __launch_bounds__(kBlock) void mse_crop_norm_final(const float* __restrict__ partials, int n, float inv_count,
+__global__ __launch_bounds__(kBlock) void mse_window_norm_final(const float* __restrict__ partials, int n, float inv_count,
                                                              float* __restrict__ loss) {
   __shared__ float part[kBlock];
   float s = 0.0f;
@@ -152,13 +140,6 @@ int run_wgrad(const char* who, const In& in, const In& g, int pad, const WgPlan&
   PV_WG(1, 1);
 #undef PV_WG
   return fail(PV_ESIZE, "%s: no weight-gradient tile for %d rows x %d channels", who, g.c_in, in.c_in);
-}
-
-In counts_in(const void* hist, int hist_i16, const void* flow, int flow_i16, const float* horizon, int h, int w) {
-  In s = {};
-  s.x = (const float*)hist, s.x_i16 = hist_i16, s.flow = flow, s.flow_i16 = flow_i16, s.horizon = horizon;
-  s.c_in = 6, s.h = h, s.w = w;
-  return s;
 }
 
 enum Kind { KIND_CONV, KIND_POOL, KIND_CONVT };
@@ -481,6 +462,28 @@ int pv_convt2d_ae_bwd_weight_f32(const float* x, const float* dy, const float* d
                                          ws_bytes, as_stream(stream));
 }
 
+int pv_mse_window_norm_f32(const float* y_hat, const void* target, int32_t target_is_i16, int32_t n, int32_t out_h,
+                           int32_t out_w, int32_t target_h, int32_t target_w, int32_t row0, int32_t col0, float* loss,
+                           float* dy_hat, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "pv_mse_window_norm_f32";
+  PV_REQUIRE(y_hat && target && loss, PV_EINVAL, "%s: null pointer", who);
+  PV_REQUIRE(n > 0 && out_h > 0 && out_w > 0, PV_EINVAL, "%s: non-positive dimension", who);
+  PV_REQUIRE(row0 >= 0 && col0 >= 0 && row0 + out_h <= target_h && col0 + out_w <= target_w, PV_ESIZE,
+             "%s: the %d x %d window at (%d, %d) leaves the %d x %d target", who, out_h, out_w, row0, col0, target_h,
+             target_w);
+  PV_REQUIRE((long long)n * target_h * target_w < (1LL << 31), PV_ESIZE, "%s: tensor beyond 2^31 elements", who);
+  int rc = check_workspace(who, ws, ws_bytes, (size_t)n * sizeof(float));
+  if (rc) return rc;
+  const float inv_count = (float)(1.0 / ((double)n * out_h * out_w));
+  hipStream_t st = as_stream(stream);
+  mse_window_norm_partial<<<dim3((unsigned)n), dim3(kBlock), 0, st>>>(y_hat, target, target_is_i16, out_h, out_w, target_h,
+                                                                     target_w, row0, col0, inv_count, dy_hat, (float*)ws);
+  rc = check_launch(who);
+  if (rc) return rc;
+  mse_window_norm_final<<<dim3(1), dim3(kBlock), 0, st>>>((const float*)ws, n, inv_count, loss);
+  return check_launch(who);
+}
+
 int pv_mse_crop_norm_f32(const float* y_hat, const void* target, int32_t target_is_i16, int32_t n, int32_t out_h,
                          int32_t out_w, int32_t target_h, int32_t target_w, float* loss, float* dy_hat, void* ws,
                          size_t ws_bytes, void* stream) {
@@ -490,17 +493,8 @@ int pv_mse_crop_norm_f32(const float* y_hat, const void* target, int32_t target_
   PV_REQUIRE(target_h - 2 * kCrop == out_h && target_w - 2 * kCrop == out_w, PV_ESIZE,
              "%s: target side %d x %d does not match the output %d x %d plus the %d-pixel crop on each side", who, target_h,
              target_w, out_h, out_w, kCrop);
-  PV_REQUIRE((long long)n * target_h * target_w < (1LL << 31), PV_ESIZE, "%s: tensor beyond 2^31 elements", who);
-  int rc = check_workspace(who, ws, ws_bytes, (size_t)n * sizeof(float));
-  if (rc) return rc;
-  const float inv_count = (float)(1.0 / ((double)n * out_h * out_w));
-  hipStream_t st = as_stream(stream);
-  mse_crop_norm_partial<<<dim3((unsigned)n), dim3(kBlock), 0, st>>>(y_hat, target, target_is_i16, out_h, out_w, target_h,
-                                                                   target_w, inv_count, dy_hat, (float*)ws);
-  rc = check_launch(who);
-  if (rc) return rc;
-  mse_crop_norm_final<<<dim3(1), dim3(kBlock), 0, st>>>((const float*)ws, n, inv_count, loss);
-  return check_launch(who);
+  return pv_mse_window_norm_f32(y_hat, target, target_is_i16, n, out_h, out_w, target_h, target_w, kCrop, kCrop, loss,
+                                dy_hat, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,9 +1,9 @@
-// What the three exact-f32 Conv2d 3x3 files share: conv2d_f32.hip (experiments/002, 17 / 32 -> 32 / 4 channels),
-// conv2d_pool_f32.hip (experiments/001, 144 channels with fused MaxPool2d(3)) and conv2d_ae_f32.hip (notebooks/16_maxpool:
-// Conv2d / ConvTranspose2d up to 128 wide).  This header holds the ordered slab sum of their weight gradients (also in the
+// What the four exact-f32 Conv2d 3x3 files share: conv2d_f32.hip (experiments/002, 17 / 32 -> 32 / 4 channels),
+// conv2d_pool_f32.hip (experiments/001, 144 channels with fused MaxPool2d(3)), conv2d_ae_f32.hip (notebooks/16_maxpool:
+// Conv2d / ConvTranspose2d up to 128 wide) and conv2d_s2_f32.hip (notebooks 14 / 15: the same at stride 2).  This header holds the ordered slab sum of their weight gradients (also in the
 // ConvTranspose2d layout), the MaxPool2d(3) + ReLU window rule and its backward, the descriptor of what a pass reads (In) with
 // its plain and pooled-gradient loads, the five synthesised input channels of the two experiments and the argument checks
-// they all repeat.  The 144-channel main loops (weights in LDS, K streamed in chunks) stay in their file; the two files whose
+// they all repeat.  The 144-channel main loops (weights in LDS, K streamed in chunks) stay in their file; the files whose
 // weights fit the VGPRs share theirs in conv2d_tile_f32.h.
 #pragma once
 #include "pv_common.h"

@@ -2,9 +2,10 @@
 // tr x tc output positions of one image staged in LDS (v_mfma_f32_16x16x4_f32: one rounding per product, f32 accumulation):
 //   forward-like  D[m][pos]  = sum_{tap, c} A[m][(tap, c)] * X[c][pos + tap]     A = weights, held in VGPRs
 //   wgrad-like    D[m][col]  = sum_{pos} G[m][pos] * X[c][pos + tap]             col = (c, tap), plus a ones column
-// conv2d_f32.hip (experiments/002: full-width bands of rows, tc = w_out) and conv2d_ae_f32.hip (notebooks/16_maxpool: tiles
-// of at most 64 columns) both instantiate them; each keeps its tile planner, its argument checks and its first layer's
-// source kind.  A forward-like output element's sum depends only on the (tap, channel group) order, not on the tile it
+// conv2d_f32.hip (experiments/002: full-width bands of rows, tc = w_out), conv2d_ae_f32.hip (notebooks/16_maxpool: tiles of
+// at most 64 columns) and conv2d_s2_f32.hip (notebooks 14 / 15: the same two GEMMs at stride 2, STRIDE = 2, the tile staged
+// split by column parity) instantiate them; each keeps its tile planner, its argument checks and its first layer's source
+// kind.  A forward-like output element's sum depends only on the (tap, channel group) order, not on the tile it
 // falls in; the weight gradient's bits depend on the row-major position order inside an item, the items per slab and the
 // slab order (fixed slabs, each block writing its own, added in slab order: no atomics, identical bits run to run).
 #pragma once
@@ -38,6 +39,24 @@ __device__ void stage_in(float* lds, const In& s, int n, int cinp, int r0, int r
   }
 }
 
+// The same for a stride-2 pass, split by column parity: row r of a channel holds its even columns first ((cols + 1) / 2 of
+// them), then its odd ones, so that the columns 2 ow + kw of consecutive ow are consecutive words for each kw (kw = 0, 2:
+// even part at ow, ow + 1; kw = 1: odd part at ow) -- a unit-stride ds_read_b32 where the plain layout read at stride 2
+// would put two lanes on every bank.
+__device__ __forceinline__ int split_col(int col, int n_even) { return (col & 1) * n_even + (col >> 1); }
+
+template <int SRC>
+__device__ void stage_in_split(float* lds, const In& s, int n, int cinp, int r0, int rows, int c0, int cols) {
+  const int tot = cinp * rows * cols, n_even = (cols + 1) / 2;
+  for (int i = threadIdx.x; i < tot; i += kBlock) {
+    const int col = i % cols, r = (i / cols) % rows, ch = i / (cols * rows);
+    const int ir = r0 + r, ic = c0 + col;
+    float v = 0.0f;
+    if (ch < s.c_in && ir >= 0 && ir < s.h && ic >= 0 && ic < s.w) v = load_in<SRC>(s, n, ch, ir, ic);
+    lds[i - col + split_col(col, n_even)] = v;
+  }
+}
+
 struct Fwd {
   In in;
   const float* w;          // element (m, c, tap) at w[m * w_sm + c * w_sc + (flip ? 8 - tap : tap)]
@@ -48,27 +67,9 @@ struct Fwd {
   int m_out, pad, h_out, w_out, tr, tc, n_rb, n_cb, w_sm, w_sc, flip, relu;
 };
 
-// Forward-like pass.  Block = (image, row band, column band): tr x tc output positions flattened row-major, wave w takes
-// the 16-position tiles w, w + 4, ...  CINP = input channels rounded up to 4 (one MFMA k-step = 4 channels of one tap), MT
-// = 16-row tiles of output channels.  Per tile: 9 * CINP / 4 k-steps, each one ds_read_b32 (B: 4 channels x 16 positions)
-// feeding MT MFMAs against weights resident in VGPRs (A: 16 output channels x 4 channels).  The bias is added after the
-// accumulation.  POOL: the tile is one row of whole windows (3 x 3 k positions); pre-activations go to LDS behind the
-// staged tile, then every thread takes (channel, window) pairs through pool3_relu.
-template <int CINP, int MT, int SRC, bool POOL>
-__global__ __launch_bounds__(kBlock) void conv2d_tile_fwd(Fwd a) {
-  extern __shared__ float lds[];
-  constexpr int KS = CINP / 4;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int bid = blockIdx.x;
-  const int cb = bid % a.n_cb; bid /= a.n_cb;
-  const int rb = bid % a.n_rb;
-  const int n = bid / a.n_rb;
-  const int r0 = rb * a.tr, c0 = cb * a.tc;
-  const int rows = min(a.tr, a.h_out - r0), cols = min(a.tc, a.w_out - c0);
-  const int sw = cols + 2, cs = (rows + 2) * sw, npos = rows * cols;
-
-  // weights: lane holds A[m = mt * 16 + lane % 16][c = s * 4 + lane / 16] of every tap
-  float wa[MT][9][KS];
+// weights resident in VGPRs: lane holds A[m = mt * 16 + lane % 16][c = s * 4 + lane / 16] of every tap
+template <int MT, int KS>
+__device__ __forceinline__ void load_weights(float (&wa)[MT][9][KS], const Fwd& a, int lane) {
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
     const int m = mt * 16 + (lane & 15);
@@ -81,8 +82,44 @@ __global__ __launch_bounds__(kBlock) void conv2d_tile_fwd(Fwd a) {
       }
     }
   }
+}
 
-  stage_in<SRC>(lds, a.in, n, CINP, r0 - a.pad, rows + 2, c0 - a.pad, sw);
+// one output element of a forward-like pass: bias, ReLU, output gate
+__device__ __forceinline__ void store_out(const Fwd& a, int n, int m, int r, int c, float acc) {
+  const size_t off = (((size_t)n * a.m_out + m) * a.h_out + r) * a.w_out + c;
+  float v = acc + (a.bias ? a.bias[m] : 0.0f);
+  if (a.relu) v = v > 0.0f ? v : 0.0f;
+  if (a.out_gate && !(a.out_gate[off] > 0.0f)) v = 0.0f;
+  a.y[off] = v;
+}
+
+// Forward-like pass.  Block = (image, row band, column band): tr x tc output positions flattened row-major, wave w takes
+// the 16-position tiles w, w + 4, ...  CINP = input channels rounded up to 4 (one MFMA k-step = 4 channels of one tap), MT
+// = 16-row tiles of output channels.  Per tile: 9 * CINP / 4 k-steps, each one ds_read_b32 (B: 4 channels x 16 positions)
+// feeding MT MFMAs against weights resident in VGPRs (A: 16 output channels x 4 channels).  The bias is added after the
+// accumulation.  POOL: the tile is one row of whole windows (3 x 3 k positions); pre-activations go to LDS behind the
+// staged tile, then every thread takes (channel, window) pairs through pool3_relu.  STRIDE = 2 (pad 0, no POOL): output (oh,
+// ow) reads rows 2 oh + kh and columns 2 ow + kw of a (2 rows + 1) x (2 cols + 1) tile staged split by column parity.
+template <int CINP, int MT, int SRC, bool POOL, int STRIDE = 1>
+__global__ __launch_bounds__(kBlock) void conv2d_tile_fwd(Fwd a) {
+  static_assert(STRIDE == 1 || (STRIDE == 2 && !POOL), "stride 1, or stride 2 without the pool");
+  extern __shared__ float lds[];
+  constexpr int KS = CINP / 4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int bid = blockIdx.x;
+  const int cb = bid % a.n_cb; bid /= a.n_cb;
+  const int rb = bid % a.n_rb;
+  const int n = bid / a.n_rb;
+  const int r0 = rb * a.tr, c0 = cb * a.tc;
+  const int rows = min(a.tr, a.h_out - r0), cols = min(a.tc, a.w_out - c0);
+  const int sw = STRIDE == 2 ? 2 * cols + 1 : cols + 2, sr = STRIDE == 2 ? 2 * rows + 1 : rows + 2;
+  const int cs = sr * sw, npos = rows * cols;
+
+  float wa[MT][9][KS];
+  load_weights<MT, KS>(wa, a, lane);
+
+  if constexpr (STRIDE == 2) stage_in_split<SRC>(lds, a.in, n, CINP, 2 * r0, sr, 2 * c0, sw);
+  else stage_in<SRC>(lds, a.in, n, CINP, r0 - a.pad, sr, c0 - a.pad, sw);
   __syncthreads();
   float* pre = lds + CINP * cs;   // POOL: [MT * 16][npos]
 
@@ -92,13 +129,14 @@ __global__ __launch_bounds__(kBlock) void conv2d_tile_fwd(Fwd a) {
     const bool valid = p < npos;
     const int pp = valid ? p : 0;
     const int oh = pp / cols, ow = pp - oh * cols;
-    const float* src = lds + (lane >> 4) * cs + oh * sw + ow;
+    const float* src = lds + (lane >> 4) * cs + STRIDE * oh * sw + ow;
     acc4 acc[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt] = (acc4){0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
-      const float* st = src + (tap / 3) * sw + (tap % 3);
+      // stride 2: kw = 1 is the odd half (cols + 1 words in), kw = 2 the even half one word on
+      const float* st = src + (tap / 3) * sw + (STRIDE == 2 ? (tap % 3 == 1 ? cols + 1 : tap % 3 / 2) : tap % 3);
 #pragma unroll
       for (int s = 0; s < KS; ++s) {
         const float b = st[s * 4 * cs];
@@ -115,11 +153,7 @@ __global__ __launch_bounds__(kBlock) void conv2d_tile_fwd(Fwd a) {
         if (POOL) {
           pre[m * npos + p] = acc[mt][i];
         } else if (m < a.m_out) {
-          const size_t off = (((size_t)n * a.m_out + m) * a.h_out + r0 + oh) * a.w_out + c0 + ow;
-          float v = acc[mt][i] + (a.bias ? a.bias[m] : 0.0f);
-          if (a.relu) v = v > 0.0f ? v : 0.0f;
-          if (a.out_gate && !(a.out_gate[off] > 0.0f)) v = 0.0f;
-          a.y[off] = v;
+          store_out(a, n, m, r0 + oh, c0 + ow, acc[mt][i]);
         }
       }
   }
@@ -149,12 +183,14 @@ struct Wg {
   int pad, h_out, w_out, tr, tc, n_rb, n_cb, items, per, cinp;
 };
 
-template <int MT, int NTW, int XSRC, int GSRC>
+// STRIDE = 2 (pad 0): position (oh, ow) slides over x at (2 oh + kh, 2 ow + kw); the x tile is (2 tr + 1) x (2 tc + 1), staged
+// split by column parity (stage_in_split).
+template <int MT, int NTW, int XSRC, int GSRC, int STRIDE = 1>
 __global__ __launch_bounds__(kBlock) void conv2d_tile_wgrad(Wg q) {
   extern __shared__ float lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int k9 = q.in.c_in * 9, ncols = k9 + 1, nt = (ncols + 15) / 16;
-  const int sw = q.tc + 2, cs = (q.tr + 2) * sw;
+  const int sw = STRIDE == 2 ? 2 * q.tc + 1 : q.tc + 2, sr = STRIDE == 2 ? 2 * q.tr + 1 : q.tr + 2, cs = sr * sw;
   const int dps = (q.tr * q.tc + 3) & ~3;
   float* xl = lds;
   float* dl = xl + q.cinp * cs;
@@ -168,7 +204,7 @@ __global__ __launch_bounds__(kBlock) void conv2d_tile_wgrad(Wg q) {
     const int col = (wave + 4 * j) * 16 + (lane & 15);
     const bool real = col < k9;
     const int ci = real ? col / 9 : 0, tap = real ? col % 9 : 0;
-    coff[j] = ci * cs + (tap / 3) * sw + tap % 3;
+    coff[j] = ci * cs + (tap / 3) * sw + (STRIDE == 2 ? (tap % 3 == 1 ? q.tc + 1 : tap % 3 / 2) : tap % 3);
     bmul[j] = real ? 1.0f : 0.0f;
     badd[j] = col == k9 ? 1.0f : 0.0f;
   }
@@ -184,7 +220,8 @@ __global__ __launch_bounds__(kBlock) void conv2d_tile_wgrad(Wg q) {
     const int r0 = rb * q.tr, c0 = cb * q.tc;
     const int rows = min(q.tr, q.h_out - r0), cols = min(q.tc, q.w_out - c0), npos = rows * cols;
     __syncthreads();   // the previous item's reads are done
-    stage_in<XSRC>(xl, q.in, n, q.cinp, r0 - q.pad, q.tr + 2, c0 - q.pad, sw);
+    if constexpr (STRIDE == 2) stage_in_split<XSRC>(xl, q.in, n, q.cinp, 2 * r0, sr, 2 * c0, sw);
+    else stage_in<XSRC>(xl, q.in, n, q.cinp, r0 - q.pad, sr, c0 - q.pad, sw);
     for (int i = threadIdx.x; i < MT * 16 * dps; i += kBlock) {
       const int m = i / dps, p = i - m * dps;
       float v = 0.0f;
@@ -196,7 +233,7 @@ __global__ __launch_bounds__(kBlock) void conv2d_tile_wgrad(Wg q) {
     }
     for (int p = threadIdx.x; p < dps; p += kBlock) {
       const int oh = p / cols, ow = p - oh * cols;
-      xo[p] = p < npos ? oh * sw + ow : 0;
+      xo[p] = p < npos ? STRIDE * oh * sw + ow : 0;
     }
     __syncthreads();
     if (wave < nt) {
@@ -255,15 +292,15 @@ inline Fwd full_fwd_args(const float* w, const float* bias, float* y, int m_out,
 }
 
 // the forward-like pass over n images with the tiles (tr, tc, n_rb, n_cb) its caller planned
-template <int CINP, int MT, int SRC, bool POOL>
+template <int CINP, int MT, int SRC, bool POOL, int STRIDE = 1>
 int launch_fwd(const char* who, const Fwd& a, int n, hipStream_t st) {
-  size_t lds = (size_t)CINP * (a.tr + 2) * (a.tc + 2);
+  size_t lds = STRIDE == 2 ? (size_t)CINP * (2 * a.tr + 1) * (2 * a.tc + 1) : (size_t)CINP * (a.tr + 2) * (a.tc + 2);
   if (POOL) lds += (size_t)MT * 16 * a.tr * a.tc;
   lds *= sizeof(float);
   PV_REQUIRE(lds <= kLdsFloats * sizeof(float), PV_ESIZE, "%s: tile of %zu bytes beyond the LDS budget", who, lds);
   const long long blocks = (long long)n * a.n_rb * a.n_cb;
   PV_REQUIRE(blocks > 0 && blocks < (1LL << 31), PV_ESIZE, "%s: grid of %lld blocks", who, blocks);
-  conv2d_tile_fwd<CINP, MT, SRC, POOL><<<dim3((unsigned)blocks), dim3(kBlock), lds, st>>>(a);
+  conv2d_tile_fwd<CINP, MT, SRC, POOL, STRIDE><<<dim3((unsigned)blocks), dim3(kBlock), lds, st>>>(a);
   return check_launch(who);
 }
 
@@ -274,23 +311,24 @@ struct WgPlan {
   size_t lds, ws;
 };
 
-inline size_t wg_lds_floats(int cinp, int mt, int tr, int tc) {
+inline size_t wg_lds_floats(int cinp, int mt, int tr, int tc, int stride = 1) {
   const size_t dps = ((size_t)tr * tc + 3) & ~(size_t)3;
-  return (size_t)cinp * (tr + 2) * (tc + 2) + (size_t)mt * 16 * dps + dps;
+  const size_t tile = stride == 2 ? (size_t)(2 * tr + 1) * (2 * tc + 1) : (size_t)(tr + 2) * (tc + 2);
+  return (size_t)cinp * tile + (size_t)mt * 16 * dps + dps;
 }
 
 // rows = the D rows (the layer's output channels), c = the sliding operand's channels
-inline void slab_split(WgPlan& p, int n, int c, int rows) {
+inline void slab_split(WgPlan& p, int n, int c, int rows, int stride = 1) {
   p.items = n * p.n_rb * p.n_cb;
   const int want = std::min(p.items, kMaxSlabs);
   p.per = (p.items + want - 1) / want;
   p.n_slabs = (p.items + p.per - 1) / p.per;
-  p.lds = wg_lds_floats(p.cinp, p.mt, p.tr, p.tc) * sizeof(float);
+  p.lds = wg_lds_floats(p.cinp, p.mt, p.tr, p.tc, stride) * sizeof(float);
   p.ws = (size_t)p.n_slabs * rows * (c * 9 + 1) * sizeof(float);
 }
 
 // the wgrad-like pass and its slab sum; MT = p.mt, NTW = ceil(ceil((9 in.c_in + 1) / 16) / 4) column tiles per wave
-template <int MT, int NTW, int XSRC, int GSRC>
+template <int MT, int NTW, int XSRC, int GSRC, int STRIDE = 1>
 int launch_wgrad(const char* who, const In& in, const In& g, int pad, const WgPlan& p, float* dw, float* db, bool transposed,
                  void* ws, size_t ws_bytes, hipStream_t st) {
   int rc = check_workspace(who, ws, ws_bytes, p.ws);
@@ -300,7 +338,7 @@ int launch_wgrad(const char* who, const In& in, const In& g, int pad, const WgPl
   q.in = in, q.g = g, q.slabs = (float*)ws, q.pad = pad;
   q.h_out = p.h_out, q.w_out = p.w_out, q.tr = p.tr, q.tc = p.tc, q.n_rb = p.n_rb, q.n_cb = p.n_cb;
   q.items = p.items, q.per = p.per, q.cinp = p.cinp;
-  conv2d_tile_wgrad<MT, NTW, XSRC, GSRC><<<dim3((unsigned)p.n_slabs), dim3(kBlock), p.lds, st>>>(q);
+  conv2d_tile_wgrad<MT, NTW, XSRC, GSRC, STRIDE><<<dim3((unsigned)p.n_slabs), dim3(kBlock), p.lds, st>>>(q);
   rc = check_launch(who);
   if (rc) return rc;
   launch_slab_sum(ws, dw, db, g.c_in, in.c_in * 9, p.n_slabs, st, transposed);

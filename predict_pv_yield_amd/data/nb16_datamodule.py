@@ -31,7 +31,9 @@ def make_fake_nb16_batch(super_batch, batch_size: int, image_size_pixels: int, r
 
 class Nb16DataModule(LightningDataModule):
     """n_train_data / n_val_data seeded batches drawn from n_super_batches synthetic super-batches, built once on the device
-    at setup()."""
+    at setup().  make_batch: the model's batch builder (a subclass sets its own target crop)."""
+
+    make_batch = staticmethod(make_fake_nb16_batch)
 
     def __init__(self, batch_size: int = 64, image_size_pixels: int = 128, n_train_data: int = 8, n_val_data: int = 2,
                  n_super_batches: int = 2, n_timesteps: int = 16, frame_size_pixels: int = 176, seed: int = 1234,
@@ -50,7 +52,7 @@ class Nb16DataModule(LightningDataModule):
         rng = np.random.default_rng(self.seed)
 
         def batches(n):
-            return [make_fake_nb16_batch(supers[int(rng.integers(len(supers)))], self.batch_size, self.image_size_pixels, rng)
+            return [self.make_batch(supers[int(rng.integers(len(supers)))], self.batch_size, self.image_size_pixels, rng)
                     for _ in range(n)]
 
         self._train, self._val = batches(self.n_train_data), batches(self.n_val_data)

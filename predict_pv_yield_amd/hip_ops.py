@@ -1573,6 +1573,179 @@ def mse_crop_norm_f32(y_hat, target, need_grad=True):
     return loss, grad
 
 
+def mse_window_norm_f32(y_hat, target, row0=0, col0=0, need_grad=True):
+    """mse_loss(y_hat, normalise(target)[..., row0:row0 + P, col0:col0 + Q]) for y_hat [N, P, Q] f32 and target [N, T, U]
+    counts (int16 or f32).  Returns (loss f32[1], dy_hat or None)."""
+    who = "mse_window_norm_f32"
+    _shape_check(y_hat.dim() == 3 and target.dim() == 3 and target.shape[0] == y_hat.shape[0], who,
+                 f"y_hat [N, P, Q] and target [N, T, U] expected, got {tuple(y_hat.shape)} / {tuple(target.shape)}")
+    require_cuda(y_hat, target)
+    _f32_contig(y_hat)
+    _counts_contig(who, target)
+    n, oh, ow = y_hat.shape
+    loss = torch.empty((1,), dtype=torch.float32, device=y_hat.device)
+    grad = torch.empty_like(y_hat) if need_grad else None
+    ws = _workspace("mse_window_norm", 4 * n, y_hat.device)
+    check(get_lib().pv_mse_window_norm_f32(ptr(y_hat), ptr(target), int(target.dtype == torch.int16), n, oh, ow,
+                                           target.shape[1], target.shape[2], int(row0), int(col0), ptr(loss), ptr(grad),
+                                           ptr(ws), 4 * n, current_stream_ptr()), "pv_mse_window_norm_f32")
+    return loss, grad
+
+
+# ------------------------------------------------------------------------------------------------
+# notebooks/14_back_to_2d_conv_AE.ipynb, 15_int16.ipynb: Conv2d 6 -> 16 -> 32 -> 32 -> 32, ConvTranspose2d 32 -> 32 -> 16 -> 1,
+# all 3x3 stride 2 (csrc/conv2d_s2_f32.hip); planes up to 128 wide on the wide side
+# ------------------------------------------------------------------------------------------------
+def s2_out(side):
+    """Side of a 3x3 stride-2 Conv2d's output."""
+    return (side - 3) // 2 + 1
+
+
+def _s2_y_shape(n, co, h, w):
+    return (n, co, max(s2_out(h), 0), max(s2_out(w), 0))
+
+
+def conv2d_s2_counts_fwd_f32(history, flow_pred, horizon, weight, bias):
+    """relu(conv2d(cat(normalise(history), normalise(flow_pred)[:, None], horizon plane), weight, stride=2) + bias): history
+    [N, 4, H, W] and flow_pred [N, H, W] as int16 or f32 counts, horizon [N] f32 -> [N, 16, (H-3)//2+1, (W-3)//2+1]."""
+    who = "conv2d_s2_counts_fwd_f32"
+    n, h, w = _check_counts(who, history, flow_pred, horizon)
+    co = weight.shape[0]
+    _shape_check(tuple(weight.shape) == (co, 6, 3, 3), who, f"weight [C_out, 6, 3, 3] expected, got {tuple(weight.shape)}")
+    _shape_check(bias is not None and tuple(bias.shape) == (co,), who, f"bias [{co}] expected")
+    require_cuda(weight, bias)
+    _f32_contig(weight, bias)
+    y = torch.empty(_s2_y_shape(n, co, h, w), dtype=torch.float32, device=history.device)
+    check(get_lib().pv_conv2d_s2_counts_fwd_f32(ptr(history), int(history.dtype == torch.int16), ptr(flow_pred),
+                                                int(flow_pred.dtype == torch.int16), ptr(horizon), ptr(weight), ptr(bias),
+                                                ptr(y), n, h, w, co, current_stream_ptr()), "pv_conv2d_s2_counts_fwd_f32")
+    return y
+
+
+def conv2d_s2_counts_bwd_weight_f32(history, flow_pred, horizon, dy, weight_shape):
+    """(dw [16, 6, 3, 3], dbias) of conv2d_s2_counts_fwd_f32's conv from its pre-activation gradient dy."""
+    who = "conv2d_s2_counts_bwd_weight_f32"
+    n, h, w = _check_counts(who, history, flow_pred, horizon)
+    co = weight_shape[0]
+    y_shape = _s2_y_shape(n, co, h, w)
+    _shape_check(tuple(weight_shape) == (co, 6, 3, 3) and tuple(dy.shape) == y_shape, who,
+                 f"weight {(co, 6, 3, 3)} and dy {y_shape} expected, got {tuple(weight_shape)} / {tuple(dy.shape)}")
+    require_cuda(dy)
+    _f32_contig(dy)
+    ws, nbytes = _wgrad_ws("conv2d_s2", history.device, n, 6, co, h, w)
+    dw, db = _grads_out(weight_shape, history.device)
+    check(get_lib().pv_conv2d_s2_counts_bwd_weight_f32(ptr(history), int(history.dtype == torch.int16), ptr(flow_pred),
+                                                       int(flow_pred.dtype == torch.int16), ptr(horizon), ptr(dy), ptr(dw),
+                                                       ptr(db), n, h, w, co, ptr(ws), nbytes, current_stream_ptr()),
+          "pv_conv2d_s2_counts_bwd_weight_f32")
+    return dw, db
+
+
+def conv2d_s2_fwd_f32(x, weight, bias, relu=True):
+    """conv2d(x, weight, stride=2) + bias (+ ReLU) for (C_in, C_out) = (16, 32) or (32, 32), W <= 128."""
+    who = "conv2d_s2_fwd_f32"
+    _check_ae(who, x.shape, weight.shape)
+    n, ci, h, w = x.shape
+    co = weight.shape[0]
+    _check_bias(who, bias, co)
+    require_cuda(x, weight, bias)
+    _f32_contig(x, weight, bias)
+    y = torch.empty(_s2_y_shape(n, co, h, w), dtype=torch.float32, device=x.device)
+    check(get_lib().pv_conv2d_s2_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, int(relu),
+                                         current_stream_ptr()), "pv_conv2d_s2_fwd_f32")
+    return y
+
+
+def conv2d_s2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of conv2d_s2_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None).  The rows and
+    columns of x the forward never reads get exactly 0."""
+    who = "conv2d_s2_bwd_data_f32"
+    _check_ae(who, x_shape, weight.shape)
+    n, ci, h, w = x_shape
+    co = weight.shape[0]
+    y_shape = _s2_y_shape(n, co, h, w)
+    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
+                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
+    require_cuda(dy, dy_gate, weight, x_gate)
+    _f32_contig(dy, dy_gate, weight, x_gate)
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
+    check(get_lib().pv_conv2d_s2_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci, co, h, w,
+                                              current_stream_ptr()), "pv_conv2d_s2_bwd_data_f32")
+    return dx
+
+
+def conv2d_s2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw, dbias) of conv2d_s2_fwd_f32; deterministic (fixed slabs summed in order)."""
+    who = "conv2d_s2_bwd_weight_f32"
+    _check_ae(who, x.shape, weight_shape)
+    n, ci, h, w = x.shape
+    co = weight_shape[0]
+    y_shape = _s2_y_shape(n, co, h, w)
+    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
+                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    require_cuda(x, dy, dy_gate)
+    _f32_contig(x, dy, dy_gate)
+    ws, nbytes = _wgrad_ws("conv2d_s2", x.device, n, ci, co, h, w)
+    dw, db = _grads_out(weight_shape, x.device)
+    check(get_lib().pv_conv2d_s2_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, ptr(ws),
+                                                nbytes, current_stream_ptr()), "pv_conv2d_s2_bwd_weight_f32")
+    return dw, db
+
+
+def convt2d_s2_fwd_f32(x, weight, bias, relu=True):
+    """conv_transpose2d(x, weight, stride=2) + bias (+ ReLU): x [N, C_in, H, W], weight [C_in, C_out, 3, 3] -> [N, C_out,
+    2H+1, 2W+1] for (C_in, C_out) = (32, 32), (32, 16) or (16, 1)."""
+    who = "convt2d_s2_fwd_f32"
+    _check_aet(who, x.shape, weight.shape)
+    n, ci, h, w = x.shape
+    co = weight.shape[1]
+    _check_bias(who, bias, co)
+    require_cuda(x, weight, bias)
+    _f32_contig(x, weight, bias)
+    y = torch.empty((n, co, 2 * h + 1, 2 * w + 1), dtype=torch.float32, device=x.device)
+    check(get_lib().pv_convt2d_s2_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, int(relu),
+                                          current_stream_ptr()), "pv_convt2d_s2_fwd_f32")
+    return y
+
+
+def convt2d_s2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of convt2d_s2_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
+    who = "convt2d_s2_bwd_data_f32"
+    _check_aet(who, x_shape, weight.shape)
+    n, ci, h, w = x_shape
+    co = weight.shape[1]
+    y_shape = (n, co, 2 * h + 1, 2 * w + 1)
+    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
+                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
+    require_cuda(dy, dy_gate, weight, x_gate)
+    _f32_contig(dy, dy_gate, weight, x_gate)
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
+    check(get_lib().pv_convt2d_s2_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci, co, h, w,
+                                               current_stream_ptr()), "pv_convt2d_s2_bwd_data_f32")
+    return dx
+
+
+def convt2d_s2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw [C_in, C_out, 3, 3], dbias [C_out]) of convt2d_s2_fwd_f32; deterministic (fixed slabs summed in order)."""
+    who = "convt2d_s2_bwd_weight_f32"
+    _check_aet(who, x.shape, weight_shape)
+    n, ci, h, w = x.shape
+    co = weight_shape[1]
+    y_shape = (n, co, 2 * h + 1, 2 * w + 1)
+    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
+                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    require_cuda(x, dy, dy_gate)
+    _f32_contig(x, dy, dy_gate)
+    ws, nbytes = _wgrad_ws("convt2d_s2", x.device, n, ci, co, h, w)
+    dw = torch.empty(tuple(weight_shape), dtype=torch.float32, device=x.device)
+    db = torch.empty((co,), dtype=torch.float32, device=x.device)
+    check(get_lib().pv_convt2d_s2_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, ptr(ws),
+                                                 nbytes, current_stream_ptr()), "pv_convt2d_s2_bwd_weight_f32")
+    return dw, db
+
+
 def maxpool3d_fwd_f32(x, kernel=3, stride=None, padding=0):
     require_cuda(x)
     b, c, t, h, w = x.shape
