@@ -83,6 +83,41 @@ _PFB = ctypes.POINTER(FarnebackParams)
 _PCD = ctypes.POINTER(Conv3dDims)
 _PCG = ctypes.POINTER(Conv3dGeom)
 _PI32 = ctypes.POINTER(c_i32)
+
+# The exact-f32 Conv2d / ConvTranspose2d families (hip_ops.py's _ConvFamily / _PoolFamily records) share their argument lists:
+# each is spelled once here.  _DIMS5 is (n, c_in, c_out, h, w); every launch ends with the stream.
+_DIMS5 = [c_i32] * 5
+_WORKSPACE = [c_vp, c_sz]                                            # workspace, workspace_bytes
+_CONV_FWD = [c_vp] * 4 + _DIMS5 + [c_i32, c_vp]                      # x, weight, bias, y, dims, relu
+_CONV_BWD_DATA = [c_vp] * 5 + _DIMS5 + [c_vp]                        # dy, dy_gate | codes, weight, dx, x_gate, dims
+_CONV_BWD_WEIGHT = [c_vp] * 5 + _DIMS5 + _WORKSPACE + [c_vp]         # x, dy, dy_gate | codes, dw, dbias, dims
+_POOL_FWD = [c_vp] * 5 + _DIMS5                                      # x, weight, bias, y, codes, dims (+ workspace) + stream
+_WS_QUERY5 = _DIMS5 + [ctypes.POINTER(c_sz)]
+_WS_QUERY6 = _DIMS5 + [c_i32, ctypes.POINTER(c_sz)]                  # ... + pooled
+_COUNTS = [c_vp, c_i32, c_vp, c_i32, c_vp]                           # history, is_i16, flow prediction, is_i16, horizon
+_COUNTS_FWD = _COUNTS + [c_vp] * 3 + [c_i32] * 4 + [c_vp]            # weight, bias, y, (n, h, w, c_out)
+_COUNTS_BWD_WEIGHT = _COUNTS + [c_vp] * 3 + [c_i32] * 4 + _WORKSPACE + [c_vp]      # dy, dw, dbias, (n, h, w, c_out)
+_MSE_NORM_TAIL = [c_vp, c_vp] + _WORKSPACE + [c_vp]                  # loss, grad, workspace, stream
+
+
+def _conv2d_family(stem, ws_query):
+    return {f"pv_{stem}_fwd_f32": _CONV_FWD, f"pv_{stem}_bwd_data_f32": _CONV_BWD_DATA,
+            f"pv_{stem}_bwd_weight_workspace_bytes": ws_query, f"pv_{stem}_bwd_weight_f32": _CONV_BWD_WEIGHT}
+
+
+def _conv2d_pool_family(stem, fwd_workspace):
+    """The weight gradient uses the plain family's workspace query."""
+    out = {f"pv_{stem}_pool_fwd_f32": _POOL_FWD + (_WORKSPACE if fwd_workspace else []) + [c_vp],
+           f"pv_{stem}_pool_bwd_data_f32": _CONV_BWD_DATA, f"pv_{stem}_pool_bwd_weight_f32": _CONV_BWD_WEIGHT}
+    if fwd_workspace:
+        out[f"pv_{stem}_pool_fwd_workspace_bytes"] = _WS_QUERY5
+    return out
+
+
+def _conv2d_counts_family(stem):
+    return {f"pv_{stem}_counts_fwd_f32": _COUNTS_FWD, f"pv_{stem}_counts_bwd_weight_f32": _COUNTS_BWD_WEIGHT}
+
+
 SIGNATURES = {
     "pv_abi_version": [],
     "pv_last_error": [],
@@ -149,54 +184,24 @@ SIGNATURES = {
     "pv_conv3d_general_bwd_weight_workspace_bytes": [_PCG, ctypes.POINTER(c_sz)],
     "pv_conv3d_general_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, _PCG, c_vp, c_sz, c_vp],
     "pv_conv2d_coords_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d_bwd_weight_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)],
-    "pv_conv2d_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
     "pv_conv2d_coords_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz,
                                         c_vp],
+    **_conv2d_family("conv2d", _WS_QUERY5),
     "pv_conv2d144_sat_pool_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                       c_vp],
-    "pv_conv2d144_pool_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d144_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d144_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d144_pool_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d144_bwd_weight_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)],
-    "pv_conv2d144_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
-    "pv_conv2d144_pool_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz,
-                                         c_vp],
     "pv_conv2d144_sat_pool_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32,
                                              c_i32, c_vp, c_sz, c_vp],
-    "pv_conv2d_ae_counts_fwd_f32": [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d_ae_counts_bwd_weight_f32": [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32,
-                                           c_vp, c_sz, c_vp],
-    "pv_conv2d_ae_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d_ae_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d_ae_bwd_weight_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)],
-    "pv_conv2d_ae_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
-    "pv_conv2d_ae_pool_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
-    "pv_conv2d_ae_pool_fwd_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)],
-    "pv_conv2d_ae_pool_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d_ae_pool_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz,
-                                         c_vp],
-    "pv_convt2d_ae_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_convt2d_ae_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_convt2d_ae_bwd_weight_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)],
-    "pv_convt2d_ae_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
-    "pv_mse_crop_norm_f32": [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp],
-    "pv_mse_window_norm_f32": [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz,
-                               c_vp],
-    "pv_conv2d_s2_counts_fwd_f32": [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d_s2_counts_bwd_weight_f32": [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32,
-                                           c_vp, c_sz, c_vp],
-    "pv_conv2d_s2_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d_s2_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_conv2d_s2_bwd_weight_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)],
-    "pv_conv2d_s2_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
-    "pv_convt2d_s2_fwd_f32": [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_convt2d_s2_bwd_data_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp],
-    "pv_convt2d_s2_bwd_weight_workspace_bytes": [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)],
-    "pv_convt2d_s2_bwd_weight_f32": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp],
+    **_conv2d_family("conv2d144", _WS_QUERY6),
+    **_conv2d_pool_family("conv2d144", fwd_workspace=False),
+    **_conv2d_family("conv2d_ae", _WS_QUERY6),
+    **_conv2d_pool_family("conv2d_ae", fwd_workspace=True),
+    **_conv2d_counts_family("conv2d_ae"),
+    **_conv2d_family("convt2d_ae", _WS_QUERY5),
+    "pv_mse_crop_norm_f32": [c_vp, c_vp] + [c_i32] * 6 + _MSE_NORM_TAIL,
+    "pv_mse_window_norm_f32": [c_vp, c_vp] + [c_i32] * 8 + _MSE_NORM_TAIL,     # ... + row0, col0
+    **_conv2d_family("conv2d_s2", _WS_QUERY5),
+    **_conv2d_counts_family("conv2d_s2"),
+    **_conv2d_family("convt2d_s2", _WS_QUERY5),
     "pv_maxpool3d_fwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_maxpool3d_bwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_mse_loss_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp],

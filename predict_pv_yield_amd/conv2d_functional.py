@@ -37,7 +37,8 @@ import torch
 
 from . import hip_ops as K
 
-# entry points of the plain (unpooled) conv: (forward, data gradient, weight gradient)
+# entry points of the plain (unpooled) conv: (forward, data gradient, weight gradient); each is a one-line call into the one
+# implementation of its pass in hip_ops.py, with the family's record (a new family is added there, then named here)
 CONV2D_OPS = (K.conv2d_fwd_f32, K.conv2d_bwd_data_f32, K.conv2d_bwd_weight_f32)
 CONV2D144_OPS = (K.conv2d144_fwd_f32, K.conv2d144_bwd_data_f32, K.conv2d144_bwd_weight_f32)
 CONV2D_AE_OPS = (K.conv2d_ae_fwd_f32, K.conv2d_ae_bwd_data_f32, K.conv2d_ae_bwd_weight_f32)
@@ -215,36 +216,25 @@ class CountsConvReLU(torch.autograd.Function):
         return None, None, None, None, dw, db, None
 
 
-class MseCropNorm(torch.autograd.Function):
-    """F.mse_loss(y_hat, normalise(target)[..., 8:-8, 8:-8]): y_hat [N, P, Q] f32, target [N, P + 16, Q + 16] raw counts;
-    the gradient 2 (y_hat - y) / count is produced in the same pass."""
+class MseNorm(torch.autograd.Function):
+    """F.mse_loss(y_hat, normalise(target)[window]): y_hat [N, P, Q] f32, target raw counts; the gradient 2 (y_hat - y) / count
+    is produced in the same pass.  window None: target [N, P + 16, Q + 16] and the crop [..., 8:-8, 8:-8], whose entry point
+    checks that the sides match; (row0, col0): target [N, T, U] and [..., row0:row0 + P, col0:col0 + Q]."""
 
     @staticmethod
-    def forward(ctx, y_hat, target):
-        out, grad = K.mse_crop_norm_f32(y_hat.contiguous(), target.contiguous(), need_grad=True)
+    def forward(ctx, y_hat, target, window):
+        y_hat, target = y_hat.contiguous(), target.contiguous()
+        if window is None:
+            out, grad = K.mse_crop_norm_f32(y_hat, target, need_grad=True)
+        else:
+            out, grad = K.mse_window_norm_f32(y_hat, target, *window, need_grad=True)
         ctx.save_for_backward(grad)
         return out[0]
 
     @staticmethod
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
-        return grad * g, None
-
-
-class MseWindowNorm(torch.autograd.Function):
-    """F.mse_loss(y_hat, normalise(target)[..., row0:row0 + P, col0:col0 + Q]): y_hat [N, P, Q] f32, target [N, T, U] raw
-    counts; the gradient 2 (y_hat - y) / count is produced in the same pass."""
-
-    @staticmethod
-    def forward(ctx, y_hat, target, row0, col0):
-        out, grad = K.mse_window_norm_f32(y_hat.contiguous(), target.contiguous(), row0, col0, need_grad=True)
-        ctx.save_for_backward(grad)
-        return out[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return grad * g, None, None, None
+        return grad * g, None, None
 
 
 def counts_conv_relu(history, flow_pred, horizon, weight, bias):
@@ -269,7 +259,7 @@ def conv_transpose2d_relu(x, weight, bias, relu=True, x_is_relu_output=False):
 
 def mse_crop_norm(y_hat, target):
     """F.mse_loss(y_hat, normalise_images_in_model(target)[..., 8:-8, 8:-8]) of 16_maxpool.ipynb:13805-13809."""
-    return MseCropNorm.apply(y_hat, target)
+    return MseNorm.apply(y_hat, target, None)
 
 
 def nb16_autoencoder_f32(history, flow_pred, horizon, enc, dec):
@@ -307,7 +297,7 @@ def conv_transpose2d_s2_relu(x, weight, bias, relu=True, x_is_relu_output=False)
 def mse_window_norm(y_hat, target, row0=0, col0=0):
     """F.mse_loss(y_hat, normalise_images_in_model(target)[..., row0:row0 + P, col0:col0 + Q]); (0, 0) with a target one
     larger than y_hat is y[..., :-1, :-1] of 15_int16.ipynb:13783-13788."""
-    return MseWindowNorm.apply(y_hat, target, int(row0), int(col0))
+    return MseNorm.apply(y_hat, target, (int(row0), int(col0)))
 
 
 def nb15_autoencoder_f32(history, flow_pred, horizon, conv):

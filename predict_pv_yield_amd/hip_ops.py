@@ -5,7 +5,7 @@ HIP stream.  torch is used for device memory and streams only.  There is no CPU 
 or a missing library raise.
 """
 import ctypes
-from typing import Optional, Sequence
+from typing import Callable, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -1069,8 +1069,15 @@ def conv3d_general_bwd_weight_f32(x, dy, y_mask, weight_shape, stride=1, padding
 
 
 # ------------------------------------------------------------------------------------------------
-# Conv2d 3x3 "valid", exact f32: conv2d_* for experiments/002_cnn_processes_single_sat_image_then_rnn.py (17 / 32 -> 32 / 4
-# channels), conv2d144_* for experiments/001_CNN_concat_all_timesteps_as_channels.py (144 -> 144, + MaxPool2d(3))
+# Conv2d / ConvTranspose2d 3x3, exact f32, for four models: experiments/002 (conv2d_*, 17 / 32 -> 32 / 4 channels),
+# experiments/001 (conv2d144_*, 144 -> 144, + MaxPool2d(3)), notebooks/16_maxpool.ipynb (conv2d_ae_* / convt2d_ae_*, + pool,
+# cropped normalised MSE) and notebooks/14, 15 (conv2d_s2_* / convt2d_s2_*, stride 2, windowed normalised MSE).
+#
+# A family of entry points is described once, by a _ConvFamily record (its plain forward / data gradient / weight gradient)
+# and, where it has them, a _PoolFamily record (the same three passes with MaxPool2d(3) fused).  _conv_fwd, _conv_bwd_data,
+# _conv_bwd_weight, _pool_*, _counts_* and _mse_norm are the only implementations; the public functions below them are
+# one-line calls.  A new family is a new record plus its one-line functions, and its argtypes from the shared lists of
+# _lib.py; a new pass is written once here.  tests/test_conv2d_glue_cpu.py pins what each wrapper hands to the C ABI.
 # ------------------------------------------------------------------------------------------------
 C144 = 144
 
@@ -1086,9 +1093,10 @@ def _u8_contig(who, codes):
         raise TypeError(f"{who}: codes must be a contiguous uint8 tensor")
 
 
-def _shape_check(ok, who, msg):
-    if not ok:
-        raise ValueError(f"{who}: {msg}")
+def _counts_contig(who, *ts):
+    for t in ts:
+        if t.dtype not in (torch.int16, torch.float32) or not t.is_contiguous():
+            raise TypeError(f"{who}: counts must be contiguous int16 or float32 tensors, got {t.dtype}")
 
 
 def _check_bias(who, bias, c_out):
@@ -1097,41 +1105,126 @@ def _check_bias(who, bias, c_out):
 
 
 def _check_xy_coords(who, x_coords, y_coords, b, h, w):
-    _shape_check(tuple(x_coords.shape) == (b, w) and tuple(y_coords.shape) == (b, h), who,
-                 f"x_coords [{b}, {w}] and y_coords [{b}, {h}] expected, got {tuple(x_coords.shape)} / {tuple(y_coords.shape)}")
+    if tuple(x_coords.shape) != (b, w) or tuple(y_coords.shape) != (b, h):
+        raise ValueError(f"{who}: x_coords [{b}, {w}] and y_coords [{b}, {h}] expected, got {tuple(x_coords.shape)} / "
+                         f"{tuple(y_coords.shape)}")
 
 
 def _check_coords(who, sat, x_coords, y_coords, t_per_example):
     n, h, w, c = sat.shape
-    _shape_check(c == 12 and t_per_example > 0 and n % t_per_example == 0, who,
-                 f"sat [N, H, W, 12] with N a multiple of t_per_example={t_per_example}, got {tuple(sat.shape)}")
+    if not (c == 12 and t_per_example > 0 and n % t_per_example == 0):
+        raise ValueError(f"{who}: sat [N, H, W, 12] with N a multiple of t_per_example={t_per_example}, got "
+                         f"{tuple(sat.shape)}")
     _check_xy_coords(who, x_coords, y_coords, n // t_per_example, h, w)
 
 
 def _check_sat001(who, sat, x_coords, y_coords, n_frames):
-    _shape_check(sat.dim() == 5 and sat.shape[4] == 1, who, f"sat_data [B, T, H, W, 1] expected, got {tuple(sat.shape)}")
+    if not (sat.dim() == 5 and sat.shape[4] == 1):
+        raise ValueError(f"{who}: sat_data [B, T, H, W, 1] expected, got {tuple(sat.shape)}")
     b, t, h, w, _ = sat.shape
-    _shape_check(0 < n_frames <= t, who, f"n_frames={n_frames} must lie in 1..T={t}")
-    _shape_check(h >= 5 and w >= 5, who, f"images of at least 5 x 5 expected, got {h} x {w}")
+    if not 0 < n_frames <= t:
+        raise ValueError(f"{who}: n_frames={n_frames} must lie in 1..T={t}")
+    if h < 5 or w < 5:
+        raise ValueError(f"{who}: images of at least 5 x 5 expected, got {h} x {w}")
     _check_xy_coords(who, x_coords, y_coords, b, h, w)
     return b, t, h, w
 
 
+def _check_counts(who, history, flow_pred, horizon):
+    if not (history.dim() == 4 and history.shape[1] == 4):
+        raise ValueError(f"{who}: history [N, 4, H, W] expected, got {tuple(history.shape)}")
+    n, _, h, w = history.shape
+    if tuple(flow_pred.shape) != (n, h, w) or tuple(horizon.shape) != (n,):
+        raise ValueError(f"{who}: flow prediction [{n}, {h}, {w}] and horizon [{n}] expected, got "
+                         f"{tuple(flow_pred.shape)} / {tuple(horizon.shape)}")
+    require_cuda(history, flow_pred, horizon)
+    _counts_contig(who, history, flow_pred)
+    _f32_contig(horizon)
+    return n, h, w
+
+
 def _check_c32(who, x_shape, weight_shape):
     n, ci, h, w = x_shape
-    _shape_check(len(weight_shape) == 4 and tuple(weight_shape[1:]) == (ci, 3, 3), who,
-                 f"weight [C_out, {ci}, 3, 3] expected for x {tuple(x_shape)}, got {tuple(weight_shape)}")
+    if not (len(weight_shape) == 4 and tuple(weight_shape[1:]) == (ci, 3, 3)):
+        raise ValueError(f"{who}: weight [C_out, {ci}, 3, 3] expected for x {tuple(x_shape)}, got {tuple(weight_shape)}")
 
 
 def _check_c144(who, x_shape, weight_shape, pooled=False):
-    _shape_check(len(x_shape) == 4 and x_shape[1] == C144, who, f"x [N, 144, H, W] expected, got {tuple(x_shape)}")
-    _shape_check(tuple(weight_shape) == (C144, C144, 3, 3), who, f"weight [144, 144, 3, 3] expected, got {tuple(weight_shape)}")
+    if not (len(x_shape) == 4 and x_shape[1] == C144):
+        raise ValueError(f"{who}: x [N, 144, H, W] expected, got {tuple(x_shape)}")
+    if tuple(weight_shape) != (C144, C144, 3, 3):
+        raise ValueError(f"{who}: weight [144, 144, 3, 3] expected, got {tuple(weight_shape)}")
     lo = 5 if pooled else 3
-    _shape_check(x_shape[2] >= lo and x_shape[3] >= lo, who, f"images of at least {lo} x {lo} expected, got {tuple(x_shape)}")
+    if x_shape[2] < lo or x_shape[3] < lo:
+        raise ValueError(f"{who}: images of at least {lo} x {lo} expected, got {tuple(x_shape)}")
 
 
-def _pooled_shape(n, h, w):
-    return (n, C144, (h - 2) // 3, (w - 2) // 3)
+def _check_c144_pooled(who, x_shape, weight_shape):
+    _check_c144(who, x_shape, weight_shape, True)
+
+
+def _check_ae(who, x_shape, weight_shape):
+    if not (len(x_shape) == 4 and len(weight_shape) == 4 and tuple(weight_shape[1:]) == (x_shape[1], 3, 3)):
+        raise ValueError(f"{who}: x [N, C_in, H, W] and weight [C_out, C_in, 3, 3] expected, got {tuple(x_shape)} / "
+                         f"{tuple(weight_shape)}")
+
+
+def _check_aet(who, x_shape, weight_shape):
+    if not (len(x_shape) == 4 and len(weight_shape) == 4 and weight_shape[0] == x_shape[1]
+            and tuple(weight_shape[2:]) == (3, 3)):
+        raise ValueError(f"{who}: x [N, C_in, H, W] and weight [C_in, C_out, 3, 3] expected, got {tuple(x_shape)} / "
+                         f"{tuple(weight_shape)}")
+
+
+def _pooled_shape(n, c, h, w):
+    return (n, c, (h - 2) // 3, (w - 2) // 3)
+
+
+def _pooled_shape_c(n, c, h, w):
+    if h < 5 or w < 5:
+        raise ValueError(f"images of at least 5 x 5 expected (one whole 3x3 pool window after the 3x3 conv), got {h} x {w}")
+    return _pooled_shape(n, c, h, w)
+
+
+def s2_out(side):
+    """Side of a 3x3 stride-2 Conv2d's output."""
+    return (side - 3) // 2 + 1
+
+
+class _ConvFamily(NamedTuple):
+    """One family of plain entry points: pv_{stem}_{fwd,bwd_data,bwd_weight}_f32 and pv_{stem}_bwd_weight_workspace_bytes."""
+    stem: str                       # also names the weight gradient's workspace, "{stem}_wgrad" (a captured graph pins by key)
+    check_channels: Callable        # (who, x_shape, weight_shape): raises ValueError
+    out_hw: Callable                # (h, w) of the input -> (h, w) of the output
+    c_out_axis: int = 0             # of the weight: 0 in Conv2d's [C_out, C_in, 3, 3], 1 in ConvTranspose2d's [C_in, C_out, ..]
+    ws_args: tuple = ()             # the workspace query's arguments after (n, c_in, c_out, h, w): the "pooled" flag, 0 here
+
+
+class _PoolFamily(NamedTuple):
+    """The conv + MaxPool2d(3) passes of a family, pv_{stem}_pool_{fwd,bwd_data,bwd_weight}_f32; the weight gradient takes
+    the plain family's workspace, queried with the "pooled" flag 1."""
+    stem: str
+    check_channels: Callable        # as _ConvFamily's; the pooled passes need a bias
+    pooled_shape: Callable          # (n, c_out, h, w) -> shape of the pooled output
+    fwd_workspace: bool             # the forward has pv_{stem}_pool_fwd_workspace_bytes and takes (workspace, bytes)
+
+
+def _valid_hw(h, w):
+    return h - 2, w - 2         # not clamped: a plane under 3 rows fails in torch.empty
+
+
+def _s2_hw(h, w):
+    return max(s2_out(h), 0), max(s2_out(w), 0)
+
+
+_CONV2D = _ConvFamily("conv2d", _check_c32, _valid_hw)
+_CONV2D144 = _ConvFamily("conv2d144", _check_c144, _valid_hw, ws_args=(0,))
+_CONV2D_AE = _ConvFamily("conv2d_ae", _check_ae, _valid_hw, ws_args=(0,))
+_CONVT2D_AE = _ConvFamily("convt2d_ae", _check_aet, lambda h, w: (h + 2, w + 2), c_out_axis=1)
+_CONV2D_S2 = _ConvFamily("conv2d_s2", _check_ae, _s2_hw)
+_CONVT2D_S2 = _ConvFamily("convt2d_s2", _check_aet, lambda h, w: (2 * h + 1, 2 * w + 1), c_out_axis=1)
+_CONV2D144_POOL = _PoolFamily("conv2d144", _check_c144_pooled, _pooled_shape, False)
+_CONV2D_AE_POOL = _PoolFamily("conv2d_ae", _check_ae, _pooled_shape_c, True)
 
 
 def _wgrad_ws(family, device, *dims):
@@ -1143,90 +1236,202 @@ def _wgrad_ws(family, device, *dims):
     return _workspace(f"{family}_wgrad", nbytes.value, device), nbytes.value
 
 
-def _grads_out(weight_shape, device):
+def _grads_out(weight_shape, c_out, device):
     return (torch.empty(tuple(weight_shape), dtype=torch.float32, device=device),
-            torch.empty((weight_shape[0],), dtype=torch.float32, device=device))
+            torch.empty((c_out,), dtype=torch.float32, device=device))
 
 
-# the plain passes of the three families ("conv2d", "conv2d144", "conv2d_ae"): check_channels(who, x_shape, weight_shape) is the family's
-# channel-count check, the rest is the same for all
-def _conv_fwd(family, check_channels, x, weight, bias, relu):
-    who = f"{family}_fwd_f32"
-    check_channels(who, x.shape, weight.shape)
+def _check_dy(who, fam, dy, dy_gate, n, co, h, w):
+    y_shape = (n, co, *fam.out_hw(h, w))
+    if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
+        raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+
+
+# ---- the plain passes ----
+def _conv_fwd(fam, x, weight, bias, relu):
+    who = f"{fam.stem}_fwd_f32"
+    fam.check_channels(who, x.shape, weight.shape)
     n, ci, h, w = x.shape
-    co = weight.shape[0]
+    co = weight.shape[fam.c_out_axis]
     _check_bias(who, bias, co)
     require_cuda(x, weight, bias)
     _f32_contig(x, weight, bias)
-    y = torch.empty((n, co, h - 2, w - 2), dtype=torch.float32, device=x.device)
+    y = torch.empty((n, co, *fam.out_hw(h, w)), dtype=torch.float32, device=x.device)
     check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, int(relu),
                                           current_stream_ptr()), "pv_" + who)
     return y
 
 
-def _conv_bwd_data(family, check_channels, dy, dy_gate, weight, x_gate, x_shape):
-    who = f"{family}_bwd_data_f32"
-    check_channels(who, x_shape, weight.shape)
+def _conv_bwd_data(fam, dy, dy_gate, weight, x_gate, x_shape):
+    who = f"{fam.stem}_bwd_data_f32"
+    fam.check_channels(who, x_shape, weight.shape)
     n, ci, h, w = x_shape
-    y_shape = (n, weight.shape[0], h - 2, w - 2)
-    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
-                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
+    co = weight.shape[fam.c_out_axis]
+    _check_dy(who, fam, dy, dy_gate, n, co, h, w)
+    if x_gate is not None and tuple(x_gate.shape) != tuple(x_shape):
+        raise ValueError(f"{who}: x_gate {tuple(x_shape)} expected")
     require_cuda(dy, dy_gate, weight, x_gate)
     _f32_contig(dy, dy_gate, weight, x_gate)
     dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
-    check(getattr(get_lib(), "pv_" + who)(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci, weight.shape[0],
-                                          h, w, current_stream_ptr()), "pv_" + who)
+    check(getattr(get_lib(), "pv_" + who)(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci, co, h, w,
+                                          current_stream_ptr()), "pv_" + who)
     return dx
 
 
-def _conv_bwd_weight(family, check_channels, x, dy, dy_gate, weight_shape, ws_args=()):
-    """ws_args: the workspace query's arguments after (n, c_in, c_out, h, w)."""
-    who = f"{family}_bwd_weight_f32"
-    check_channels(who, x.shape, weight_shape)
+def _conv_bwd_weight(fam, x, dy, dy_gate, weight_shape):
+    who = f"{fam.stem}_bwd_weight_f32"
+    fam.check_channels(who, x.shape, weight_shape)
     n, ci, h, w = x.shape
-    co = weight_shape[0]
-    y_shape = (n, co, h - 2, w - 2)
-    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
-                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    co = weight_shape[fam.c_out_axis]
+    _check_dy(who, fam, dy, dy_gate, n, co, h, w)
     require_cuda(x, dy, dy_gate)
     _f32_contig(x, dy, dy_gate)
-    ws, nbytes = _wgrad_ws(family, x.device, n, ci, co, h, w, *ws_args)
-    dw, db = _grads_out(weight_shape, x.device)
+    ws, nbytes = _wgrad_ws(fam.stem, x.device, n, ci, co, h, w, *fam.ws_args)
+    dw, db = _grads_out(weight_shape, co, x.device)
     check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, ptr(ws), nbytes,
                                           current_stream_ptr()), "pv_" + who)
     return dw, db
 
 
-def conv2d_coords_fwd_f32(sat, x_coords, y_coords, weight, bias, t_per_example):
-    """relu(conv2d(cat(sat.permute(0, 3, 1, 2), 5 synthesised channels), weight) + bias) with sat [N, H, W, 12],
-    x_coords [N / t, W], y_coords [N / t, H]: the 17-channel input is built inside the kernel.  Returns [N, C_out, H-2, W-2]."""
-    _check_coords("conv2d_coords_fwd_f32", sat, x_coords, y_coords, t_per_example)
-    n, h, w, c = sat.shape
-    _shape_check(weight.dim() == 4 and tuple(weight.shape[1:]) == (17, 3, 3), "conv2d_coords_fwd_f32",
-                 f"weight [C_out, 17, 3, 3] expected, got {tuple(weight.shape)}")
+# ---- conv + MaxPool2d(3): the forward also returns one uint8 code per pooled output, which the gradients take ----
+def _check_pooled(who, pool, dy_pooled, codes, n, co, h, w):
+    p_shape = pool.pooled_shape(n, co, h, w)
+    if tuple(dy_pooled.shape) != p_shape or tuple(codes.shape) != p_shape:
+        raise ValueError(f"{who}: dy_pooled / codes {p_shape} expected, got {tuple(dy_pooled.shape)} / "
+                         f"{tuple(codes.shape)}")
+
+
+def _pool_fwd(pool, x, weight, bias):
+    who = f"{pool.stem}_pool_fwd_f32"
+    pool.check_channels(who, x.shape, weight.shape)
+    n, c, h, w = x.shape
     co = weight.shape[0]
-    _check_bias("conv2d_coords_fwd_f32", bias, co)
-    require_cuda(sat, x_coords, y_coords, weight, bias)
-    _f32_contig(sat, x_coords, y_coords, weight, bias)
-    y = torch.empty((n, co, h - 2, w - 2), dtype=torch.float32, device=sat.device)
-    check(get_lib().pv_conv2d_coords_fwd_f32(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(weight), ptr(bias), ptr(y), n,
-                                             t_per_example, h, w, co, current_stream_ptr()), "pv_conv2d_coords_fwd_f32")
+    if bias is None or tuple(bias.shape) != (co,):
+        raise ValueError(f"{who}: bias [{co}] expected")
+    require_cuda(x, weight, bias)
+    _f32_contig(x, weight, bias)
+    y = torch.empty(pool.pooled_shape(n, co, h, w), dtype=torch.float32, device=x.device)
+    codes = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
+    ws_args = ()
+    if pool.fwd_workspace:
+        query = f"pv_{pool.stem}_pool_fwd_workspace_bytes"
+        nbytes = ctypes.c_size_t(0)
+        check(getattr(get_lib(), query)(n, c, co, h, w, ctypes.byref(nbytes)), query)
+        ws = _workspace(f"{pool.stem}_pool_fwd", nbytes.value, x.device) if nbytes.value else None
+        ws_args = (ptr(ws), nbytes.value)
+    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(codes), n, c, co, h, w, *ws_args,
+                                          current_stream_ptr()), "pv_" + who)
+    return y, codes
+
+
+def _pool_bwd_data(pool, dy_pooled, codes, weight, x_gate, x_shape):
+    who = f"{pool.stem}_pool_bwd_data_f32"
+    pool.check_channels(who, x_shape, weight.shape)
+    n, c, h, w = x_shape
+    co = weight.shape[0]
+    _check_pooled(who, pool, dy_pooled, codes, n, co, h, w)
+    if x_gate is not None and tuple(x_gate.shape) != tuple(x_shape):
+        raise ValueError(f"{who}: x_gate {tuple(x_shape)} expected")
+    require_cuda(dy_pooled, codes, weight, x_gate)
+    _f32_contig(dy_pooled, weight, x_gate)
+    _u8_contig(who, codes)
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy_pooled.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(dy_pooled), ptr(codes), ptr(weight), ptr(dx), ptr(x_gate), n, c, co, h, w,
+                                          current_stream_ptr()), "pv_" + who)
+    return dx
+
+
+def _pool_bwd_weight(pool, x, dy_pooled, codes, weight_shape):
+    who = f"{pool.stem}_pool_bwd_weight_f32"
+    pool.check_channels(who, x.shape, weight_shape)
+    n, c, h, w = x.shape
+    co = weight_shape[0]
+    _check_pooled(who, pool, dy_pooled, codes, n, co, h, w)
+    require_cuda(x, dy_pooled, codes)
+    _f32_contig(x, dy_pooled)
+    _u8_contig(who, codes)
+    ws, nbytes = _wgrad_ws(pool.stem, x.device, n, c, co, h, w, 1)
+    dw, db = _grads_out(weight_shape, co, x.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(dy_pooled), ptr(codes), ptr(dw), ptr(db), n, c, co, h, w, ptr(ws),
+                                          nbytes, current_stream_ptr()), "pv_" + who)
+    return dw, db
+
+
+# ---- the raw-counts first layer of notebooks 14-16, on its plain family's output rule and weight-gradient workspace ----
+def _counts_fwd(fam, history, flow_pred, horizon, weight, bias):
+    who = f"{fam.stem}_counts_fwd_f32"
+    n, h, w = _check_counts(who, history, flow_pred, horizon)
+    co = weight.shape[0]
+    if tuple(weight.shape) != (co, 6, 3, 3):
+        raise ValueError(f"{who}: weight [C_out, 6, 3, 3] expected, got {tuple(weight.shape)}")
+    if bias is None or tuple(bias.shape) != (co,):
+        raise ValueError(f"{who}: bias [{co}] expected")
+    require_cuda(weight, bias)
+    _f32_contig(weight, bias)
+    # clamped, unlike the plain forward: an undersized plane reaches the entry point, which names the smallest it takes
+    oh, ow = fam.out_hw(h, w)
+    y = torch.empty((n, co, max(oh, 0), max(ow, 0)), dtype=torch.float32, device=history.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(history), int(history.dtype == torch.int16), ptr(flow_pred),
+                                          int(flow_pred.dtype == torch.int16), ptr(horizon), ptr(weight), ptr(bias), ptr(y),
+                                          n, h, w, co, current_stream_ptr()), "pv_" + who)
     return y
 
 
-def conv2d_fwd_f32(x, weight, bias, relu=True):
-    return _conv_fwd("conv2d", _check_c32, x, weight, bias, relu)
+def _counts_bwd_weight(fam, history, flow_pred, horizon, dy, weight_shape):
+    who = f"{fam.stem}_counts_bwd_weight_f32"
+    n, h, w = _check_counts(who, history, flow_pred, horizon)
+    co = weight_shape[0]
+    y_shape = (n, co, *fam.out_hw(h, w))
+    if tuple(weight_shape) != (co, 6, 3, 3) or tuple(dy.shape) != y_shape:
+        raise ValueError(f"{who}: weight {(co, 6, 3, 3)} and dy {y_shape} expected, got {tuple(weight_shape)} / "
+                         f"{tuple(dy.shape)}")
+    require_cuda(dy)
+    _f32_contig(dy)
+    ws, nbytes = _wgrad_ws(fam.stem, history.device, n, 6, co, h, w, *fam.ws_args)
+    dw, db = _grads_out(weight_shape, co, history.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(history), int(history.dtype == torch.int16), ptr(flow_pred),
+                                          int(flow_pred.dtype == torch.int16), ptr(horizon), ptr(dy), ptr(dw), ptr(db), n, h,
+                                          w, co, ptr(ws), nbytes, current_stream_ptr()), "pv_" + who)
+    return dw, db
 
 
-def conv2d_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
-    """dx of a 3x3 valid conv; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
-    return _conv_bwd_data("conv2d", _check_c32, dy, dy_gate, weight, x_gate, x_shape)
+def _mse_norm(name, y_hat, target, window, need_grad):
+    """pv_{name}_f32 and the workspace "{name}": window = () for the crop form, whose entry point matches the sides itself,
+    (row0, col0) for the window form."""
+    who = name + "_f32"
+    if not (y_hat.dim() == 3 and target.dim() == 3 and target.shape[0] == y_hat.shape[0]):
+        raise ValueError(f"{who}: y_hat [N, P, Q] and target [N, T, U] expected, got {tuple(y_hat.shape)} / "
+                         f"{tuple(target.shape)}")
+    require_cuda(y_hat, target)
+    _f32_contig(y_hat)
+    _counts_contig(who, target)
+    n, oh, ow = y_hat.shape
+    loss = torch.empty((1,), dtype=torch.float32, device=y_hat.device)
+    grad = torch.empty_like(y_hat) if need_grad else None
+    ws = _workspace(name, 4 * n, y_hat.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(y_hat), ptr(target), int(target.dtype == torch.int16), n, oh, ow,
+                                          target.shape[1], target.shape[2], *map(int, window), ptr(loss), ptr(grad), ptr(ws),
+                                          4 * n, current_stream_ptr()), "pv_" + who)
+    return loss, grad
 
 
-def conv2d_bwd_weight_f32(x, dy, dy_gate, weight_shape):
-    """(dw, dbias) of a 3x3 valid conv; deterministic (fixed slab split over images, slabs summed in order)."""
-    return _conv_bwd_weight("conv2d", _check_c32, x, dy, dy_gate, weight_shape)
+# ---- experiments/002_cnn_processes_single_sat_image_then_rnn.py (csrc/conv2d_f32.hip) ----
+def conv2d_coords_fwd_f32(sat, x_coords, y_coords, weight, bias, t_per_example):
+    """relu(conv2d(cat(sat.permute(0, 3, 1, 2), 5 synthesised channels), weight) + bias) with sat [N, H, W, 12],
+    x_coords [N / t, W], y_coords [N / t, H]: the 17-channel input is built inside the kernel.  Returns [N, C_out, H-2, W-2]."""
+    who = "conv2d_coords_fwd_f32"
+    _check_coords(who, sat, x_coords, y_coords, t_per_example)
+    n, h, w, c = sat.shape
+    if not (weight.dim() == 4 and tuple(weight.shape[1:]) == (17, 3, 3)):
+        raise ValueError(f"{who}: weight [C_out, 17, 3, 3] expected, got {tuple(weight.shape)}")
+    co = weight.shape[0]
+    _check_bias(who, bias, co)
+    require_cuda(sat, x_coords, y_coords, weight, bias)
+    _f32_contig(sat, x_coords, y_coords, weight, bias)
+    y = torch.empty((n, co, h - 2, w - 2), dtype=torch.float32, device=sat.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(weight), ptr(bias), ptr(y), n,
+                                          t_per_example, h, w, co, current_stream_ptr()), "pv_" + who)
+    return y
 
 
 def conv2d_coords_bwd_weight_f32(sat, x_coords, y_coords, dy, t_per_example, weight_shape):
@@ -1235,515 +1440,212 @@ def conv2d_coords_bwd_weight_f32(sat, x_coords, y_coords, dy, t_per_example, wei
     _check_coords(who, sat, x_coords, y_coords, t_per_example)
     n, h, w, _ = sat.shape
     co = weight_shape[0]
-    _shape_check(tuple(weight_shape) == (co, 17, 3, 3) and tuple(dy.shape) == (n, co, h - 2, w - 2), who,
-                 f"weight {(co, 17, 3, 3)} and dy {(n, co, h - 2, w - 2)} expected, got {tuple(weight_shape)} / "
-                 f"{tuple(dy.shape)}")
+    if tuple(weight_shape) != (co, 17, 3, 3) or tuple(dy.shape) != (n, co, h - 2, w - 2):
+        raise ValueError(f"{who}: weight {(co, 17, 3, 3)} and dy {(n, co, h - 2, w - 2)} expected, got "
+                         f"{tuple(weight_shape)} / {tuple(dy.shape)}")
     require_cuda(sat, x_coords, y_coords, dy)
     _f32_contig(sat, x_coords, y_coords, dy)
     ws, nbytes = _wgrad_ws("conv2d", sat.device, n, 17, co, h, w)
-    dw, db = _grads_out(weight_shape, sat.device)
-    check(get_lib().pv_conv2d_coords_bwd_weight_f32(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(dy), ptr(dw), ptr(db), n,
-                                                    t_per_example, h, w, co, ptr(ws), nbytes, current_stream_ptr()),
-          "pv_conv2d_coords_bwd_weight_f32")
+    dw, db = _grads_out(weight_shape, co, sat.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(dy), ptr(dw), ptr(db), n,
+                                          t_per_example, h, w, co, ptr(ws), nbytes, current_stream_ptr()), "pv_" + who)
     return dw, db
 
 
+def conv2d_fwd_f32(x, weight, bias, relu=True):
+    """conv2d(x, weight) + bias (+ ReLU) for x [N, 32, H, W] -> [N, C_out, H-2, W-2], C_out = 32 or 4."""
+    return _conv_fwd(_CONV2D, x, weight, bias, relu)
+
+
+def conv2d_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of a 3x3 valid conv; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
+    return _conv_bwd_data(_CONV2D, dy, dy_gate, weight, x_gate, x_shape)
+
+
+def conv2d_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw, dbias) of a 3x3 valid conv; deterministic (fixed slab split over images, slabs summed in order)."""
+    return _conv_bwd_weight(_CONV2D, x, dy, dy_gate, weight_shape)
+
+
+# ---- experiments/001_CNN_concat_all_timesteps_as_channels.py (csrc/conv2d_pool_f32.hip) ----
 def conv2d144_sat_pool_fwd_f32(sat, x_coords, y_coords, weight, bias, n_frames):
     """relu(max_pool2d(conv2d(cat(frames 0..n_frames-1 of sat [B, T, H, W, 1], 5 synthesised channels), weight) + bias, 3))
     with x_coords [B, W], y_coords [B, H]; the input is built inside the kernel.  Returns (pooled [B, 144, (H-2)//3, (W-2)//3],
     codes uint8 of the same shape)."""
     who = "conv2d144_sat_pool_fwd_f32"
     b, t, h, w = _check_sat001(who, sat, x_coords, y_coords, n_frames)
-    _shape_check(tuple(weight.shape) == (C144, n_frames + 5, 3, 3), who,
-                 f"weight [144, {n_frames + 5}, 3, 3] expected, got {tuple(weight.shape)}")
-    _shape_check(bias is not None and tuple(bias.shape) == (C144,), who, "bias [144] expected")
+    if tuple(weight.shape) != (C144, n_frames + 5, 3, 3):
+        raise ValueError(f"{who}: weight [144, {n_frames + 5}, 3, 3] expected, got {tuple(weight.shape)}")
+    if bias is None or tuple(bias.shape) != (C144,):
+        raise ValueError(f"{who}: bias [144] expected")
     require_cuda(sat, x_coords, y_coords, weight, bias)
     _f32_contig(sat, x_coords, y_coords, weight, bias)
-    y = torch.empty(_pooled_shape(b, h, w), dtype=torch.float32, device=sat.device)
+    y = torch.empty(_pooled_shape(b, C144, h, w), dtype=torch.float32, device=sat.device)
     codes = torch.empty(y.shape, dtype=torch.uint8, device=sat.device)
-    check(get_lib().pv_conv2d144_sat_pool_fwd_f32(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(weight), ptr(bias), ptr(y),
-                                                  ptr(codes), b, t, n_frames, h, w, C144, current_stream_ptr()),
-          "pv_conv2d144_sat_pool_fwd_f32")
+    check(getattr(get_lib(), "pv_" + who)(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(weight), ptr(bias), ptr(y), ptr(codes),
+                                          b, t, n_frames, h, w, C144, current_stream_ptr()), "pv_" + who)
     return y, codes
-
-
-def conv2d144_pool_fwd_f32(x, weight, bias):
-    """relu(max_pool2d(conv2d(x, weight) + bias, 3)) for x [N, 144, H, W] -> (pooled, codes uint8)."""
-    who = "conv2d144_pool_fwd_f32"
-    _check_c144(who, x.shape, weight.shape, True)
-    _shape_check(bias is not None and tuple(bias.shape) == (C144,), who, "bias [144] expected")
-    require_cuda(x, weight, bias)
-    _f32_contig(x, weight, bias)
-    n, c, h, w = x.shape
-    y = torch.empty(_pooled_shape(n, h, w), dtype=torch.float32, device=x.device)
-    codes = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
-    check(get_lib().pv_conv2d144_pool_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(codes), n, c, C144, h, w,
-                                              current_stream_ptr()), "pv_conv2d144_pool_fwd_f32")
-    return y, codes
-
-
-def conv2d144_fwd_f32(x, weight, bias, relu=True):
-    """conv2d(x, weight) + bias (+ ReLU) for x [N, 144, H, W] -> [N, 144, H-2, W-2]."""
-    return _conv_fwd("conv2d144", _check_c144, x, weight, bias, relu)
-
-
-def conv2d144_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
-    """dx of conv2d144_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
-    return _conv_bwd_data("conv2d144", _check_c144, dy, dy_gate, weight, x_gate, x_shape)
-
-
-def conv2d144_pool_bwd_data_f32(dy_pooled, codes, weight, x_gate, x_shape):
-    """dx of conv2d144_pool_fwd_f32 from the pooled gradient and the forward's codes; dx zeroed where x_gate <= 0."""
-    who = "conv2d144_pool_bwd_data_f32"
-    _check_c144(who, x_shape, weight.shape, True)
-    n, c, h, w = x_shape
-    p_shape = _pooled_shape(n, h, w)
-    _shape_check(tuple(dy_pooled.shape) == p_shape and tuple(codes.shape) == p_shape, who,
-                 f"dy_pooled / codes {p_shape} expected, got {tuple(dy_pooled.shape)} / {tuple(codes.shape)}")
-    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
-    require_cuda(dy_pooled, codes, weight, x_gate)
-    _f32_contig(dy_pooled, weight, x_gate)
-    _u8_contig(who, codes)
-    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy_pooled.device)
-    check(get_lib().pv_conv2d144_pool_bwd_data_f32(ptr(dy_pooled), ptr(codes), ptr(weight), ptr(dx), ptr(x_gate), n, c,
-                                                   C144, h, w, current_stream_ptr()), "pv_conv2d144_pool_bwd_data_f32")
-    return dx
-
-
-def conv2d144_bwd_weight_f32(x, dy, dy_gate, weight_shape):
-    """(dw, dbias) of conv2d144_fwd_f32; deterministic (fixed slabs summed in order)."""
-    return _conv_bwd_weight("conv2d144", _check_c144, x, dy, dy_gate, weight_shape, ws_args=(0,))
-
-
-def conv2d144_pool_bwd_weight_f32(x, dy_pooled, codes, weight_shape):
-    """(dw, dbias) of conv2d144_pool_fwd_f32 from the pooled gradient and the codes; deterministic."""
-    who = "conv2d144_pool_bwd_weight_f32"
-    _check_c144(who, x.shape, weight_shape, True)
-    n, c, h, w = x.shape
-    p_shape = _pooled_shape(n, h, w)
-    _shape_check(tuple(dy_pooled.shape) == p_shape and tuple(codes.shape) == p_shape, who,
-                 f"dy_pooled / codes {p_shape} expected, got {tuple(dy_pooled.shape)} / {tuple(codes.shape)}")
-    require_cuda(x, dy_pooled, codes)
-    _f32_contig(x, dy_pooled)
-    _u8_contig(who, codes)
-    ws, nbytes = _wgrad_ws("conv2d144", x.device, n, c, C144, h, w, 1)
-    dw, db = _grads_out((C144, c, 3, 3), x.device)
-    check(get_lib().pv_conv2d144_pool_bwd_weight_f32(ptr(x), ptr(dy_pooled), ptr(codes), ptr(dw), ptr(db), n, c, C144, h,
-                                                     w, ptr(ws), nbytes, current_stream_ptr()),
-          "pv_conv2d144_pool_bwd_weight_f32")
-    return dw, db
 
 
 def conv2d144_sat_pool_bwd_weight_f32(sat, x_coords, y_coords, dy_pooled, codes, n_frames):
     """(dw [144, n_frames + 5, 3, 3], dbias) of conv2d144_sat_pool_fwd_f32, re-synthesising its input; deterministic."""
     who = "conv2d144_sat_pool_bwd_weight_f32"
     b, t, h, w = _check_sat001(who, sat, x_coords, y_coords, n_frames)
-    p_shape = _pooled_shape(b, h, w)
-    _shape_check(tuple(dy_pooled.shape) == p_shape and tuple(codes.shape) == p_shape, who,
-                 f"dy_pooled / codes {p_shape} expected, got {tuple(dy_pooled.shape)} / {tuple(codes.shape)}")
+    _check_pooled(who, _CONV2D144_POOL, dy_pooled, codes, b, C144, h, w)
     require_cuda(sat, x_coords, y_coords, dy_pooled, codes)
     _f32_contig(sat, x_coords, y_coords, dy_pooled)
     _u8_contig(who, codes)
     ws, nbytes = _wgrad_ws("conv2d144", sat.device, b, n_frames + 5, C144, h, w, 1)
-    dw, db = _grads_out((C144, n_frames + 5, 3, 3), sat.device)
-    check(get_lib().pv_conv2d144_sat_pool_bwd_weight_f32(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(dy_pooled), ptr(codes),
-                                                         ptr(dw), ptr(db), b, t, n_frames, h, w, C144, ptr(ws), nbytes,
-                                                         current_stream_ptr()), "pv_conv2d144_sat_pool_bwd_weight_f32")
+    dw, db = _grads_out((C144, n_frames + 5, 3, 3), C144, sat.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(sat), ptr(x_coords), ptr(y_coords), ptr(dy_pooled), ptr(codes), ptr(dw),
+                                          ptr(db), b, t, n_frames, h, w, C144, ptr(ws), nbytes, current_stream_ptr()),
+                                          "pv_" + who)
     return dw, db
 
 
-# ------------------------------------------------------------------------------------------------
-# notebooks/16_maxpool.ipynb: Conv2d 6 -> 16 -> 32 -> 32 -> 32 (+ MaxPool2d(3)), ConvTranspose2d 32 -> 32 -> 16 -> 16 -> 1,
-# cropped normalised MSE (csrc/conv2d_ae_f32.hip); planes up to 128 wide
-# ------------------------------------------------------------------------------------------------
-def _counts_contig(who, *ts):
-    for t in ts:
-        if t.dtype not in (torch.int16, torch.float32) or not t.is_contiguous():
-            raise TypeError(f"{who}: counts must be contiguous int16 or float32 tensors, got {t.dtype}")
+def conv2d144_fwd_f32(x, weight, bias, relu=True):
+    """conv2d(x, weight) + bias (+ ReLU) for x [N, 144, H, W] -> [N, 144, H-2, W-2]."""
+    return _conv_fwd(_CONV2D144, x, weight, bias, relu)
 
 
-def _check_counts(who, history, flow_pred, horizon):
-    _shape_check(history.dim() == 4 and history.shape[1] == 4, who,
-                 f"history [N, 4, H, W] expected, got {tuple(history.shape)}")
-    n, _, h, w = history.shape
-    _shape_check(tuple(flow_pred.shape) == (n, h, w) and tuple(horizon.shape) == (n,), who,
-                 f"flow prediction [{n}, {h}, {w}] and horizon [{n}] expected, got {tuple(flow_pred.shape)} / "
-                 f"{tuple(horizon.shape)}")
-    require_cuda(history, flow_pred, horizon)
-    _counts_contig(who, history, flow_pred)
-    _f32_contig(horizon)
-    return n, h, w
+def conv2d144_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of conv2d144_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
+    return _conv_bwd_data(_CONV2D144, dy, dy_gate, weight, x_gate, x_shape)
 
 
-def _check_ae(who, x_shape, weight_shape):
-    _shape_check(len(x_shape) == 4 and len(weight_shape) == 4 and tuple(weight_shape[1:]) == (x_shape[1], 3, 3), who,
-                 f"x [N, C_in, H, W] and weight [C_out, C_in, 3, 3] expected, got {tuple(x_shape)} / {tuple(weight_shape)}")
+def conv2d144_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw, dbias) of conv2d144_fwd_f32; deterministic (fixed slabs summed in order)."""
+    return _conv_bwd_weight(_CONV2D144, x, dy, dy_gate, weight_shape)
 
 
-def _check_aet(who, x_shape, weight_shape):
-    _shape_check(len(x_shape) == 4 and len(weight_shape) == 4 and weight_shape[0] == x_shape[1]
-                 and tuple(weight_shape[2:]) == (3, 3), who,
-                 f"x [N, C_in, H, W] and weight [C_in, C_out, 3, 3] expected, got {tuple(x_shape)} / {tuple(weight_shape)}")
+def conv2d144_pool_fwd_f32(x, weight, bias):
+    """relu(max_pool2d(conv2d(x, weight) + bias, 3)) for x [N, 144, H, W] -> (pooled, codes uint8)."""
+    return _pool_fwd(_CONV2D144_POOL, x, weight, bias)
 
 
-def _pooled_shape_c(n, c, h, w):
-    if h < 5 or w < 5:
-        raise ValueError(f"images of at least 5 x 5 expected (one whole 3x3 pool window after the 3x3 conv), got {h} x {w}")
-    return (n, c, (h - 2) // 3, (w - 2) // 3)
+def conv2d144_pool_bwd_data_f32(dy_pooled, codes, weight, x_gate, x_shape):
+    """dx of conv2d144_pool_fwd_f32 from the pooled gradient and the forward's codes; dx zeroed where x_gate <= 0."""
+    return _pool_bwd_data(_CONV2D144_POOL, dy_pooled, codes, weight, x_gate, x_shape)
 
 
+def conv2d144_pool_bwd_weight_f32(x, dy_pooled, codes, weight_shape):
+    """(dw, dbias) of conv2d144_pool_fwd_f32 from the pooled gradient and the codes; deterministic."""
+    return _pool_bwd_weight(_CONV2D144_POOL, x, dy_pooled, codes, weight_shape)
+
+
+# ---- notebooks/16_maxpool.ipynb: Conv2d 6 -> 16 -> 32 -> 32 -> 32 (+ MaxPool2d(3)), ConvTranspose2d 32 -> 32 -> 16 -> 16 -> 1,
+# cropped normalised MSE (csrc/conv2d_ae_f32.hip); planes up to 128 wide ----
 def conv2d_ae_counts_fwd_f32(history, flow_pred, horizon, weight, bias):
     """relu(conv2d(cat(normalise(history), normalise(flow_pred)[:, None], horizon plane), weight) + bias): history
     [N, 4, H, W] and flow_pred [N, H, W] as int16 or f32 counts, horizon [N] f32 -> [N, 16, H-2, W-2]."""
-    who = "conv2d_ae_counts_fwd_f32"
-    n, h, w = _check_counts(who, history, flow_pred, horizon)
-    co = weight.shape[0]
-    _shape_check(tuple(weight.shape) == (co, 6, 3, 3), who, f"weight [C_out, 6, 3, 3] expected, got {tuple(weight.shape)}")
-    _shape_check(bias is not None and tuple(bias.shape) == (co,), who, f"bias [{co}] expected")
-    require_cuda(weight, bias)
-    _f32_contig(weight, bias)
-    y = torch.empty((n, co, max(h - 2, 0), max(w - 2, 0)), dtype=torch.float32, device=history.device)
-    check(get_lib().pv_conv2d_ae_counts_fwd_f32(ptr(history), int(history.dtype == torch.int16), ptr(flow_pred),
-                                                int(flow_pred.dtype == torch.int16), ptr(horizon), ptr(weight), ptr(bias),
-                                                ptr(y), n, h, w, co, current_stream_ptr()), "pv_conv2d_ae_counts_fwd_f32")
-    return y
+    return _counts_fwd(_CONV2D_AE, history, flow_pred, horizon, weight, bias)
 
 
 def conv2d_ae_counts_bwd_weight_f32(history, flow_pred, horizon, dy, weight_shape):
     """(dw [16, 6, 3, 3], dbias) of conv2d_ae_counts_fwd_f32's conv from its pre-activation gradient dy."""
-    who = "conv2d_ae_counts_bwd_weight_f32"
-    n, h, w = _check_counts(who, history, flow_pred, horizon)
-    co = weight_shape[0]
-    _shape_check(tuple(weight_shape) == (co, 6, 3, 3) and tuple(dy.shape) == (n, co, h - 2, w - 2), who,
-                 f"weight {(co, 6, 3, 3)} and dy {(n, co, h - 2, w - 2)} expected, got {tuple(weight_shape)} / "
-                 f"{tuple(dy.shape)}")
-    require_cuda(dy)
-    _f32_contig(dy)
-    ws, nbytes = _wgrad_ws("conv2d_ae", history.device, n, 6, co, h, w, 0)
-    dw, db = _grads_out(weight_shape, history.device)
-    check(get_lib().pv_conv2d_ae_counts_bwd_weight_f32(ptr(history), int(history.dtype == torch.int16), ptr(flow_pred),
-                                                       int(flow_pred.dtype == torch.int16), ptr(horizon), ptr(dy), ptr(dw),
-                                                       ptr(db), n, h, w, co, ptr(ws), nbytes, current_stream_ptr()),
-          "pv_conv2d_ae_counts_bwd_weight_f32")
-    return dw, db
+    return _counts_bwd_weight(_CONV2D_AE, history, flow_pred, horizon, dy, weight_shape)
 
 
 def conv2d_ae_fwd_f32(x, weight, bias, relu=True):
     """conv2d(x, weight) + bias (+ ReLU) for (C_in, C_out) = (16, 32) or (32, 32), W <= 128."""
-    return _conv_fwd("conv2d_ae", _check_ae, x, weight, bias, relu)
+    return _conv_fwd(_CONV2D_AE, x, weight, bias, relu)
 
 
 def conv2d_ae_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
     """dx of conv2d_ae_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
-    return _conv_bwd_data("conv2d_ae", _check_ae, dy, dy_gate, weight, x_gate, x_shape)
+    return _conv_bwd_data(_CONV2D_AE, dy, dy_gate, weight, x_gate, x_shape)
 
 
 def conv2d_ae_bwd_weight_f32(x, dy, dy_gate, weight_shape):
     """(dw, dbias) of conv2d_ae_fwd_f32; deterministic (fixed slabs summed in order)."""
-    return _conv_bwd_weight("conv2d_ae", _check_ae, x, dy, dy_gate, weight_shape, ws_args=(0,))
+    return _conv_bwd_weight(_CONV2D_AE, x, dy, dy_gate, weight_shape)
 
 
 def conv2d_ae_pool_fwd_f32(x, weight, bias):
     """relu(max_pool2d(conv2d(x, weight) + bias, 3)) for x [N, 32, H, W] -> (pooled, codes uint8)."""
-    who = "conv2d_ae_pool_fwd_f32"
-    _check_ae(who, x.shape, weight.shape)
-    n, c, h, w = x.shape
-    co = weight.shape[0]
-    _shape_check(bias is not None and tuple(bias.shape) == (co,), who, f"bias [{co}] expected")
-    require_cuda(x, weight, bias)
-    _f32_contig(x, weight, bias)
-    y = torch.empty(_pooled_shape_c(n, co, h, w), dtype=torch.float32, device=x.device)
-    codes = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
-    nbytes = ctypes.c_size_t(0)
-    check(get_lib().pv_conv2d_ae_pool_fwd_workspace_bytes(n, c, co, h, w, ctypes.byref(nbytes)),
-          "pv_conv2d_ae_pool_fwd_workspace_bytes")
-    ws = _workspace("conv2d_ae_pool_fwd", nbytes.value, x.device) if nbytes.value else None
-    check(get_lib().pv_conv2d_ae_pool_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), ptr(codes), n, c, co, h, w, ptr(ws),
-                                              nbytes.value, current_stream_ptr()), "pv_conv2d_ae_pool_fwd_f32")
-    return y, codes
+    return _pool_fwd(_CONV2D_AE_POOL, x, weight, bias)
 
 
 def conv2d_ae_pool_bwd_data_f32(dy_pooled, codes, weight, x_gate, x_shape):
     """dx of conv2d_ae_pool_fwd_f32 from the pooled gradient and the forward's codes; dx zeroed where x_gate <= 0."""
-    who = "conv2d_ae_pool_bwd_data_f32"
-    _check_ae(who, x_shape, weight.shape)
-    n, c, h, w = x_shape
-    p_shape = _pooled_shape_c(n, weight.shape[0], h, w)
-    _shape_check(tuple(dy_pooled.shape) == p_shape and tuple(codes.shape) == p_shape, who,
-                 f"dy_pooled / codes {p_shape} expected, got {tuple(dy_pooled.shape)} / {tuple(codes.shape)}")
-    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
-    require_cuda(dy_pooled, codes, weight, x_gate)
-    _f32_contig(dy_pooled, weight, x_gate)
-    _u8_contig(who, codes)
-    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy_pooled.device)
-    check(get_lib().pv_conv2d_ae_pool_bwd_data_f32(ptr(dy_pooled), ptr(codes), ptr(weight), ptr(dx), ptr(x_gate), n, c,
-                                                   weight.shape[0], h, w, current_stream_ptr()),
-          "pv_conv2d_ae_pool_bwd_data_f32")
-    return dx
+    return _pool_bwd_data(_CONV2D_AE_POOL, dy_pooled, codes, weight, x_gate, x_shape)
 
 
 def conv2d_ae_pool_bwd_weight_f32(x, dy_pooled, codes, weight_shape):
     """(dw, dbias) of conv2d_ae_pool_fwd_f32 from the pooled gradient and the codes; deterministic."""
-    who = "conv2d_ae_pool_bwd_weight_f32"
-    _check_ae(who, x.shape, weight_shape)
-    n, c, h, w = x.shape
-    co = weight_shape[0]
-    p_shape = _pooled_shape_c(n, co, h, w)
-    _shape_check(tuple(dy_pooled.shape) == p_shape and tuple(codes.shape) == p_shape, who,
-                 f"dy_pooled / codes {p_shape} expected, got {tuple(dy_pooled.shape)} / {tuple(codes.shape)}")
-    require_cuda(x, dy_pooled, codes)
-    _f32_contig(x, dy_pooled)
-    _u8_contig(who, codes)
-    ws, nbytes = _wgrad_ws("conv2d_ae", x.device, n, c, co, h, w, 1)
-    dw, db = _grads_out(tuple(weight_shape), x.device)
-    check(get_lib().pv_conv2d_ae_pool_bwd_weight_f32(ptr(x), ptr(dy_pooled), ptr(codes), ptr(dw), ptr(db), n, c, co, h, w,
-                                                     ptr(ws), nbytes, current_stream_ptr()),
-          "pv_conv2d_ae_pool_bwd_weight_f32")
-    return dw, db
+    return _pool_bwd_weight(_CONV2D_AE_POOL, x, dy_pooled, codes, weight_shape)
 
 
 def convt2d_ae_fwd_f32(x, weight, bias, relu=True):
     """conv_transpose2d(x, weight) + bias (+ ReLU): x [N, C_in, H, W], weight [C_in, C_out, 3, 3] -> [N, C_out, H+2, W+2]."""
-    who = "convt2d_ae_fwd_f32"
-    _check_aet(who, x.shape, weight.shape)
-    n, ci, h, w = x.shape
-    co = weight.shape[1]
-    _check_bias(who, bias, co)
-    require_cuda(x, weight, bias)
-    _f32_contig(x, weight, bias)
-    y = torch.empty((n, co, h + 2, w + 2), dtype=torch.float32, device=x.device)
-    check(get_lib().pv_convt2d_ae_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, int(relu),
-                                          current_stream_ptr()), "pv_convt2d_ae_fwd_f32")
-    return y
+    return _conv_fwd(_CONVT2D_AE, x, weight, bias, relu)
 
 
 def convt2d_ae_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
     """dx of convt2d_ae_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
-    who = "convt2d_ae_bwd_data_f32"
-    _check_aet(who, x_shape, weight.shape)
-    n, ci, h, w = x_shape
-    co = weight.shape[1]
-    y_shape = (n, co, h + 2, w + 2)
-    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
-                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
-    require_cuda(dy, dy_gate, weight, x_gate)
-    _f32_contig(dy, dy_gate, weight, x_gate)
-    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
-    check(get_lib().pv_convt2d_ae_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci, co, h, w,
-                                               current_stream_ptr()), "pv_convt2d_ae_bwd_data_f32")
-    return dx
+    return _conv_bwd_data(_CONVT2D_AE, dy, dy_gate, weight, x_gate, x_shape)
 
 
 def convt2d_ae_bwd_weight_f32(x, dy, dy_gate, weight_shape):
     """(dw [C_in, C_out, 3, 3], dbias [C_out]) of convt2d_ae_fwd_f32; deterministic (fixed slabs summed in order)."""
-    who = "convt2d_ae_bwd_weight_f32"
-    _check_aet(who, x.shape, weight_shape)
-    n, ci, h, w = x.shape
-    co = weight_shape[1]
-    y_shape = (n, co, h + 2, w + 2)
-    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
-                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    require_cuda(x, dy, dy_gate)
-    _f32_contig(x, dy, dy_gate)
-    ws, nbytes = _wgrad_ws("convt2d_ae", x.device, n, ci, co, h, w)
-    dw = torch.empty(tuple(weight_shape), dtype=torch.float32, device=x.device)
-    db = torch.empty((co,), dtype=torch.float32, device=x.device)
-    check(get_lib().pv_convt2d_ae_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, ptr(ws),
-                                                 nbytes, current_stream_ptr()), "pv_convt2d_ae_bwd_weight_f32")
-    return dw, db
+    return _conv_bwd_weight(_CONVT2D_AE, x, dy, dy_gate, weight_shape)
 
 
 def mse_crop_norm_f32(y_hat, target, need_grad=True):
     """mse_loss(y_hat, normalise(target)[..., 8:-8, 8:-8]) for y_hat [N, P, Q] f32 and target [N, P+16, Q+16] counts (int16
     or f32).  Returns (loss f32[1], dy_hat or None)."""
-    who = "mse_crop_norm_f32"
-    _shape_check(y_hat.dim() == 3 and target.dim() == 3 and target.shape[0] == y_hat.shape[0], who,
-                 f"y_hat [N, P, Q] and target [N, T, U] expected, got {tuple(y_hat.shape)} / {tuple(target.shape)}")
-    require_cuda(y_hat, target)
-    _f32_contig(y_hat)
-    _counts_contig(who, target)
-    n, oh, ow = y_hat.shape
-    loss = torch.empty((1,), dtype=torch.float32, device=y_hat.device)
-    grad = torch.empty_like(y_hat) if need_grad else None
-    ws = _workspace("mse_crop_norm", 4 * n, y_hat.device)
-    check(get_lib().pv_mse_crop_norm_f32(ptr(y_hat), ptr(target), int(target.dtype == torch.int16), n, oh, ow,
-                                         target.shape[1], target.shape[2], ptr(loss), ptr(grad), ptr(ws), 4 * n,
-                                         current_stream_ptr()), "pv_mse_crop_norm_f32")
-    return loss, grad
+    return _mse_norm("mse_crop_norm", y_hat, target, (), need_grad)
 
 
-def mse_window_norm_f32(y_hat, target, row0=0, col0=0, need_grad=True):
-    """mse_loss(y_hat, normalise(target)[..., row0:row0 + P, col0:col0 + Q]) for y_hat [N, P, Q] f32 and target [N, T, U]
-    counts (int16 or f32).  Returns (loss f32[1], dy_hat or None)."""
-    who = "mse_window_norm_f32"
-    _shape_check(y_hat.dim() == 3 and target.dim() == 3 and target.shape[0] == y_hat.shape[0], who,
-                 f"y_hat [N, P, Q] and target [N, T, U] expected, got {tuple(y_hat.shape)} / {tuple(target.shape)}")
-    require_cuda(y_hat, target)
-    _f32_contig(y_hat)
-    _counts_contig(who, target)
-    n, oh, ow = y_hat.shape
-    loss = torch.empty((1,), dtype=torch.float32, device=y_hat.device)
-    grad = torch.empty_like(y_hat) if need_grad else None
-    ws = _workspace("mse_window_norm", 4 * n, y_hat.device)
-    check(get_lib().pv_mse_window_norm_f32(ptr(y_hat), ptr(target), int(target.dtype == torch.int16), n, oh, ow,
-                                           target.shape[1], target.shape[2], int(row0), int(col0), ptr(loss), ptr(grad),
-                                           ptr(ws), 4 * n, current_stream_ptr()), "pv_mse_window_norm_f32")
-    return loss, grad
-
-
-# ------------------------------------------------------------------------------------------------
-# notebooks/14_back_to_2d_conv_AE.ipynb, 15_int16.ipynb: Conv2d 6 -> 16 -> 32 -> 32 -> 32, ConvTranspose2d 32 -> 32 -> 16 -> 1,
-# all 3x3 stride 2 (csrc/conv2d_s2_f32.hip); planes up to 128 wide on the wide side
-# ------------------------------------------------------------------------------------------------
-def s2_out(side):
-    """Side of a 3x3 stride-2 Conv2d's output."""
-    return (side - 3) // 2 + 1
-
-
-def _s2_y_shape(n, co, h, w):
-    return (n, co, max(s2_out(h), 0), max(s2_out(w), 0))
-
-
+# ---- notebooks/14_back_to_2d_conv_AE.ipynb, 15_int16.ipynb: Conv2d 6 -> 16 -> 32 -> 32 -> 32, ConvTranspose2d 32 -> 32 -> 16
+# -> 1, all 3x3 stride 2 (csrc/conv2d_s2_f32.hip); planes up to 128 wide on the wide side ----
 def conv2d_s2_counts_fwd_f32(history, flow_pred, horizon, weight, bias):
     """relu(conv2d(cat(normalise(history), normalise(flow_pred)[:, None], horizon plane), weight, stride=2) + bias): history
     [N, 4, H, W] and flow_pred [N, H, W] as int16 or f32 counts, horizon [N] f32 -> [N, 16, (H-3)//2+1, (W-3)//2+1]."""
-    who = "conv2d_s2_counts_fwd_f32"
-    n, h, w = _check_counts(who, history, flow_pred, horizon)
-    co = weight.shape[0]
-    _shape_check(tuple(weight.shape) == (co, 6, 3, 3), who, f"weight [C_out, 6, 3, 3] expected, got {tuple(weight.shape)}")
-    _shape_check(bias is not None and tuple(bias.shape) == (co,), who, f"bias [{co}] expected")
-    require_cuda(weight, bias)
-    _f32_contig(weight, bias)
-    y = torch.empty(_s2_y_shape(n, co, h, w), dtype=torch.float32, device=history.device)
-    check(get_lib().pv_conv2d_s2_counts_fwd_f32(ptr(history), int(history.dtype == torch.int16), ptr(flow_pred),
-                                                int(flow_pred.dtype == torch.int16), ptr(horizon), ptr(weight), ptr(bias),
-                                                ptr(y), n, h, w, co, current_stream_ptr()), "pv_conv2d_s2_counts_fwd_f32")
-    return y
+    return _counts_fwd(_CONV2D_S2, history, flow_pred, horizon, weight, bias)
 
 
 def conv2d_s2_counts_bwd_weight_f32(history, flow_pred, horizon, dy, weight_shape):
     """(dw [16, 6, 3, 3], dbias) of conv2d_s2_counts_fwd_f32's conv from its pre-activation gradient dy."""
-    who = "conv2d_s2_counts_bwd_weight_f32"
-    n, h, w = _check_counts(who, history, flow_pred, horizon)
-    co = weight_shape[0]
-    y_shape = _s2_y_shape(n, co, h, w)
-    _shape_check(tuple(weight_shape) == (co, 6, 3, 3) and tuple(dy.shape) == y_shape, who,
-                 f"weight {(co, 6, 3, 3)} and dy {y_shape} expected, got {tuple(weight_shape)} / {tuple(dy.shape)}")
-    require_cuda(dy)
-    _f32_contig(dy)
-    ws, nbytes = _wgrad_ws("conv2d_s2", history.device, n, 6, co, h, w)
-    dw, db = _grads_out(weight_shape, history.device)
-    check(get_lib().pv_conv2d_s2_counts_bwd_weight_f32(ptr(history), int(history.dtype == torch.int16), ptr(flow_pred),
-                                                       int(flow_pred.dtype == torch.int16), ptr(horizon), ptr(dy), ptr(dw),
-                                                       ptr(db), n, h, w, co, ptr(ws), nbytes, current_stream_ptr()),
-          "pv_conv2d_s2_counts_bwd_weight_f32")
-    return dw, db
+    return _counts_bwd_weight(_CONV2D_S2, history, flow_pred, horizon, dy, weight_shape)
 
 
 def conv2d_s2_fwd_f32(x, weight, bias, relu=True):
     """conv2d(x, weight, stride=2) + bias (+ ReLU) for (C_in, C_out) = (16, 32) or (32, 32), W <= 128."""
-    who = "conv2d_s2_fwd_f32"
-    _check_ae(who, x.shape, weight.shape)
-    n, ci, h, w = x.shape
-    co = weight.shape[0]
-    _check_bias(who, bias, co)
-    require_cuda(x, weight, bias)
-    _f32_contig(x, weight, bias)
-    y = torch.empty(_s2_y_shape(n, co, h, w), dtype=torch.float32, device=x.device)
-    check(get_lib().pv_conv2d_s2_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, int(relu),
-                                         current_stream_ptr()), "pv_conv2d_s2_fwd_f32")
-    return y
+    return _conv_fwd(_CONV2D_S2, x, weight, bias, relu)
 
 
 def conv2d_s2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
     """dx of conv2d_s2_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None).  The rows and
     columns of x the forward never reads get exactly 0."""
-    who = "conv2d_s2_bwd_data_f32"
-    _check_ae(who, x_shape, weight.shape)
-    n, ci, h, w = x_shape
-    co = weight.shape[0]
-    y_shape = _s2_y_shape(n, co, h, w)
-    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
-                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
-    require_cuda(dy, dy_gate, weight, x_gate)
-    _f32_contig(dy, dy_gate, weight, x_gate)
-    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
-    check(get_lib().pv_conv2d_s2_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci, co, h, w,
-                                              current_stream_ptr()), "pv_conv2d_s2_bwd_data_f32")
-    return dx
+    return _conv_bwd_data(_CONV2D_S2, dy, dy_gate, weight, x_gate, x_shape)
 
 
 def conv2d_s2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
     """(dw, dbias) of conv2d_s2_fwd_f32; deterministic (fixed slabs summed in order)."""
-    who = "conv2d_s2_bwd_weight_f32"
-    _check_ae(who, x.shape, weight_shape)
-    n, ci, h, w = x.shape
-    co = weight_shape[0]
-    y_shape = _s2_y_shape(n, co, h, w)
-    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
-                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    require_cuda(x, dy, dy_gate)
-    _f32_contig(x, dy, dy_gate)
-    ws, nbytes = _wgrad_ws("conv2d_s2", x.device, n, ci, co, h, w)
-    dw, db = _grads_out(weight_shape, x.device)
-    check(get_lib().pv_conv2d_s2_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, ptr(ws),
-                                                nbytes, current_stream_ptr()), "pv_conv2d_s2_bwd_weight_f32")
-    return dw, db
+    return _conv_bwd_weight(_CONV2D_S2, x, dy, dy_gate, weight_shape)
 
 
 def convt2d_s2_fwd_f32(x, weight, bias, relu=True):
     """conv_transpose2d(x, weight, stride=2) + bias (+ ReLU): x [N, C_in, H, W], weight [C_in, C_out, 3, 3] -> [N, C_out,
     2H+1, 2W+1] for (C_in, C_out) = (32, 32), (32, 16) or (16, 1)."""
-    who = "convt2d_s2_fwd_f32"
-    _check_aet(who, x.shape, weight.shape)
-    n, ci, h, w = x.shape
-    co = weight.shape[1]
-    _check_bias(who, bias, co)
-    require_cuda(x, weight, bias)
-    _f32_contig(x, weight, bias)
-    y = torch.empty((n, co, 2 * h + 1, 2 * w + 1), dtype=torch.float32, device=x.device)
-    check(get_lib().pv_convt2d_s2_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, int(relu),
-                                          current_stream_ptr()), "pv_convt2d_s2_fwd_f32")
-    return y
+    return _conv_fwd(_CONVT2D_S2, x, weight, bias, relu)
 
 
 def convt2d_s2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
     """dx of convt2d_s2_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
-    who = "convt2d_s2_bwd_data_f32"
-    _check_aet(who, x_shape, weight.shape)
-    n, ci, h, w = x_shape
-    co = weight.shape[1]
-    y_shape = (n, co, 2 * h + 1, 2 * w + 1)
-    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
-                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    _shape_check(x_gate is None or tuple(x_gate.shape) == tuple(x_shape), who, f"x_gate {tuple(x_shape)} expected")
-    require_cuda(dy, dy_gate, weight, x_gate)
-    _f32_contig(dy, dy_gate, weight, x_gate)
-    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
-    check(get_lib().pv_convt2d_s2_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci, co, h, w,
-                                               current_stream_ptr()), "pv_convt2d_s2_bwd_data_f32")
-    return dx
+    return _conv_bwd_data(_CONVT2D_S2, dy, dy_gate, weight, x_gate, x_shape)
 
 
 def convt2d_s2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
     """(dw [C_in, C_out, 3, 3], dbias [C_out]) of convt2d_s2_fwd_f32; deterministic (fixed slabs summed in order)."""
-    who = "convt2d_s2_bwd_weight_f32"
-    _check_aet(who, x.shape, weight_shape)
-    n, ci, h, w = x.shape
-    co = weight_shape[1]
-    y_shape = (n, co, 2 * h + 1, 2 * w + 1)
-    _shape_check(tuple(dy.shape) == y_shape and (dy_gate is None or tuple(dy_gate.shape) == y_shape), who,
-                 f"dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    require_cuda(x, dy, dy_gate)
-    _f32_contig(x, dy, dy_gate)
-    ws, nbytes = _wgrad_ws("convt2d_s2", x.device, n, ci, co, h, w)
-    dw = torch.empty(tuple(weight_shape), dtype=torch.float32, device=x.device)
-    db = torch.empty((co,), dtype=torch.float32, device=x.device)
-    check(get_lib().pv_convt2d_s2_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, ptr(ws),
-                                                 nbytes, current_stream_ptr()), "pv_convt2d_s2_bwd_weight_f32")
-    return dw, db
+    return _conv_bwd_weight(_CONVT2D_S2, x, dy, dy_gate, weight_shape)
+
+
+def mse_window_norm_f32(y_hat, target, row0=0, col0=0, need_grad=True):
+    """mse_loss(y_hat, normalise(target)[..., row0:row0 + P, col0:col0 + Q]) for y_hat [N, P, Q] f32 and target [N, T, U]
+    counts (int16 or f32).  Returns (loss f32[1], dy_hat or None)."""
+    return _mse_norm("mse_window_norm", y_hat, target, (row0, col0), need_grad)
 
 
 def maxpool3d_fwd_f32(x, kernel=3, stride=None, padding=0):
