@@ -16,6 +16,7 @@ import ctypes
 import torch
 
 from . import hip_ops as K
+from ._backward_pass import PassTable
 from ._lib import check, current_stream_ptr, get_lib, ptr
 
 
@@ -276,22 +277,17 @@ def bf16_shadow_of(weight: torch.Tensor) -> torch.Tensor:
     return shadow
 
 
-# dx tensors that already carry their producer's ReLU derivative (keyed by storage address, valid inside one backward pass):
-# the fc1 single-pass kernel can apply (x > 0) while it stores dx, and the last conv layer's backward then repacks without
-# reading its activation again
-_PREGATED_DX = {}
+# dx tensors that already carry their producer's ReLU derivative: the fc1 single-pass kernel can apply (x > 0) while it stores dx,
+# and the last conv layer's backward then repacks without reading its activation again (lifetime: _backward_pass.PassTable)
+_PREGATED_DX = PassTable()
 
 
 def _mark_pregated(t: torch.Tensor) -> None:
-    task = torch._C._current_graph_task_id()
-    if any(v != task for v in _PREGATED_DX.values()):
-        _PREGATED_DX.clear()          # marks of an earlier backward pass that nobody consumed
-    _PREGATED_DX[t.data_ptr()] = task
+    _PREGATED_DX.put(t, True)
 
 
 def _take_pregated(t: torch.Tensor) -> bool:
-    task = _PREGATED_DX.pop(t.data_ptr(), None)
-    return task is not None and task == torch._C._current_graph_task_id() and task >= 0
+    return _PREGATED_DX.take(t) is not None
 
 
 class LinearBF16(torch.autograd.Function):
@@ -499,26 +495,10 @@ def _conv_on_f16x2(x, weight, stride, padding) -> bool:
     return conv_f16x2_takes(x.shape[0], x.shape[1], x.shape[2], x.shape[3], x.shape[4], weight, stride, padding, x.requires_grad)
 
 
-def _register_gated(t: torch.Tensor, registry: dict, value) -> None:
-    """Something a gradient tensor's producer leaves for its consumer -- the largest magnitude (_GATED_MAX) or the finished
-    operand images (_GATED_PLANES) of the two-term split -- keyed by storage, valid inside this backward pass (see
-    ReluGateF32.backward)."""
-    task = torch._C._current_graph_task_id()
-    if _GATED_MAX_TASK[0] != task:
-        _GATED_MAX.clear()
-        _GATED_PLANES.clear()
-        _GATED_MAX_TASK[0] = task
-    # the entry HOLDS the tensor: while it is registered its storage cannot be handed to another gradient of the same backward
-    # pass by the caching allocator, so a later tensor can never find a stale entry at "its" address (ADVICE r5); an entry
-    # nobody consumes lives until the next backward pass starts (one gradient tensor kept alive, at most)
-    registry[(t.data_ptr(), t.numel())] = (value, t)
-
-
-def _gated_planes_of(t: torch.Tensor):
-    if _GATED_MAX_TASK[0] != torch._C._current_graph_task_id():
-        return None
-    hit = _GATED_PLANES.pop((t.data_ptr(), t.numel()), None)
-    return hit[0] if hit is not None else None
+# what a gradient tensor's producer leaves for its consumer (_backward_pass.PassTable): the largest magnitude of a gated gradient
+# (ReluGateF32.backward) and the finished operand images of the two-term split (Conv3dF32OnF16x2.backward)
+_GATED_MAX = PassTable()
+_GATED_PLANES = PassTable()
 
 
 class Conv3dF32OnF16x2(torch.autograd.Function):
@@ -548,27 +528,28 @@ class Conv3dF32OnF16x2(torch.autograd.Function):
                                           relu=relu, want_f32=not chain_out)
         ctx.save_for_backward(y if (relu and not dy_pregated) else None, xh, xl, xs, wp, ws)
         ctx.padding, ctx.has_bias, ctx.c_in, ctx.gate_dx, ctx.chain_out = p, bias is not None, weight.shape[1], x_is_relu_output, chain_out
-        if chain_out:
-            _FWD_PLANES[0] = (yp.data_ptr(), ys)
-            return yp
-        _FWD_PLANES[0] = (y.data_ptr(), (yp[0], yp[1], ys))
-        return y
+        # the by-products (the output's own operand images, its scale state) leave as non-differentiable outputs, like
+        # Conv3dReLUBF16's mask; a chained output IS the images
+        out, planes = (yp, torch.empty(0, dtype=torch.float16, device=yp.device)) if chain_out else (y, yp)
+        ctx.mark_non_differentiable(planes, ys)
+        ctx.set_materialize_grads(False)
+        return out, planes, ys
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, _dplanes, _dstate):
         y, xh, xl, xs, wp, ws = ctx.saved_tensors
         dy = dy.contiguous()
         planes = None
         if ctx.chain_out:
-            planes = _gated_planes_of(dy)
+            planes = _GATED_PLANES.take(dy)
             if planes is None:
                 raise RuntimeError("Conv3dF32OnF16x2: the gradient of a chained output (operand images) must come from exactly one "
                                    "Conv3dF32OnF16x2 consumer's backward; build the layer with chain_out=False for any other use")
         elif y is not None:
             dy, dmax = K.relu_gate_f32(dy, y, want_max=True)
         else:
-            planes = _gated_planes_of(dy)
-            dmax = None if planes is not None else _gated_max_of(dy)
+            planes = _GATED_PLANES.take(dy)
+            dmax = None if planes is not None else _GATED_MAX.take(dy)
         if planes is None:
             planes = K.pack_split2_ncdhw_f32_to_ndhwc_f16(dy, maxabs_state=dmax)
         dh, dl, ds = planes
@@ -580,15 +561,11 @@ class Conv3dF32OnF16x2(torch.autograd.Function):
                                                  gate_h=xh if ctx.gate_dx else None, data_gradient=True, want_f32=not ctx.x_is_images)
             if ctx.x_is_images:
                 dx = dxp
-            _register_gated(dx, _GATED_PLANES, (dxp[0], dxp[1], dxs))
+            _GATED_PLANES.put(dx, (dxp[0], dxp[1], dxs))
         dw, db = K.conv3d_bwd_weight_f32_from_split2(xh, xl, xs, dh, dl, ds, 32, ctx.padding)
         if ctx.c_in < 32:
             dw = dw[:, :ctx.c_in].contiguous()      # (the padded channels' gradient is zero)
         return dx, dw, (db if ctx.has_bias else None), None, None, None, None, None
-
-
-_FWD_PLANES = [None]      # (data_ptr of the newest f16x2 forward's output, its operand images + state): attached to the tensor by the wrapper
-_GATED_PLANES = {}
 
 
 class Conv3dGeneralF32(torch.autograd.Function):
@@ -619,22 +596,11 @@ class Conv3dGeneralF32(torch.autograd.Function):
         if _wgrad_on_f16x2(x, dy, y, weight, ctx.stride):
             # the PV-yield model's 3x3x3 layers: three launches of the 16-bit weight-gradient kernel on two-term half-float
             # operands instead of one at the f32 matrix rate, f32-accurate (hip_ops.conv3d_bwd_weight_f32_on_f16x2)
-            dw, db = K.conv3d_bwd_weight_f32_on_f16x2(x, dy, _triple(ctx.padding), dy_maxabs_state=_gated_max_of(dy))
+            dw, db = K.conv3d_bwd_weight_f32_on_f16x2(x, dy, _triple(ctx.padding), dy_maxabs_state=_GATED_MAX.take(dy))
             return dx, dw, (db if ctx.has_bias else None), None, None, None, None, None
         dw, db = K.conv3d_general_bwd_weight_f32(x, dy, y, tuple(weight.shape), ctx.stride, ctx.padding,
                                                  need_bias=ctx.has_bias)
         return dx, dw, db, None, None, None, None, None
-
-
-_GATED_MAX = {}
-_GATED_MAX_TASK = [-1]
-
-
-def _gated_max_of(t: torch.Tensor):
-    if _GATED_MAX_TASK[0] != torch._C._current_graph_task_id():
-        return None
-    hit = _GATED_MAX.pop((t.data_ptr(), t.numel()), None)   # consumed once
-    return hit[0] if hit is not None else None
 
 
 class ReluGateF32(torch.autograd.Function):
@@ -650,9 +616,7 @@ class ReluGateF32(torch.autograd.Function):
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
         g, state = K.relu_gate_f32(dy, y, want_max=True)
-        # the gated gradient's largest magnitude, for the two-term split of the producing layer's weight gradient (keyed by the
-        # tensor's storage like _PREGATED_DX, valid inside this backward pass)
-        _register_gated(g, _GATED_MAX, state)
+        _GATED_MAX.put(g, state)      # for the two-term split of the producing layer's weight gradient
         return g
 
 
@@ -665,14 +629,12 @@ def conv3d_general_f32(x, weight, bias, stride=1, padding=0, relu=False, x_is_re
     the result may then be the pair of operand images (is_operand_images) instead of a float32 tensor."""
     if x.is_cuda and _conv_on_f16x2(x, weight, stride, padding):
         chain = bool(chain_out) and (dy_pregated or not relu)
-        y = Conv3dF32OnF16x2.apply(x, weight, bias, padding, relu, x_is_relu_output, dy_pregated, chain)
+        y, planes, state = Conv3dF32OnF16x2.apply(x, weight, bias, padding, relu, x_is_relu_output, dy_pregated, chain)
         # the sum pass's split of y travels with the tensor object: the next layer reads it instead of splitting y again
-        tag, _FWD_PLANES[0] = _FWD_PLANES[0], None
-        if tag is not None and tag[0] == y.data_ptr():
-            if chain:
-                y._pv_state = tag[1]
-            else:
-                y._pv_planes = tag[1] + (y._version,)
+        if chain:
+            y._pv_state = state
+        else:
+            y._pv_planes = (planes[0], planes[1], state, y._version)
         return y
     if is_operand_images(x):
         raise RuntimeError("conv3d_general_f32: operand images (a chained half-float conv's output) reached a layer the half-float "

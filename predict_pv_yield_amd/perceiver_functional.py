@@ -4,6 +4,7 @@ data movement; every contraction and every row-wise arithmetic op runs in the HI
 import torch
 
 from . import hip_ops as K
+from ._backward_pass import PassTable
 
 
 # ---- gradients of weights that several layers share ---------------------------------------------------------------------
@@ -13,11 +14,7 @@ from . import hip_ops as K
 # later one of the same pass is added into that very tensor by the kernel that produces it (same order of additions as
 # autograd's: arrival order) and autograd is told "no gradient" -- it still holds the first tensor, which now carries the sum.
 ACCUMULATE_TIED_GRADS = True
-_TIED = {}
-_TIED_TASK = [-1]
-
-
-_GRAPH_GEN = [0]      # number of backward passes seen so far: a use count noted before the latest one is stale
+_TIED = PassTable()       # first-arrival gradient (or tuple of gradients) of a parameter; _TIED.passes: a use count noted before the latest pass is stale
 
 
 def _note_use(param) -> None:
@@ -30,43 +27,36 @@ def _note_use(param) -> None:
     at the first use after the next backward pass (they carry the generation they were noted in)."""
     if param is None or not param.requires_grad or not torch.is_grad_enabled():
         return
-    if getattr(param, "_pv_uses_gen", -1) != _GRAPH_GEN[0]:
-        param._pv_uses, param._pv_uses_gen = 0, _GRAPH_GEN[0]
+    if getattr(param, "_pv_uses_gen", -1) != _TIED.passes:
+        param._pv_uses, param._pv_uses_gen = 0, _TIED.passes
     param._pv_uses += 1
 
 
 def _tied_slot(param: torch.Tensor):
     """-> (key, buffer | None): the tensor this backward pass already handed out for `param`, if any.  key is None when
     nothing has to be kept (the parameter was applied once)."""
-    task = torch._C._current_graph_task_id()
-    if not ACCUMULATE_TIED_GRADS or task < 0:
+    if not ACCUMULATE_TIED_GRADS or torch._C._current_graph_task_id() < 0:
         return None, None
-    if _TIED_TASK[0] != task:               # entries live for one backward pass (as _SHARED_ACT below)
-        _TIED.clear()
-        _TIED_TASK[0] = task
-        _GRAPH_GEN[0] += 1
+    hit = _TIED.get(param)
     uses = getattr(param, "_pv_uses", 0)
     if uses > 0:
         param._pv_uses = uses - 1           # this call consumes one of the forward's applications
-    key = (param.data_ptr(), param.numel())
-    hit = _TIED.get(key)
     if hit is not None:
         if uses <= 1:                       # the last contribution: nothing more will be added to the kept tensor
-            _TIED.pop(key, None)
-        return key, hit
-    return (key, None) if uses > 1 else (None, None)
+            _TIED.drop(param)
+        return param, hit
+    return (param, None) if uses > 1 else (None, None)
 
 
 def _tied_keep(key, grad) -> None:
     if key is not None:
-        _TIED[key] = grad
+        _TIED.put(key, grad)
 
 
 # the same for an ACTIVATION that several layers consume (the projected context of weight-tied cross-attention layers,
-# tagged `_pv_shared` by its producer): entries live for one backward pass only -- they are dropped as soon as another pass
-# is seen, so no gradient tensor outlives its step here
-_SHARED_ACT = {}
-_SHARED_ACT_TASK = [-1]
+# tagged `_pv_shared` by its producer).  Not held: the keys are forward activations that all exist before the pass starts,
+# so they cannot alias, and holding one would keep the projected context alive a step longer
+_SHARED_ACT = PassTable()
 
 
 def mark_shared(t: torch.Tensor) -> torch.Tensor:
@@ -75,14 +65,9 @@ def mark_shared(t: torch.Tensor) -> torch.Tensor:
 
 
 def _shared_activation_slot(t: torch.Tensor):
-    task = torch._C._current_graph_task_id()
-    if not ACCUMULATE_TIED_GRADS or task < 0 or not getattr(t, "_pv_shared", False):
+    if not ACCUMULATE_TIED_GRADS or torch._C._current_graph_task_id() < 0 or not getattr(t, "_pv_shared", False):
         return None, None
-    if _SHARED_ACT_TASK[0] != task:
-        _SHARED_ACT.clear()
-        _SHARED_ACT_TASK[0] = task
-    key = (t.data_ptr(), t.numel())
-    return key, _SHARED_ACT.get(key)
+    return t, _SHARED_ACT.get(t)
 
 
 # Operand precision of every linear() issued while the flag is set: "bf16" = both operands rounded once to bf16, one
@@ -403,7 +388,7 @@ class AttentionCoreF32(torch.autograd.Function):
                 return dq, None, None, None, None
             dq, dkv = K.attention_bwd(q, kv, out, dout.contiguous(), lse, ctx.heads, ctx.scale, bf16_operands=ctx.bf16)
             if key is not None:
-                _SHARED_ACT[key] = dkv
+                _SHARED_ACT.put(key, dkv, hold=False)
             return dq, dkv, None, None, None
         q, kv, p = ctx.saved_tensors
         h, inner = ctx.heads, q.shape[-1]
