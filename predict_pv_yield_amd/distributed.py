@@ -17,6 +17,8 @@ from typing import Dict
 import torch
 import torch.distributed as dist
 
+from . import _large_param as L
+
 
 def is_distributed() -> bool:
     """True when gradients / metrics must be exchanged.  PV_DIST_SINGLE_RANK=1 also counts an initialised ONE-rank group:
@@ -300,8 +302,8 @@ class OverlappedGradSync:
         if is_distributed():
             for p in self.large:
                 self._handles.append(p.register_post_accumulate_grad_hook(self._launch))
-                # side channel of functional.LinearBF16 (HipAdam large_grad_mode "bf16"): the bf16 gradient tensor is
-                # handed over the moment the wgrad kernel is enqueued
+                # side channel of functional.LinearBF16 (HipAdam large_grad_mode "bf16" / "sharded"): the bf16 gradient tensor is handed
+                # over the moment the wgrad kernel is enqueued.  On the parameter itself, not in its _large_param record
                 p._pv_on_grad = self._launch_tensor
 
     def _launch(self, p: torch.Tensor) -> None:
@@ -309,7 +311,8 @@ class OverlappedGradSync:
             self._pending.append(dist.all_reduce(p.grad, op=dist.ReduceOp.SUM, async_op=True))
 
     def _launch_tensor(self, g: torch.Tensor, param: torch.Tensor = None) -> None:
-        if param is not None and getattr(param, "_pv_grad_mode", None) == "sharded":
+        rec = L.large_of(param)
+        if rec is not None and rec.mode == "sharded":
             # ZeRO-1 for the big layer: this rank only needs the summed gradient of the rows it owns
             shard, work = reduce_scatter_rows(g)
             param._pv_grad_shard = shard
@@ -450,9 +453,9 @@ def negotiate_grad_sync(model: torch.nn.Module, optimizer, batch, mode: str, all
                   f" ({errors[-1] if errors else 'on another rank'}); trying the next simpler mode", flush=True)
         # drop whatever the failed attempt left behind, then make the replicas identical again
         for p in optimizer.large_params():
-            p._pv_pending = p._pv_grad_bf16 = p._pv_grad_shard = None
-            p._pv_kshard_pending = None
-            p._pv_shadow_work = None
+            L.clear_parked(p)               # (the rule of HipAdam.zero_grad(); the operand all-gather is discarded unwaited)
+            if L.large_of(p) is not None:
+                L.large_of(p).shadow_work = None
             if hasattr(p, "_pv_bf16_shadow"):
                 del p._pv_bf16_shadow
         optimizer._sharded_dirty = False

@@ -16,6 +16,7 @@ import ctypes
 import torch
 
 from . import hip_ops as K
+from . import _large_param as L
 from ._backward_pass import PassTable
 from ._lib import check, current_stream_ptr, get_lib, ptr
 
@@ -64,20 +65,19 @@ class LinearF32(torch.autograd.Function):
                 else:
                     dx = K.gemm(g, weight)
             owner = ctx.weight_param
-            earlier = getattr(owner, "_pv_pending_f32", None)
-            if (getattr(owner, "_pv_grad_mode", "autograd") == "fused" and getattr(owner, "_pv_takes_f32_pending", False)
-                    and x.shape[1] % 8 == 0 and x.shape[0] <= F32_PENDING_MAX_ROWS and x.is_contiguous() and earlier is None
-                    and owner.grad is None):
+            rec = L.large_of(owner)
+            earlier = rec.parked if rec is not None else None
+            if (rec is not None and rec.mode == "fused" and rec.takes_f32_pending and x.shape[1] % 8 == 0
+                    and x.shape[0] <= F32_PENDING_MAX_ROWS and x.is_contiguous() and earlier is None and owner.grad is None):
                 # HipAdam owns this parameter (single process): it forms the gradient inside its pass over p / m / v
                 # (pv_linear_wgrad_adam_f32): the 0.5 GB gradient is neither written nor read back
-                owner._pv_pending_f32 = (x, g)
+                rec.parked = (L.PAIR_F32, (x, g))
                 dw = None
             else:
-                if earlier is not None:
+                if earlier is not None and earlier[0] == L.PAIR_F32:
                     # a second backward before step() (gradient accumulation, several losses): the pair parked by the first one
                     # becomes an ordinary gradient now, and this call's joins it through autograd's accumulation
-                    x0, g0 = earlier
-                    owner._pv_pending_f32 = None
+                    (x0, g0), rec.parked = earlier[1], None
                     dw0 = K.gemm(g0.t(), x0)
                     owner.grad = dw0 if owner.grad is None else owner.grad + dw0
                 dw = K.gemm(g.t(), x)
@@ -151,7 +151,7 @@ def split2_conv_weight(weight: torch.Tensor):
 def drop_derived_copies(p: torch.Tensor) -> None:
     """Forget every operand copy derived from p's value and cached on it (conv fragment images, the f16x2 split, the bf16
     shadow): each is rebuilt from p on its next use.  For writes that `_version` cannot see (through `.data` or raw pointers).
-    The fc1 column shard (`_pv_kshard`) is optimiser state, not a copy: HipAdam owns it."""
+    The fc1 column shard (`_large_param.LargeParam.kshard`) is optimiser state, not a copy: HipAdam owns it."""
     for name in ("_pv_packed", "_pv_split2", "_pv_bf16_shadow", "_pv_bf16_shadow_version"):
         if getattr(p, name, None) is not None:
             setattr(p, name, None)
@@ -262,10 +262,10 @@ def conv3d_first_layer_bf16(x, weight, bias, padding=(0, 0, 0), relu=True, dy_pr
 
 def bf16_shadow_of(weight: torch.Tensor) -> torch.Tensor:
     """bf16 copy of a big f32 parameter, kept current by HipAdam (pv_adam_step_f32 writes it)."""
-    work = getattr(weight, "_pv_shadow_work", None)
-    if work is not None:      # all-gather of the row shards other ranks updated (HipAdam "sharded"): stream-level wait
-        work.wait()
-        weight._pv_shadow_work = None
+    rec = L.large_of(weight)
+    if rec is not None and rec.shadow_work is not None:
+        rec.shadow_work.wait()      # all-gather of the row shards other ranks updated (HipAdam "sharded"): stream-level wait
+        rec.shadow_work = None
     shadow = getattr(weight, "_pv_bf16_shadow", None)
     version = getattr(weight, "_pv_bf16_shadow_version", None)
     if shadow is None or shadow.device != weight.device or version != weight._version:
@@ -311,11 +311,11 @@ class LinearBF16(torch.autograd.Function):
         x, wb, y = ctx.saved_tensors
         dy = dy.contiguous()
         weight = ctx.weight_param
-        mode = getattr(weight, "_pv_grad_mode", "autograd")
+        rec = L.large_of(weight)
+        mode = rec.mode if rec is not None else "autograd"
         if mode == "fused":
-            fused = getattr(weight, "_pv_fused_backward", None)
-            out = (fused(x, dy, y, ctx.needs_input_grad[0], ctx.has_bias, gate_dx=ctx.x_is_relu_output)
-                   if fused is not None else None)
+            out = (rec.fused_backward(x, dy, y, ctx.needs_input_grad[0], ctx.has_bias, gate_dx=ctx.x_is_relu_output)
+                   if rec.fused_backward is not None else None)
             if out is not None:
                 # HipAdam owns this parameter (single process): dx, db, the weight gradient and its Adam update came out of
                 # ONE pass over the matrix; nothing is left for step()
@@ -331,11 +331,10 @@ class LinearBF16(torch.autograd.Function):
         if mode == "fused":
             # HipAdam owns this parameter (single process): hand it (x, dy, relu mask); the weight gradient is formed
             # inside the optimiser's pass over p/m/v and never written to memory
-            eager = getattr(weight, "_pv_eager_update", None)
-            if eager is not None:
-                eager(x, dy, y)     # HBM-bound update starts now, on a side stream, under the MFMA-bound conv backward
+            if rec.eager_update is not None:
+                rec.eager_update(x, dy, y)     # HBM-bound update starts now, on a side stream, under the MFMA-bound conv backward
             else:
-                weight._pv_pending = (x, dy, y)
+                rec.parked = (L.OPERANDS_BF16, (x, dy, y))
         elif mode in ("bf16", "sharded"):
             # data parallel: the gradient is written once in bf16 and handed to the gradient-sync callback right
             # away, so its exchange (99.9 % of the bytes of the step) runs under the conv backward that follows.
@@ -343,14 +342,12 @@ class LinearBF16(torch.autograd.Function):
             # own rows and the bf16 operand copy is all-gathered afterwards (HipAdam)
             gb = K.linear_wgrad_bf16out(x, dy, y, weight.shape[0])
             cb = getattr(weight, "_pv_on_grad", None)
-            if mode == "bf16":
-                weight._pv_grad_bf16 = gb
+            if mode == "bf16" or cb is None:    # ("sharded" without a callback: single process, nothing to scatter)
+                rec.parked = (L.GRAD_BF16, gb)
                 if cb is not None:
                     cb(gb)
-            elif cb is not None:
-                cb(gb, weight)              # sets weight._pv_grad_shard
             else:
-                weight._pv_grad_bf16 = gb   # single process: nothing to scatter
+                cb(gb, weight)              # (leaves this rank's rows of the sum on the parameter for step())
         return dx, dw, (db if ctx.has_bias else None), None, None
 
 
@@ -368,7 +365,7 @@ class LinearBF16KSharded(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, relu, x_is_relu_output=False):
         from . import distributed as D
-        ks = weight._pv_kshard
+        ks = L.large_of(weight).kshard
         x_cols = D.all_to_all_columns(x.contiguous())
         partial = K.linear_fwd_bf16(x_cols, ks["shadow"], None, False)
         y = K.scale_bias_relu_f32(D.reduce_scatter_sample_rows(partial), bias.contiguous() if bias is not None else None, 1.0, relu)
@@ -382,11 +379,10 @@ class LinearBF16KSharded(torch.autograd.Function):
         from . import distributed as D
         x_cols, y = ctx.saved_tensors
         has_bias, x_is_relu_output, b_local = ctx.cfg
-        weight = ctx.weight_param
-        ks = weight._pv_kshard
+        rec = L.large_of(ctx.weight_param)
+        ks, one_pass = rec.kshard, rec.kshard_backward
         g = K.relu_gate_f32(dy.contiguous(), y) if y is not None else dy.contiguous()
         g_all = D.all_gather_sample_rows(g)
-        one_pass = getattr(weight, "_pv_kshard_backward", None)
         dx_cols = one_pass(x_cols, g_all, ctx.needs_input_grad[0], x_is_relu_output) if one_pass is not None else None
         if dx_cols is not None:
             # dx of every sample for this rank's columns AND the Adam update of the shard came out of ONE pass over it
@@ -401,10 +397,10 @@ class LinearBF16KSharded(torch.autograd.Function):
             dx = D.all_to_all_rows_back(dx_cols)
             if x_is_relu_output:
                 _mark_pregated(dx)
-        if getattr(weight, "_pv_kshard_pending", None) is not None:
+        if rec.parked is not None:
             raise RuntimeError("K-sharded fc1: backward() ran twice without optimizer.step() in between (gradient accumulation "
                                "needs another large_grad_mode)")
-        weight._pv_kshard_pending = (x_cols, g_all)
+        rec.parked = (L.PAIR_KSHARD, (x_cols, g_all))
         return dx, None, (K.colsum(g) if has_bias else None), None, None
 
 
@@ -431,7 +427,8 @@ def _recut_kshard_weight(weight: torch.Tensor, ks: dict) -> None:
 
 
 def linear_bf16(x, weight, bias, relu=False, x_is_relu_output=False):
-    ks = getattr(weight, "_pv_kshard", None) if getattr(weight, "_pv_grad_mode", None) == "ksharded" else None
+    rec = L.large_of(weight)
+    ks = rec.kshard if rec is not None and rec.mode == "ksharded" else None
     if ks is not None:
         if ks.get("version") != weight._version:
             _recut_kshard_weight(weight, ks)

@@ -11,9 +11,12 @@ round-trips (`exp_avg`, `exp_avg_sq`, `step`: the same keys torch.optim.Adam use
 interchange).  Parameters that carry a `_pv_bf16_shadow` (fc1 in the bf16 path) get the shadow rewritten in
 the same pass.  `grad_scale` folds the 1/world_size of a summing gradient all-reduce into the update.
 """
+from functools import partial
+
 import torch
 
 from . import hip_ops as K
+from . import _large_param as L
 
 
 # Single process, "fused" mode: fc1's whole backward (dx, db, weight gradient, Adam) runs as ONE pass over the matrix,
@@ -47,6 +50,8 @@ class HipAdam(torch.optim.Optimizer):
     #             "autograd" -- plain f32 .grad.
     #             "sharded" -- bf16 gradient, reduce-scatter over rows, Adam on this rank's rows, all-gather of the operand copy;
     #             "ksharded" -- fc1's COLUMNS dealt over the ranks: activations are exchanged, no weight or gradient is.
+    # The mode, what backward() parked for step(), the in-backward entry points and the column shard of such a matrix are ONE
+    # record on the parameter, shared with the glue (_large_param.LargeParam).
     FUSE_MIN_NUMEL = 1 << 22
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, fuse_large_linear=True, overlap_large_update=False,
@@ -70,10 +75,6 @@ class HipAdam(torch.optim.Optimizer):
         self.overlap_large_update = overlap_large_update
         self._side_stream = None
         self._inflight = []
-        for p in self.large_params():
-            # a column shard left on the parameter by another optimiser (an earlier fit, a resume) holds THAT optimiser's
-            # weights, moments and step: this one cuts its own from its own state (set_large_grad_mode("ksharded"))
-            p._pv_kshard = None
         self.set_large_grad_mode("fused" if fuse_large_linear else "autograd")
 
     def _advance_device_scalars(self, device) -> torch.Tensor:
@@ -105,7 +106,7 @@ class HipAdam(torch.optim.Optimizer):
         return [p for g in self.param_groups for p in g["params"] if p.dim() == 2 and p.numel() >= self.FUSE_MIN_NUMEL]
 
     def set_large_grad_mode(self, mode: str) -> None:
-        if mode not in ("fused", "bf16", "sharded", "ksharded", "autograd"):
+        if mode not in L.MODES:
             raise ValueError(mode)
         if getattr(self, "_layout_frozen", False) and mode != getattr(self, "large_grad_mode", mode):
             raise RuntimeError("HipAdam.set_large_grad_mode(): a captured HIP graph holds this optimiser's state tensors and the "
@@ -114,8 +115,6 @@ class HipAdam(torch.optim.Optimizer):
             # (collective, a no-op unless sharded steps were taken) the row / column shards hold the truth: back into the full
             # tensors before another mode reads them, or before "ksharded" cuts its shard again from them
             self.consolidate_sharded()
-            for p in self.large_params():
-                p._pv_kshard = None
         if mode == "ksharded":
             from . import distributed as D
             if self.capturable or not D.is_distributed() or any(
@@ -128,21 +127,17 @@ class HipAdam(torch.optim.Optimizer):
         self.large_grad_mode = mode
         self._moments_rows()
         for p in self.large_params():
+            rec = L.reset(p, mode, takes_f32_pending=(mode == "fused" and not self.capturable))
+            # (a column shard cut earlier -- by this optimiser, or by another one on the same parameter, from THAT one's state -- is
+            # never reused: "ksharded" cuts from the full tensors as they stand)
+            rec.kshard = None
             if mode == "ksharded":
-                self._make_column_shard(p)      # always from the full tensors as they stand: never a shard cut earlier
-            else:
-                p._pv_kshard = None
-            p._pv_grad_mode = mode
-            p._pv_kshard_pending = None
-            p._pv_kshard_backward = self._make_kshard_backward(p) if mode == "ksharded" else None
-            p._pv_pending = None
-            p._pv_pending_f32 = None
-            p._pv_takes_f32_pending = mode == "fused" and not self.capturable
-            p._pv_grad_bf16 = None
-            p._pv_grad_shard = None
-            p._pv_eager_update = self._make_eager_update(p) if (mode == "fused" and self.overlap_large_update) else None
-            p._pv_fused_backward = self._make_fused_backward(p) if (mode == "fused" and not self.overlap_large_update) else None
-            p._pv_applied = False
+                self._make_column_shard(p)
+                rec.kshard_backward = partial(self._kshard_backward, p)
+            elif mode == "fused" and self.overlap_large_update:
+                rec.eager_update = partial(self._eager_update, p)
+            elif mode == "fused":
+                rec.fused_backward = partial(self._fused_backward, p)
 
     def _make_column_shard(self, p) -> None:
         """large_grad_mode "ksharded": this rank's COLUMNS of p as contiguous tensors of their own -- f32 master, bf16 operand
@@ -159,7 +154,7 @@ class HipAdam(torch.optim.Optimizer):
                   "exp_avg": (st["exp_avg"][:, k0:k1].contiguous() if "exp_avg" in st else torch.zeros_like(w)),
                   "exp_avg_sq": (st["exp_avg_sq"][:, k0:k1].contiguous() if "exp_avg_sq" in st else torch.zeros_like(w)),
                   "step": int(st["step"].item()) if "step" in st else 0, "version": p._version}
-        p._pv_kshard = ks
+        L.large_of(p).kshard = ks
 
     def consolidate_sharded(self) -> None:
         """After sharded steps every rank holds current f32 values (parameter, exp_avg, exp_avg_sq) only for the rows
@@ -171,8 +166,9 @@ class HipAdam(torch.optim.Optimizer):
         from . import distributed as D
         if D.is_distributed():
             for p in self.large_params():
-                ks = getattr(p, "_pv_kshard", None)
-                if getattr(p, "_pv_grad_mode", None) == "ksharded" and ks is not None:
+                rec = L.large_of(p)
+                mode, ks = (rec.mode, rec.kshard) if rec is not None else ("autograd", None)
+                if mode == "ksharded" and ks is not None:
                     st = self._init_state(p)
                     with torch.no_grad():
                         D.all_gather_columns(ks["w"], p.data)
@@ -182,7 +178,7 @@ class HipAdam(torch.optim.Optimizer):
                     from .functional import drop_derived_copies
                     drop_derived_copies(p)      # (the full operand copy, if any mode built one earlier, is stale)
                     continue
-                if getattr(p, "_pv_grad_mode", None) != "sharded":
+                if mode != "sharded":
                     continue
                 st = self.state.get(p, {})
                 for t in (p.data, st.get("exp_avg"), st.get("exp_avg_sq")):
@@ -369,98 +365,90 @@ class HipAdam(torch.optim.Optimizer):
             self._k_channels(p)      # copies the parameter's layout mark onto exp_avg
         return st
 
-    def _make_eager_update(self, p):
-        def eager(x, dy, y):
-            from .functional import bf16_shadow_of
-            group = self._group_of(p)
-            with torch.no_grad():
-                st = self._init_state(p)
-                self._moments_rows(p)
-                shadow = bf16_shadow_of(p)
-                st["step"] += 1
-                main = torch.cuda.current_stream(p.device)
-                if self._side_stream is None:
-                    self._side_stream = torch.cuda.Stream(device=p.device)
-                ready = main.record_event()            # dx (which reads the pre-update weights) is queued before this
-                self._side_stream.wait_event(ready)
-                with torch.cuda.stream(self._side_stream):
-                    K.linear_wgrad_adam_bf16(x, dy, y, p, st["exp_avg"], st["exp_avg_sq"], shadow, int(st["step"].item()),
-                                             lr=group["lr"], betas=group["betas"], eps=group["eps"])
-                    done = self._side_stream.record_event()
-                self._inflight.append((done, (x, dy, y)))   # keep the operands alive until step() has waited
-        return eager
+    def _eager_update(self, p, x, dy, y):
+        from .functional import bf16_shadow_of
+        group = self._group_of(p)
+        with torch.no_grad():
+            st = self._init_state(p)
+            self._moments_rows(p)
+            shadow = bf16_shadow_of(p)
+            st["step"] += 1
+            main = torch.cuda.current_stream(p.device)
+            if self._side_stream is None:
+                self._side_stream = torch.cuda.Stream(device=p.device)
+            ready = main.record_event()            # dx (which reads the pre-update weights) is queued before this
+            self._side_stream.wait_event(ready)
+            with torch.cuda.stream(self._side_stream):
+                K.linear_wgrad_adam_bf16(x, dy, y, p, st["exp_avg"], st["exp_avg_sq"], shadow, int(st["step"].item()),
+                                         lr=group["lr"], betas=group["betas"], eps=group["eps"])
+                done = self._side_stream.record_event()
+            self._inflight.append((done, (x, dy, y)))   # keep the operands alive until step() has waited
 
-    def _make_fused_backward(self, p):
-        def fused(x, dy, y, need_dx, need_db, gate_dx=False):
-            """(dx, db) of the layer, with the Adam update of p applied in the same pass; None if the shape is not covered
-            (the caller then takes the two-kernel path) or the switch is off."""
-            from .functional import bf16_shadow_of
-            if not FUSE_DX_INTO_UPDATE or not need_dx or not K.fused_dx_update_supported(x.shape[0], p.shape[0], p.shape[1],
-                                                                                         self.capturable):
-                return None
-            if p._pv_applied:
-                raise RuntimeError("HipAdam: backward() ran twice without optimizer.step() in between; the fused fc1 pass has "
-                                   "already applied the first update (gradient accumulation needs HipAdam(fuse_large_linear="
-                                   "False))")
-            group = self._group_of(p)
-            with torch.no_grad():
-                self._ensure_device_state(p.device)
-                st = self._init_state(p)
-                tiled = self._moments_tiled(p)
-                st["step"] += 1
-                if x.shape[0] > 32:
-                    # more than 32 rows (a per-GPU batch of 64, the one-GPU form of a global batch of 512): the row-block form of the
-                    # same pass -- the gated output gradient as operand fragments, gradient tile on the matrix cores
-                    g = K.relu_gate_f32(dy, y) if y is not None else dy
-                    db = K.colsum(g) if need_db else None
-                    dx = K.linear_wgrad_dx_adam_tall_bf16(x, g, p, st["exp_avg"], st["exp_avg_sq"], bf16_shadow_of(p),
-                                                          int(st["step"].item()), lr=group["lr"], betas=group["betas"],
-                                                          eps=group["eps"], grad_scale=1.0, need_dx=True, gate_dx_by_x=gate_dx,
-                                                          moments_tiled=tiled)
-                    out = (dx, db) if need_db else dx
-                elif self.capturable:
-                    out = K.linear_wgrad_dx_adam_dev_bf16(x, dy, y, p, st["exp_avg"], st["exp_avg_sq"], bf16_shadow_of(p),
-                                                          self._advance_device_scalars(p.device), need_db=need_db,
-                                                          gate_dx_by_x=gate_dx, moments_tiled=tiled)
-                else:
-                    out = K.linear_wgrad_dx_adam_bf16(x, dy, y, p, st["exp_avg"], st["exp_avg_sq"], bf16_shadow_of(p),
+    def _fused_backward(self, p, x, dy, y, need_dx, need_db, gate_dx=False):
+        """(dx, db) of the layer, with the Adam update of p applied in the same pass; None if the shape is not covered
+        (the caller then takes the two-kernel path) or the switch is off."""
+        from .functional import bf16_shadow_of
+        if not FUSE_DX_INTO_UPDATE or not need_dx or not K.fused_dx_update_supported(x.shape[0], p.shape[0], p.shape[1],
+                                                                                     self.capturable):
+            return None
+        rec = L.large_of(p)
+        if rec.applied:
+            raise RuntimeError("HipAdam: backward() ran twice without optimizer.step() in between; the fused fc1 pass has "
+                               "already applied the first update (gradient accumulation needs HipAdam(fuse_large_linear="
+                               "False))")
+        group = self._group_of(p)
+        with torch.no_grad():
+            self._ensure_device_state(p.device)
+            st = self._init_state(p)
+            tiled = self._moments_tiled(p)
+            st["step"] += 1
+            if x.shape[0] > 32:
+                # more than 32 rows (a per-GPU batch of 64, the one-GPU form of a global batch of 512): the row-block form of the
+                # same pass -- the gated output gradient as operand fragments, gradient tile on the matrix cores
+                g = K.relu_gate_f32(dy, y) if y is not None else dy
+                db = K.colsum(g) if need_db else None
+                dx = K.linear_wgrad_dx_adam_tall_bf16(x, g, p, st["exp_avg"], st["exp_avg_sq"], bf16_shadow_of(p),
                                                       int(st["step"].item()), lr=group["lr"], betas=group["betas"],
-                                                      eps=group["eps"], need_dx=True, need_db=need_db, gate_dx_by_x=gate_dx,
+                                                      eps=group["eps"], grad_scale=1.0, need_dx=True, gate_dx_by_x=gate_dx,
                                                       moments_tiled=tiled)
-            p._pv_applied = True
-            return out if need_db else (out, None)
-        return fused
+                out = (dx, db) if need_db else dx
+            elif self.capturable:
+                out = K.linear_wgrad_dx_adam_dev_bf16(x, dy, y, p, st["exp_avg"], st["exp_avg_sq"], bf16_shadow_of(p),
+                                                      self._advance_device_scalars(p.device), need_db=need_db,
+                                                      gate_dx_by_x=gate_dx, moments_tiled=tiled)
+            else:
+                out = K.linear_wgrad_dx_adam_bf16(x, dy, y, p, st["exp_avg"], st["exp_avg_sq"], bf16_shadow_of(p),
+                                                  int(st["step"].item()), lr=group["lr"], betas=group["betas"],
+                                                  eps=group["eps"], need_dx=True, need_db=need_db, gate_dx_by_x=gate_dx,
+                                                  moments_tiled=tiled)
+        rec.applied = True
+        return out if need_db else (out, None)
 
-    def _make_kshard_backward(self, p):
-        def one_pass(x_cols, g_all, need_dx, gate_dx):
-            """K-sharded fc1: dx_cols, with the Adam update of this rank's column shard applied in the same pass
-            (pv_linear_wgrad_dx_adam_tall_bf16); None if the shape is not covered (the caller then parks the pair for step())."""
-            ks = p._pv_kshard
-            if not need_dx or not K.kshard_one_pass_supported(ks["w"].shape[0], ks["w"].shape[1]):
-                return None
-            if p._pv_applied:
-                raise RuntimeError("HipAdam: backward() ran twice without optimizer.step() in between; the K-sharded fc1 pass has "
-                                   "already applied the first update (gradient accumulation needs another large_grad_mode)")
-            group = self._group_of(p)
-            with torch.no_grad():
-                ks["step"] += 1
-                dx = K.linear_wgrad_dx_adam_tall_bf16(x_cols, g_all, ks["w"], ks["exp_avg"], ks["exp_avg_sq"], ks["shadow"], ks["step"],
-                                                      lr=group["lr"], betas=group["betas"], eps=group["eps"],
-                                                      grad_scale=self.grad_scale, need_dx=True, gate_dx_by_x=gate_dx)
-            p._pv_applied = True
-            self._sharded_dirty = True
-            return dx
-        return one_pass
+    def _kshard_backward(self, p, x_cols, g_all, need_dx, gate_dx):
+        """K-sharded fc1: dx_cols, with the Adam update of this rank's column shard applied in the same pass
+        (pv_linear_wgrad_dx_adam_tall_bf16); None if the shape is not covered (the caller then parks the pair for step())."""
+        rec = L.large_of(p)
+        ks = rec.kshard
+        if not need_dx or not K.kshard_one_pass_supported(ks["w"].shape[0], ks["w"].shape[1]):
+            return None
+        if rec.applied:
+            raise RuntimeError("HipAdam: backward() ran twice without optimizer.step() in between; the K-sharded fc1 pass has "
+                               "already applied the first update (gradient accumulation needs another large_grad_mode)")
+        group = self._group_of(p)
+        with torch.no_grad():
+            ks["step"] += 1
+            dx = K.linear_wgrad_dx_adam_tall_bf16(x_cols, g_all, ks["w"], ks["exp_avg"], ks["exp_avg_sq"], ks["shadow"], ks["step"],
+                                                  lr=group["lr"], betas=group["betas"], eps=group["eps"],
+                                                  grad_scale=self.grad_scale, need_dx=True, gate_dx_by_x=gate_dx)
+        rec.applied = True
+        self._sharded_dirty = True
+        return dx
 
     def zero_grad(self, set_to_none: bool = True):
         """Also drops what a backward() parked on the large matrices for a step() that never came (a skipped step would otherwise
         keep the activations alive and apply a stale gradient later)."""
         for p in self.large_params():
-            p._pv_pending = None
-            p._pv_pending_f32 = None
-            p._pv_grad_bf16 = None
-            p._pv_grad_shard = None
-            p._pv_kshard_pending = None
+            L.clear_parked(p)
         return super().zero_grad(set_to_none=set_to_none)
 
     def _wait_inflight(self):
@@ -484,24 +472,23 @@ class HipAdam(torch.optim.Optimizer):
             first = next((p for g in self.param_groups for p in g["params"] if p.is_cuda), None)
             if first is not None:
                 self._ensure_device_state(first.device)
-        for p in self.large_params():
-            p._pv_applied = False          # the update of this step was applied from inside backward
         for group in self.param_groups:
             plain = {}      # step count -> [(param, grad, exp_avg, exp_avg_sq, bf16 shadow)]: one multi-tensor launch each
             stepped = []
             for p in group["params"]:
-                pending = getattr(p, "_pv_pending", None)
-                pending32 = getattr(p, "_pv_pending_f32", None)
-                gb = getattr(p, "_pv_grad_bf16", None)
-                gs = getattr(p, "_pv_grad_shard", None)
-                kpend = getattr(p, "_pv_kshard_pending", None)
-                if kpend is not None and p.grad is None:
-                    # K-sharded fc1: the gradient of THIS RANK'S COLUMNS over the whole global batch, formed and applied in
-                    # one pass over the shard's p / m / v (no gradient tensor, no exchange: functional.LinearBF16KSharded
-                    # parked the exchanged activations and the all-gathered output gradients)
-                    x_cols, g_full = kpend
-                    p._pv_kshard_pending = None
-                    ks = p._pv_kshard
+                rec = L.large_of(p)
+                kind = payload = None
+                if rec is not None:
+                    rec.applied = False          # the update of this step was applied from inside backward
+                    gs = getattr(p, "_pv_grad_shard", None)     # (the fifth kind: left on the parameter by the gradient-sync callback)
+                    kind, payload = rec.parked or ((L.GRAD_SHARD, gs) if gs is not None else (None, None))
+                take = kind is not None and p.grad is None      # (with a .grad the plain path runs; the entry stays until zero_grad())
+                if take and kind == L.PAIR_KSHARD:
+                    # K-sharded fc1: the gradient of THIS RANK'S COLUMNS over the whole global batch, formed from the exchanged
+                    # activations and the all-gathered output gradients inside one pass over the shard's p / m / v
+                    x_cols, g_full = payload
+                    L.clear_parked(p)
+                    ks = rec.kshard
                     ks["step"] += 1
                     if self.grad_scale != 1.0:
                         g_full = K.scale_f32(g_full, self.grad_scale)
@@ -509,54 +496,43 @@ class HipAdam(torch.optim.Optimizer):
                                              ks["step"], lr=group["lr"], betas=group["betas"], eps=group["eps"])
                     self._sharded_dirty = True
                     continue
-                if p.grad is None and pending is None and pending32 is None and gb is None and gs is None:
+                if p.grad is None and kind is None:
                     continue
                 if not p.is_cuda:
                     raise RuntimeError("HipAdam steps parameters on the MI355X only (no CPU path)")
                 st = self._init_state(p)
                 self._moments_rows(p)       # (a no-op unless an earlier step of p went through the one-pass backward)
                 st["step"] += 1
-                if self.capturable and (pending is not None or gs is not None or gb is not None):
+                if self.capturable and kind in (L.OPERANDS_BF16, L.GRAD_SHARD, L.GRAD_BF16):
                     raise NotImplementedError("HipAdam(capturable=True) covers the single-process paths (fc1's one-pass "
                                               "backward + the multi-tensor step); not the deferred / exchanged fc1 gradients")
-                if pending32 is not None and p.grad is None:
-                    # the f32 model's fc1 (functional.LinearF32): gradient from the f32 activations + Adam in one pass
-                    x, g = pending32
-                    p._pv_pending_f32 = None
-                    K.linear_wgrad_adam_f32(x, g, None, p, st["exp_avg"], st["exp_avg_sq"], int(st["step"].item()),
-                                            lr=group["lr"], betas=group["betas"], eps=group["eps"])
-                    if getattr(p, "_pv_bf16_shadow", None) is not None:
-                        p._pv_bf16_shadow = None      # (a bf16 operand copy from an earlier bf16 forward is stale now)
-                    continue
-                if pending is not None and p.grad is None:
+                if take:
                     from .functional import bf16_shadow_of
-                    x, dy, y = pending
-                    p._pv_pending = None
-                    K.linear_wgrad_adam_bf16(x, dy, y, p, st["exp_avg"], st["exp_avg_sq"], bf16_shadow_of(p),
-                                             int(st["step"].item()), lr=group["lr"], betas=group["betas"], eps=group["eps"])
-                    continue
-                if gs is not None and p.grad is None:
-                    # sharded update (data parallel): Adam over this rank's rows only, then every rank's bf16 operand
-                    # rows are all-gathered; the gather is waited for by the next forward (functional.bf16_shadow_of),
-                    # so it runs under the next step's conv forward.  f32 rows owned by other ranks go stale until
-                    # consolidate_sharded().
-                    from . import distributed as D
-                    from .functional import bf16_shadow_of
-                    p._pv_grad_shard = None
-                    r0, r1 = D.row_shard(p.shape[0])
-                    shadow = bf16_shadow_of(p)
-                    K.adam_step_bf16grad(p[r0:r1], gs, st["exp_avg"][r0:r1], st["exp_avg_sq"][r0:r1],
-                                         int(st["step"].item()), lr=group["lr"], betas=group["betas"], eps=group["eps"],
-                                         bf16_shadow=shadow[r0:r1], grad_scale=self.grad_scale)
-                    p._pv_shadow_work = D.all_gather_rows(shadow)
-                    self._sharded_dirty = True
-                    continue
-                if gb is not None and p.grad is None:
-                    from .functional import bf16_shadow_of
-                    p._pv_grad_bf16 = None
-                    K.adam_step_bf16grad(p, gb, st["exp_avg"], st["exp_avg_sq"], int(st["step"].item()), lr=group["lr"],
-                                         betas=group["betas"], eps=group["eps"], bf16_shadow=bf16_shadow_of(p),
-                                         grad_scale=self.grad_scale)
+                    L.clear_parked(p)
+                    if kind == L.PAIR_F32:
+                        # the f32 model's fc1 (functional.LinearF32): gradient from the f32 activations + Adam in one pass
+                        K.linear_wgrad_adam_f32(*payload, None, p, st["exp_avg"], st["exp_avg_sq"], int(st["step"].item()),
+                                                lr=group["lr"], betas=group["betas"], eps=group["eps"])
+                        if getattr(p, "_pv_bf16_shadow", None) is not None:
+                            p._pv_bf16_shadow = None      # (a bf16 operand copy from an earlier bf16 forward is stale now)
+                    elif kind == L.OPERANDS_BF16:
+                        K.linear_wgrad_adam_bf16(*payload, p, st["exp_avg"], st["exp_avg_sq"], bf16_shadow_of(p),
+                                                 int(st["step"].item()), lr=group["lr"], betas=group["betas"], eps=group["eps"])
+                    elif kind == L.GRAD_SHARD:
+                        # Adam over this rank's rows only, then every rank's bf16 operand rows are all-gathered under the next
+                        # step's conv forward (functional.bf16_shadow_of waits); other ranks' f32 rows: consolidate_sharded()
+                        from . import distributed as D
+                        r0, r1 = D.row_shard(p.shape[0])
+                        shadow = bf16_shadow_of(p)
+                        K.adam_step_bf16grad(p[r0:r1], payload, st["exp_avg"][r0:r1], st["exp_avg_sq"][r0:r1],
+                                             int(st["step"].item()), lr=group["lr"], betas=group["betas"], eps=group["eps"],
+                                             bf16_shadow=shadow[r0:r1], grad_scale=self.grad_scale)
+                        rec.shadow_work = D.all_gather_rows(shadow)
+                        self._sharded_dirty = True
+                    else:       # L.GRAD_BF16
+                        K.adam_step_bf16grad(p, payload, st["exp_avg"], st["exp_avg_sq"], int(st["step"].item()), lr=group["lr"],
+                                             betas=group["betas"], eps=group["eps"], bf16_shadow=bf16_shadow_of(p),
+                                             grad_scale=self.grad_scale)
                     continue
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 stepped.append(p)

@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from predict_pv_yield_amd import distributed as D
+from predict_pv_yield_amd._large_param import large_of
 from predict_pv_yield_amd.models.conv3d.model import Model
 from predict_pv_yield_amd.optim import HipAdam
 
@@ -98,7 +99,7 @@ def _mode_probe(model):
         seen = []
 
         def on_train_epoch_end(self, trainer, module):
-            self.seen.append((trainer.optimizers[0].large_grad_mode, getattr(model.fc1.weight, "_pv_kshard", None) is not None))
+            self.seen.append((trainer.optimizers[0].large_grad_mode, large_of(model.fc1.weight).kshard is not None))
     return ModeProbe()
 
 
@@ -112,8 +113,8 @@ def case_after_fit(rank, world, dev, out_path):
     trainer = pl.Trainer(gpus=1, max_epochs=1, large_grad_mode="ksharded", callbacks=[probe])
     trainer.fit(model, [_rank_batch(dev, s) for s in (7, 8)])
     w = model.fc1.weight
-    out = {"during": probe.seen, "kshard_after": getattr(w, "_pv_kshard", None) is not None,
-           "grad_mode_after": getattr(w, "_pv_grad_mode", None)}
+    out = {"during": probe.seen, "kshard_after": large_of(w).kshard is not None,
+           "grad_mode_after": large_of(w).mode}
     torch.distributed.barrier()
     if rank == 0 and not out["kshard_after"] and out["grad_mode_after"] != "ksharded":
         # rank-local inference (a load of the best checkpoint, test, predict on one rank) against a cold twin that has
@@ -139,7 +140,7 @@ def case_nan(rank, world, dev, out_path):
 
         def __iter__(self):
             yield _rank_batch(dev, 7)
-            ks = model.fc1.weight._pv_kshard     # (the first step has been queued: the copies below follow it on the stream)
+            ks = large_of(model.fc1.weight).kshard     # (the first step has been queued: the copies below follow it on the stream)
             out["before"] = {k: (ks[k].cpu().clone() if torch.is_tensor(ks[k]) else ks[k])
                              for k in ("w", "shadow", "exp_avg", "exp_avg_sq", "step")}
             yield _rank_batch(dev, 8, nan=True)
@@ -151,7 +152,7 @@ def case_nan(rank, world, dev, out_path):
     except ValueError as e:
         out["raised"] = str(e)
     torch.cuda.synchronize()
-    ks = model.fc1.weight._pv_kshard
+    ks = large_of(model.fc1.weight).kshard
     out["after"] = {k: (ks[k].cpu().clone() if torch.is_tensor(ks[k]) else ks[k])
                     for k in ("w", "shadow", "exp_avg", "exp_avg_sq", "step")}
     out["mode"] = trainer.optimizers[0].large_grad_mode

@@ -23,6 +23,7 @@ import pytest
 import torch
 
 from conftest import ref_order
+from predict_pv_yield_amd._large_param import PAIR_F32, large_of
 
 from oracle import conv3d_oracle as co
 from oracle import flow_oracle as fo
@@ -79,7 +80,7 @@ def test_headline_size_engages_the_production_kernels(device):
     _, model = _pair("bf16", device)
     assert model.cnn_output_size == 1_003_520 and model.fc1.weight.numel() >= HipAdam.FUSE_MIN_NUMEL
     opt = model.configure_optimizers()
-    assert opt.large_grad_mode == "fused" and model.fc1.weight._pv_grad_mode == "fused"
+    assert opt.large_grad_mode == "fused" and large_of(model.fc1.weight).mode == "fused"
     assert model._bf16_supported()
 
 
@@ -174,7 +175,7 @@ def test_bf16_adam_steps_with_the_fused_fc1_kernel(device, emulate):
         loss = model.training_step(batch, 0)
         loss.backward()
         # the fused path is live: no gradient tensor; the single-pass kernel applied the update from inside backward
-        assert model.fc1.weight.grad is None and model.fc1.weight._pv_applied
+        assert model.fc1.weight.grad is None and large_of(model.fc1.weight).applied
         opt.step()
         losses.append(float(loss))
         if step == 0:
@@ -228,7 +229,7 @@ def test_fused_fc1_backward_takes_more_than_32_rows_through_the_row_block_kernel
             loss = model.training_step(b, 0)
             loss.backward()
             if fused:
-                assert model.fc1.weight._pv_applied and model.fc1.weight.grad is None
+                assert large_of(model.fc1.weight).applied and model.fc1.weight.grad is None
             opt.step()
             losses.append(float(loss))
         m1, v1 = opt.moments(model.fc1.weight)
@@ -271,7 +272,7 @@ def test_fp32_path_at_headline_size(device, monkeypatch, exact):
         if g is None:
             # fc1 only: HipAdam forms its gradient inside its own pass over p / m / v (pv_linear_wgrad_adam_f32); it is checked
             # below through the first moment, m1 = (1 - beta1) g
-            assert k == "fc1.weight" and getattr(p, "_pv_pending_f32", None) is not None, f"{k}: no gradient"
+            assert k == "fc1.weight" and (large_of(p).parked or (None,))[0] == PAIR_F32, f"{k}: no gradient"
             fused.append((k, p, q))
             continue
         # norm-wise: a ReLU output within rounding of zero is live on one side only, which moves the 864 weight-gradient

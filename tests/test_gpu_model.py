@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from conftest import ref_order
+from predict_pv_yield_amd._large_param import GRAD_BF16, OPERANDS_BF16, large_of
 
 from oracle import conv3d_oracle as co
 
@@ -177,7 +178,7 @@ def test_fused_fc1_adam_path_in_the_model(device, monkeypatch):
     monkeypatch.setattr(HipAdam, "FUSE_MIN_NUMEL", 1)
     _, model_b = _pair(SMALL, "bf16", device)
     opt = model_b.configure_optimizers()
-    assert getattr(model_b.fc1.weight, "_pv_grad_mode", "autograd") == "fused"
+    assert large_of(model_b.fc1.weight).mode == "fused"
     batch = {"satellite": {"data": sat.to(device)}, "pv": {"pv_yield": pv.to(device)}}
     losses_b = []
     for _ in range(3):
@@ -186,8 +187,8 @@ def test_fused_fc1_adam_path_in_the_model(device, monkeypatch):
         loss.backward()
         # the update was launched from inside backward on the optimiser's side stream (or left pending for step())
         # applied from inside backward by the single-pass kernel (or launched / left pending for step() by the older forms)
-        assert model_b.fc1.weight.grad is None and (model_b.fc1.weight._pv_applied or opt._inflight
-                                                    or model_b.fc1.weight._pv_pending is not None)
+        assert model_b.fc1.weight.grad is None and (large_of(model_b.fc1.weight).applied or opt._inflight
+                                                    or (large_of(model_b.fc1.weight).parked or (None,))[0] == OPERANDS_BF16)
         opt.step()
         losses_b.append(float(loss))
     # fc1's dx comes from a different kernel in the single-pass form (same operands, another summation order): isolated
@@ -244,7 +245,8 @@ def test_bf16_gradient_side_channel_in_the_model(device, monkeypatch):
         opt.zero_grad()
         loss = model_b.training_step(batch, 0)
         loss.backward()
-        assert model_b.fc1.weight.grad is None and model_b.fc1.weight._pv_grad_bf16.dtype == torch.bfloat16
+        kind, gb = large_of(model_b.fc1.weight).parked
+        assert model_b.fc1.weight.grad is None and kind == GRAD_BF16 and gb.dtype == torch.bfloat16
         opt.step()
         losses_b.append(float(loss))
     assert seen == [torch.bfloat16] * 3
