@@ -455,6 +455,57 @@ int pv_convt2d_s2_bwd_weight_f32(const float* x, const float* dy, const float* d
                                  int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
                                  void* stream);
 
+/* ---- notebooks/10_just_conv.ipynb: padded Conv2d 3x3 on 64 / 128 channels, stripe input, stride-2 head ---- */
+/* (line numbers: the raw 10_just_conv.ipynb file; the LitAutoEncoder cell starts at 1374, its nn.Sequential is at 1386-1392,
+ * forward at 1395-1410.)  NCHW f32, exact f32; gates (NULL = none) and weight-gradient slabs follow the conventions of the
+ * pv_conv2d_ae_* entry points above.  (h_in, w_in) is always the extent of the layer's input x.  pv_conv2d_wide_*: stride 1,
+ * pad = 0 or 2 (zeros), h -> h + 2 pad - 2; (c_in, c_out) = (64, 128) or (128, 128); w_in <= 128; every tensor below 2^31
+ * elements.  Unsupported shapes return PV_ESIZE, null pointers PV_EINVAL, before any launch. */
+/* replaces: nn.Conv2d(64, 128, 3) / nn.Conv2d(128, 128, 3, padding=2) (+ nn.ReLU() if relu), conv.2 / conv.4 of
+ * 10_just_conv.ipynb:1388-1391.  bias may be NULL. */
+int pv_conv2d_wide_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                           int32_t c_out, int32_t h_in, int32_t w_in, int32_t pad, int32_t relu, void* stream);
+/* replaces: the input gradient of conv.2 / conv.4 (autograd of 10_just_conv.ipynb:1388-1391): the same kernel on dy padded
+ * by 2 - pad with mirrored, channel-swapped weights.  dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0. */
+int pv_conv2d_wide_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                                int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, int32_t pad,
+                                void* stream);
+/* bytes of the weight-gradient workspace; also serves the stripe layer: c_in = n_hist + 1, c_out = 64, pad = 0 */
+int pv_conv2d_wide_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                              int32_t pad, size_t* bytes);
+/* replaces: the weight and bias gradients of conv.2 / conv.4.  dw [c_out][c_in][3][3] and dbias [c_out] are overwritten;
+ * slab partials summed in slab order (no atomics, identical bits run to run). */
+int pv_conv2d_wide_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias,
+                                  int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, int32_t pad,
+                                  void* ws, size_t ws_bytes, void* stream);
+/* replaces: forecast_horizon_img[example_i, 0, :, stripe_col_start:stripe_col_end] = 1; torch.cat((hist_images,
+ * forecast_horizon_img), dim=1); nn.Conv2d(5, 64, 3); nn.ReLU(), 10_just_conv.ipynb:1386-1387, 1398-1409.  history
+ * [n][n_hist][h][w], n_hist = 1..7; the last input channel is 1 on columns stripe_start[i] <= c < stripe_start[i] +
+ * stripe_width (0 <= c < w), else 0, synthesised in the kernel; c_out = 64; 3 <= h, w and w <= 128. */
+int pv_conv2d_wide_stripe_fwd_f32(const float* history, const int32_t* stripe_start, const float* w, const float* bias,
+                                  float* y, int32_t n, int32_t n_hist, int32_t h, int32_t w_img, int32_t c_out,
+                                  int32_t stripe_width, void* stream);
+/* replaces: the weight and bias gradients of conv.0 (autograd of 10_just_conv.ipynb:1386), re-synthesising the stripe
+ * channel as the forward does; dy is the pre-activation gradient.  dw [64][n_hist + 1][3][3]. */
+int pv_conv2d_wide_stripe_bwd_weight_f32(const float* history, const int32_t* stripe_start, const float* dy, float* dw,
+                                         float* dbias, int32_t n, int32_t n_hist, int32_t h, int32_t w_img, int32_t c_out,
+                                         int32_t stripe_width, void* ws, size_t ws_bytes, void* stream);
+/* replaces: nn.Conv2d(128, 1, 3, stride=2, padding=2), conv.6 of 10_just_conv.ipynb:1392 (+ ReLU if relu).  c_out = 1, any
+ * c_in >= 1, h -> (h + 1) / 2 + 1; vector code, sums in a fixed order; bias may be NULL. */
+int pv_conv2d_head_s2_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                              int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of conv.6: every dx element written once from the at most four taps of its parity class,
+ * zeroed where x_gate <= 0.  dy_gate must be NULL (no ReLU follows the head). */
+int pv_conv2d_head_s2_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                                   int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+int pv_conv2d_head_s2_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                                 size_t* bytes);
+/* replaces: the weight and bias gradients of conv.6.  dw [1][c_in][3][3] and dbias [1] are overwritten; slab partials summed
+ * in slab order (deterministic).  dy_gate must be NULL. */
+int pv_conv2d_head_s2_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias,
+                                     int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
+                                     size_t ws_bytes, void* stream);
+
 /* MaxPool3d over x[B*C planes][Ti,Hi,Wi]; argmax (may be NULL) = flat winner offset inside the plane stack, first
  * maximum wins, NaN propagates (torch CPU semantics).  bwd overwrites dx by gathering dy through argmax. */
 int pv_maxpool3d_fwd_f32(const float* x, float* y, int32_t* argmax, const pv_conv3d_geom* d, void* stream);

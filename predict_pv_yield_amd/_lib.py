@@ -97,6 +97,13 @@ _WS_QUERY6 = _DIMS5 + [c_i32, ctypes.POINTER(c_sz)]                  # ... + poo
 _COUNTS = [c_vp, c_i32, c_vp, c_i32, c_vp]                           # history, is_i16, flow prediction, is_i16, horizon
 _COUNTS_FWD = _COUNTS + [c_vp] * 3 + [c_i32] * 4 + [c_vp]            # weight, bias, y, (n, h, w, c_out)
 _COUNTS_BWD_WEIGHT = _COUNTS + [c_vp] * 3 + [c_i32] * 4 + _WORKSPACE + [c_vp]      # dy, dw, dbias, (n, h, w, c_out)
+# ... the padded wide family (notebook 10) takes pad after the dims; its stripe first layer takes (n, n_hist, h, w, c_out,
+# stripe_width) after its pointers
+_PAD_FWD = [c_vp] * 4 + _DIMS5 + [c_i32, c_i32, c_vp]                # x, weight, bias, y, dims, pad, relu
+_PAD_BWD_DATA = [c_vp] * 5 + _DIMS5 + [c_i32, c_vp]                  # dy, dy_gate, weight, dx, x_gate, dims, pad
+_PAD_BWD_WEIGHT = [c_vp] * 5 + _DIMS5 + [c_i32] + _WORKSPACE + [c_vp]      # x, dy, dy_gate, dw, dbias, dims, pad
+_STRIPE_FWD = [c_vp] * 5 + [c_i32] * 6 + [c_vp]                      # history, stripe_start, weight, bias, y
+_STRIPE_BWD_WEIGHT = [c_vp] * 5 + [c_i32] * 6 + _WORKSPACE + [c_vp]  # history, stripe_start, dy, dw, dbias
 _MSE_NORM_TAIL = [c_vp, c_vp] + _WORKSPACE + [c_vp]                  # loss, grad, workspace, stream
 
 
@@ -202,6 +209,13 @@ SIGNATURES = {
     **_conv2d_family("conv2d_s2", _WS_QUERY5),
     **_conv2d_counts_family("conv2d_s2"),
     **_conv2d_family("convt2d_s2", _WS_QUERY5),
+    "pv_conv2d_wide_fwd_f32": _PAD_FWD,
+    "pv_conv2d_wide_bwd_data_f32": _PAD_BWD_DATA,
+    "pv_conv2d_wide_bwd_weight_workspace_bytes": _WS_QUERY6,           # ... + pad
+    "pv_conv2d_wide_bwd_weight_f32": _PAD_BWD_WEIGHT,
+    "pv_conv2d_wide_stripe_fwd_f32": _STRIPE_FWD,
+    "pv_conv2d_wide_stripe_bwd_weight_f32": _STRIPE_BWD_WEIGHT,
+    **_conv2d_family("conv2d_head_s2", _WS_QUERY5),
     "pv_maxpool3d_fwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_maxpool3d_bwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_mse_loss_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp],

@@ -1,7 +1,8 @@
 """torch.autograd.Function wrappers over the exact-f32 Conv2d 3x3 "valid" kernels: csrc/conv2d_f32.hip (experiments/002) and
 the 144-channel kernels with fused MaxPool2d(3) of csrc/conv2d_pool_f32.hip (experiments/001) and the encoder / decoder
 kernels of csrc/conv2d_ae_f32.hip (notebooks/16_maxpool.ipynb: Conv2d up to 128 wide, ConvTranspose2d, cropped MSE) and the
-stride-2 Conv2d / ConvTranspose2d kernels of csrc/conv2d_s2_f32.hip (notebooks/14_back_to_2d_conv_AE.ipynb, 15_int16.ipynb).
+stride-2 Conv2d / ConvTranspose2d kernels of csrc/conv2d_s2_f32.hip (notebooks/14_back_to_2d_conv_AE.ipynb, 15_int16.ipynb) and
+the padded 64 / 128-channel kernels, stripe first layer and stride-2 head of csrc/conv2d_wide_f32.hip (notebooks/10_just_conv.ipynb).
 
 Reference operators replaced:
   experiments/002_cnn_processes_single_sat_image_then_rnn.py
@@ -21,6 +22,9 @@ Reference operators replaced:
     self.conv(cat(normalise_images_in_model(cat(history, flow)), horizon plane)): nn.Sequential of Conv2d 6 -> 16 -> 32 -> 32
     -> 32 and ConvTranspose2d 32 -> 32 -> 16 -> 1, all 3x3 stride 2, ReLU between                              :13746-13780
     F.mse_loss(y_hat.squeeze(), normalise_images_in_model(y)[..., :-1, :-1])                                  :13783-13788
+  notebooks/10_just_conv.ipynb (raw lines of the .ipynb file)
+    self.conv(cat(hist_images, forecast-horizon stripe plane)): nn.Sequential of Conv2d 5 -> 64 -> 128 -> 128 (padding 2) and
+    Conv2d 128 -> 1 (stride 2, padding 2), ReLU between                                                        :1386-1410
 
 Gating.  As in functional.Conv3dGeneralF32, the ReLU gating of an activation gradient is moved into the kernel that
 produces it.  x_is_relu_output -> this layer's dx leaves already zeroed where x <= 0 (the lower layer's pre-activation
@@ -45,6 +49,10 @@ CONV2D_AE_OPS = (K.conv2d_ae_fwd_f32, K.conv2d_ae_bwd_data_f32, K.conv2d_ae_bwd_
 CONVT2D_AE_OPS = (K.convt2d_ae_fwd_f32, K.convt2d_ae_bwd_data_f32, K.convt2d_ae_bwd_weight_f32)
 CONV2D_S2_OPS = (K.conv2d_s2_fwd_f32, K.conv2d_s2_bwd_data_f32, K.conv2d_s2_bwd_weight_f32)
 CONVT2D_S2_OPS = (K.convt2d_s2_fwd_f32, K.convt2d_s2_bwd_data_f32, K.convt2d_s2_bwd_weight_f32)
+# notebook 10: the padded wide family (one tuple per padding) and the stride-2 one-channel head
+CONV2D_WIDE_OPS = (K.conv2d_wide_fwd_f32, K.conv2d_wide_bwd_data_f32, K.conv2d_wide_bwd_weight_f32)
+CONV2D_WIDE_P2_OPS = (K.conv2d_wide_p2_fwd_f32, K.conv2d_wide_p2_bwd_data_f32, K.conv2d_wide_p2_bwd_weight_f32)
+CONV2D_HEAD_S2_OPS = (K.conv2d_head_s2_fwd_f32, K.conv2d_head_s2_bwd_data_f32, K.conv2d_head_s2_bwd_weight_f32)
 # ... of the raw-counts first layer: (forward, weight gradient)
 COUNTS_AE_OPS = (K.conv2d_ae_counts_fwd_f32, K.conv2d_ae_counts_bwd_weight_f32)
 COUNTS_S2_OPS = (K.conv2d_s2_counts_fwd_f32, K.conv2d_s2_counts_bwd_weight_f32)
@@ -312,3 +320,65 @@ def nb15_autoencoder_f32(history, flow_pred, horizon, conv):
     for i in (8, 10):
         y = ConvReLU.apply(CONVT2D_S2_OPS, y, conv[i].weight, conv[i].bias, True, True, True)
     return ConvReLU.apply(CONVT2D_S2_OPS, y, conv[12].weight, conv[12].bias, False, True, False)
+
+
+# ---- notebooks/10_just_conv.ipynb ---------------------------------------------------------------------------------------
+STRIPE_WIDTH = 128 // 24          # 10_just_conv.ipynb:1379: a constant, not derived from the image width
+
+
+class StripeConvReLU(torch.autograd.Function):
+    """First layer of notebook 10: history [N, n_hist, H, W] f32 plus the forecast-horizon stripe plane (1 on columns
+    stripe_start[i] <= c < stripe_start[i] + stripe_width), built inside the kernels (forward and weight gradient), never
+    stored.  No gradient flows to the inputs."""
+
+    @staticmethod
+    def forward(ctx, history, stripe_start, weight, bias, stripe_width, dy_pregated):
+        history, stripe_start = history.contiguous(), stripe_start.contiguous()
+        y = K.conv2d_wide_stripe_fwd_f32(history, stripe_start, weight.contiguous(), bias.contiguous(), stripe_width)
+        ctx.save_for_backward(history, stripe_start, None if dy_pregated else y)
+        ctx.stripe_width, ctx.weight_shape = stripe_width, tuple(weight.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        history, stripe_start, y = ctx.saved_tensors
+        dy = dy.contiguous()
+        if y is not None:
+            dy = K.relu_gate_f32(dy, y)
+        dw, db = K.conv2d_wide_stripe_bwd_weight_f32(history, stripe_start, dy, ctx.weight_shape, ctx.stripe_width)
+        return None, None, dw, db, None, None
+
+
+def stripe_start_from_horizon(horizon, stripe_width=STRIPE_WIDTH):
+    """int(horizon[i] * stripe_width) of 10_just_conv.ipynb:1404 for every example at once, on the device (truncation toward
+    zero, no host synchronisation, so a step can be captured as a graph).  Any integer or float dtype."""
+    scaled = horizon * stripe_width
+    return (scaled.trunc() if scaled.is_floating_point() else scaled).to(torch.int32)
+
+
+def stripe_conv_relu(history, stripe_start, weight, bias, stripe_width=STRIPE_WIDTH):
+    """relu(conv.0(cat(history, stripe plane))) of 10_just_conv.ipynb:1386-1387, 1398-1409; gradients to weight and bias only."""
+    return StripeConvReLU.apply(history, stripe_start, weight, bias, int(stripe_width), False)
+
+
+def conv2d_wide_relu(x, weight, bias, relu=True, x_is_relu_output=False, padding=0):
+    """nn.Conv2d(64 or 128, 128, 3, padding=0 or 2)(x) (+ ReLU), planes up to 128 wide.  x_is_relu_output: dx leaves gated by
+    x > 0."""
+    ops = {0: CONV2D_WIDE_OPS, 2: CONV2D_WIDE_P2_OPS}[int(padding)]
+    return ConvReLU.apply(ops, x, weight, bias, bool(relu), bool(x_is_relu_output), False)
+
+
+def conv2d_head_s2(x, weight, bias, x_is_relu_output=False):
+    """nn.Conv2d(C_in, 1, 3, stride=2, padding=2)(x), no ReLU.  x_is_relu_output: dx leaves gated by x > 0."""
+    return ConvReLU.apply(CONV2D_HEAD_S2_OPS, x, weight, bias, False, bool(x_is_relu_output), False)
+
+
+def nb10_just_conv_f32(history, stripe_start, conv):
+    """self.conv(cat(hist_images, stripe plane)) of 10_just_conv.ipynb:1386-1410; conv = the notebook's nn.Sequential (modules 0,
+    2, 4, 6 nn.Conv2d; the nn.ReLU modules between them are fused into the layers' kernels).  Every inner ReLU output has one
+    consumer, the next layer, whose data gradient leaves gated by it (x_is_relu_output), so its producer skips gating the
+    arriving gradient (dy_pregated): no ReLU or mask kernel runs on its own.  The pairing only holds inside this chain."""
+    y = StripeConvReLU.apply(history, stripe_start, conv[0].weight, conv[0].bias, STRIPE_WIDTH, True)
+    y = ConvReLU.apply(CONV2D_WIDE_OPS, y, conv[2].weight, conv[2].bias, True, True, True)
+    y = ConvReLU.apply(CONV2D_WIDE_P2_OPS, y, conv[4].weight, conv[4].bias, True, True, True)
+    return ConvReLU.apply(CONV2D_HEAD_S2_OPS, y, conv[6].weight, conv[6].bias, False, True, False)

@@ -1186,6 +1186,34 @@ def _pooled_shape_c(n, c, h, w):
     return _pooled_shape(n, c, h, w)
 
 
+WIDE_PAIRS = ((64, 128), (128, 128))      # (c_in, c_out) of pv_conv2d_wide_*
+WIDE_MAX_W = 128
+STRIPE_C_OUT = 64
+STRIPE_MAX_HIST = 7
+
+
+def _check_wide(who, x_shape, weight_shape, pad):
+    _check_ae(who, x_shape, weight_shape)
+    n, ci, h, w = x_shape
+    if (ci, weight_shape[0]) not in WIDE_PAIRS:
+        raise ValueError(f"{who}: (C_in, C_out) = (64, 128) or (128, 128) expected, got ({ci}, {weight_shape[0]})")
+    if min(h, w) + 2 * pad < 3 or w > WIDE_MAX_W:
+        raise ValueError(f"{who}: planes of at least {max(3 - 2 * pad, 1)} rows / columns and at most {WIDE_MAX_W} columns "
+                         f"expected, got {h} x {w}")
+
+
+def _check_head(who, x_shape, weight_shape):
+    _check_ae(who, x_shape, weight_shape)
+    if weight_shape[0] != 1 or x_shape[2] < 1 or x_shape[3] < 1:
+        raise ValueError(f"{who}: weight [1, C_in, 3, 3] and a non-empty plane expected, got {tuple(weight_shape)} / "
+                         f"{tuple(x_shape)}")
+
+
+def head_s2_out(side):
+    """Side of a 3x3 stride-2 padding-2 Conv2d's output."""
+    return (side + 1) // 2 + 1
+
+
 def s2_out(side):
     """Side of a 3x3 stride-2 Conv2d's output."""
     return (side - 3) // 2 + 1
@@ -1198,6 +1226,7 @@ class _ConvFamily(NamedTuple):
     out_hw: Callable                # (h, w) of the input -> (h, w) of the output
     c_out_axis: int = 0             # of the weight: 0 in Conv2d's [C_out, C_in, 3, 3], 1 in ConvTranspose2d's [C_in, C_out, ..]
     ws_args: tuple = ()             # the workspace query's arguments after (n, c_in, c_out, h, w): the "pooled" flag, 0 here
+    pad_args: tuple = ()            # every pass's arguments after (n, c_in, c_out, h, w): the padding of a padded family
 
 
 class _PoolFamily(NamedTuple):
@@ -1223,6 +1252,12 @@ _CONV2D_AE = _ConvFamily("conv2d_ae", _check_ae, _valid_hw, ws_args=(0,))
 _CONVT2D_AE = _ConvFamily("convt2d_ae", _check_aet, lambda h, w: (h + 2, w + 2), c_out_axis=1)
 _CONV2D_S2 = _ConvFamily("conv2d_s2", _check_ae, _s2_hw)
 _CONVT2D_S2 = _ConvFamily("convt2d_s2", _check_aet, lambda h, w: (2 * h + 1, 2 * w + 1), c_out_axis=1)
+# notebook 10: the padded wide family is one stem with a record per padding (the padding goes to every pass and to the
+# workspace query); the stride-2 head maps a side s to (s + 1) // 2 + 1
+_CONV2D_WIDE_P0 = _ConvFamily("conv2d_wide", lambda *a: _check_wide(*a, pad=0), _valid_hw, ws_args=(0,), pad_args=(0,))
+_CONV2D_WIDE_P2 = _ConvFamily("conv2d_wide", lambda *a: _check_wide(*a, pad=2), lambda h, w: (h + 2, w + 2), ws_args=(2,),
+                              pad_args=(2,))
+_CONV2D_HEAD_S2 = _ConvFamily("conv2d_head_s2", lambda *a: _check_head(*a), lambda h, w: (head_s2_out(h), head_s2_out(w)))
 _CONV2D144_POOL = _PoolFamily("conv2d144", _check_c144_pooled, _pooled_shape, False)
 _CONV2D_AE_POOL = _PoolFamily("conv2d_ae", _check_ae, _pooled_shape_c, True)
 
@@ -1257,8 +1292,8 @@ def _conv_fwd(fam, x, weight, bias, relu):
     require_cuda(x, weight, bias)
     _f32_contig(x, weight, bias)
     y = torch.empty((n, co, *fam.out_hw(h, w)), dtype=torch.float32, device=x.device)
-    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, int(relu),
-                                          current_stream_ptr()), "pv_" + who)
+    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, *fam.pad_args,
+                                          int(relu), current_stream_ptr()), "pv_" + who)
     return y
 
 
@@ -1274,7 +1309,7 @@ def _conv_bwd_data(fam, dy, dy_gate, weight, x_gate, x_shape):
     _f32_contig(dy, dy_gate, weight, x_gate)
     dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
     check(getattr(get_lib(), "pv_" + who)(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci, co, h, w,
-                                          current_stream_ptr()), "pv_" + who)
+                                          *fam.pad_args, current_stream_ptr()), "pv_" + who)
     return dx
 
 
@@ -1288,8 +1323,8 @@ def _conv_bwd_weight(fam, x, dy, dy_gate, weight_shape):
     _f32_contig(x, dy, dy_gate)
     ws, nbytes = _wgrad_ws(fam.stem, x.device, n, ci, co, h, w, *fam.ws_args)
     dw, db = _grads_out(weight_shape, co, x.device)
-    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, ptr(ws), nbytes,
-                                          current_stream_ptr()), "pv_" + who)
+    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, *fam.pad_args,
+                                          ptr(ws), nbytes, current_stream_ptr()), "pv_" + who)
     return dw, db
 
 
@@ -1640,6 +1675,107 @@ def convt2d_s2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
 def convt2d_s2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
     """(dw [C_in, C_out, 3, 3], dbias [C_out]) of convt2d_s2_fwd_f32; deterministic (fixed slabs summed in order)."""
     return _conv_bwd_weight(_CONVT2D_S2, x, dy, dy_gate, weight_shape)
+
+
+# ---- notebooks/10_just_conv.ipynb: Conv2d 5 -> 64 -> 128 -> 128 (padding 2) -> 1 (stride 2, padding 2), the fifth input
+# channel a forecast-horizon stripe (csrc/conv2d_wide_f32.hip); planes up to 128 wide ----
+def _check_stripe(who, history, stripe_start, stripe_width):
+    if history.dim() != 4 or not 1 <= history.shape[1] <= STRIPE_MAX_HIST:
+        raise ValueError(f"{who}: history [N, 1..{STRIPE_MAX_HIST}, H, W] expected, got {tuple(history.shape)}")
+    n, n_hist, h, w = history.shape
+    if tuple(stripe_start.shape) != (n,) or stripe_start.dtype != torch.int32 or not stripe_start.is_contiguous():
+        raise ValueError(f"{who}: stripe_start int32 [{n}] expected, got {stripe_start.dtype} {tuple(stripe_start.shape)}")
+    if h < 3 or w < 3 or w > WIDE_MAX_W or stripe_width < 0:
+        raise ValueError(f"{who}: planes of 3 x 3 up to {WIDE_MAX_W} columns and a stripe width >= 0 expected, got {h} x {w}, "
+                         f"width {stripe_width}")
+    require_cuda(history, stripe_start)
+    _f32_contig(history)
+    return n, n_hist, h, w
+
+
+def conv2d_wide_stripe_fwd_f32(history, stripe_start, weight, bias, stripe_width):
+    """relu(conv2d(cat(history, stripe plane), weight) + bias): history [N, n_hist, H, W] f32, the stripe plane of example i is 1
+    on columns stripe_start[i] <= c < stripe_start[i] + stripe_width (inside the image) -> [N, 64, H - 2, W - 2]."""
+    who = "conv2d_wide_stripe_fwd_f32"
+    n, n_hist, h, w = _check_stripe(who, history, stripe_start, stripe_width)
+    if tuple(weight.shape) != (STRIPE_C_OUT, n_hist + 1, 3, 3):
+        raise ValueError(f"{who}: weight [{STRIPE_C_OUT}, {n_hist + 1}, 3, 3] expected, got {tuple(weight.shape)}")
+    if bias is None or tuple(bias.shape) != (STRIPE_C_OUT,):
+        raise ValueError(f"{who}: bias [{STRIPE_C_OUT}] expected")
+    require_cuda(weight, bias)
+    _f32_contig(weight, bias)
+    y = torch.empty((n, STRIPE_C_OUT, h - 2, w - 2), dtype=torch.float32, device=history.device)
+    check(get_lib().pv_conv2d_wide_stripe_fwd_f32(ptr(history), ptr(stripe_start), ptr(weight), ptr(bias), ptr(y), n, n_hist,
+                                                  h, w, STRIPE_C_OUT, int(stripe_width), current_stream_ptr()),
+          "pv_" + who)
+    return y
+
+
+def conv2d_wide_stripe_bwd_weight_f32(history, stripe_start, dy, weight_shape, stripe_width):
+    """(dw [64, n_hist + 1, 3, 3], dbias) of conv2d_wide_stripe_fwd_f32's conv from its pre-activation gradient dy."""
+    who = "conv2d_wide_stripe_bwd_weight_f32"
+    n, n_hist, h, w = _check_stripe(who, history, stripe_start, stripe_width)
+    y_shape = (n, STRIPE_C_OUT, h - 2, w - 2)
+    if tuple(weight_shape) != (STRIPE_C_OUT, n_hist + 1, 3, 3) or tuple(dy.shape) != y_shape:
+        raise ValueError(f"{who}: weight {(STRIPE_C_OUT, n_hist + 1, 3, 3)} and dy {y_shape} expected, got "
+                         f"{tuple(weight_shape)} / {tuple(dy.shape)}")
+    require_cuda(dy)
+    _f32_contig(dy)
+    ws, nbytes = _wgrad_ws("conv2d_wide", history.device, n, n_hist + 1, STRIPE_C_OUT, h, w, 0)
+    dw, db = _grads_out(weight_shape, STRIPE_C_OUT, history.device)
+    check(get_lib().pv_conv2d_wide_stripe_bwd_weight_f32(ptr(history), ptr(stripe_start), ptr(dy), ptr(dw), ptr(db), n, n_hist,
+                                                         h, w, STRIPE_C_OUT, int(stripe_width), ptr(ws), nbytes,
+                                                         current_stream_ptr()), "pv_" + who)
+    return dw, db
+
+
+def _wide_family(padding):
+    if padding not in (0, 2):
+        raise ValueError(f"conv2d_wide: padding 0 or 2 expected, got {padding}")
+    return _CONV2D_WIDE_P2 if padding else _CONV2D_WIDE_P0
+
+
+def conv2d_wide_fwd_f32(x, weight, bias, relu=True, padding=0):
+    """conv2d(x, weight, padding=padding) + bias (+ ReLU) for (C_in, C_out) = (64, 128) or (128, 128), padding 0 or 2, W <= 128."""
+    return _conv_fwd(_wide_family(padding), x, weight, bias, relu)
+
+
+def conv2d_wide_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape, padding=0):
+    """dx of conv2d_wide_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
+    return _conv_bwd_data(_wide_family(padding), dy, dy_gate, weight, x_gate, x_shape)
+
+
+def conv2d_wide_bwd_weight_f32(x, dy, dy_gate, weight_shape, padding=0):
+    """(dw, dbias) of conv2d_wide_fwd_f32; deterministic (fixed slabs summed in order)."""
+    return _conv_bwd_weight(_wide_family(padding), x, dy, dy_gate, weight_shape)
+
+
+# the padding-2 passes under the (forward, data gradient, weight gradient) signatures conv2d_functional.ConvReLU calls
+def conv2d_wide_p2_fwd_f32(x, weight, bias, relu=True):
+    return conv2d_wide_fwd_f32(x, weight, bias, relu, 2)
+
+
+def conv2d_wide_p2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    return conv2d_wide_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape, 2)
+
+
+def conv2d_wide_p2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    return conv2d_wide_bwd_weight_f32(x, dy, dy_gate, weight_shape, 2)
+
+
+def conv2d_head_s2_fwd_f32(x, weight, bias, relu=False):
+    """conv2d(x, weight [1, C_in, 3, 3], stride=2, padding=2) + bias (+ ReLU): [N, C_in, H, W] -> [N, 1, (H+1)//2+1, (W+1)//2+1]."""
+    return _conv_fwd(_CONV2D_HEAD_S2, x, weight, bias, relu)
+
+
+def conv2d_head_s2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of conv2d_head_s2_fwd_f32, zeroed where x_gate <= 0 (may be None); dy_gate must be None (no ReLU follows the head)."""
+    return _conv_bwd_data(_CONV2D_HEAD_S2, dy, dy_gate, weight, x_gate, x_shape)
+
+
+def conv2d_head_s2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw [1, C_in, 3, 3], dbias [1]) of conv2d_head_s2_fwd_f32; deterministic; dy_gate must be None."""
+    return _conv_bwd_weight(_CONV2D_HEAD_S2, x, dy, dy_gate, weight_shape)
 
 
 def mse_window_norm_f32(y_hat, target, row0=0, col0=0, need_grad=True):
