@@ -506,6 +506,86 @@ int pv_conv2d_head_s2_bwd_weight_f32(const float* x, const float* dy, const floa
                                      int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
                                      size_t ws_bytes, void* stream);
 
+/* ---- notebooks/09_horizon_represented_as_a_stripe.ipynb: Conv2d / ConvTranspose2d 3x3, stride 2, 64 / 128 channels ---- */
+/* (line numbers: the raw 09_horizon_represented_as_a_stripe.ipynb file; the LitAutoEncoder cell is 1356-1416, encoder_conv at
+ * 1366-1370, decoder_conv at 1375-1379, the stripe plane at 1382-1395, the loss at 1402-1403.)  NCHW f32, exact f32 on the
+ * matrix cores; gates (NULL = none) and weight-gradient slabs follow the conventions of the pv_conv2d_ae_* entry points
+ * above.  A Conv2d maps h -> (h - 3) / 2 + 1, a ConvTranspose2d h -> 2 h + 1; planes are at most 128 wide on the wide side
+ * (Conv2d input, ConvTranspose2d output).  (h_in, w_in) is always the extent of the layer's input x.  Unsupported shapes
+ * return PV_ESIZE, null pointers PV_EINVAL, before any launch. */
+/* replaces: forecast_horizon_img[example_i, 0, :, stripe_col_start:stripe_col_end] = 1; torch.cat((hist_images,
+ * forecast_horizon_img), dim=1); nn.Conv2d(5, 64, 3, stride=2); nn.ReLU(), 09_…ipynb:1366-1367, 1382-1395.  history
+ * [n][n_hist][h][w], n_hist = 1..7; the last input channel is 1 on columns stripe_start[i] <= c < stripe_start[i] +
+ * stripe_width (0 <= c < w), else 0, synthesised in the kernel; c_out = 64; 3 <= h, w and w <= 128. */
+int pv_conv2d_wide_s2_stripe_fwd_f32(const float* history, const int32_t* stripe_start, const float* w, const float* bias,
+                                     float* y, int32_t n, int32_t n_hist, int32_t h, int32_t w_img, int32_t c_out,
+                                     int32_t stripe_width, void* stream);
+/* replaces: the weight and bias gradients of encoder_conv.0 (autograd of 09_…ipynb:1366), re-synthesising the stripe channel
+ * as the forward does; dy is the pre-activation gradient.  dw [64][n_hist + 1][3][3]. */
+int pv_conv2d_wide_s2_stripe_bwd_weight_f32(const float* history, const int32_t* stripe_start, const float* dy, float* dw,
+                                            float* dbias, int32_t n, int32_t n_hist, int32_t h, int32_t w_img,
+                                            int32_t c_out, int32_t stripe_width, void* ws, size_t ws_bytes, void* stream);
+/* replaces: nn.Conv2d(c_in, c_out, 3, stride=2) (+ nn.ReLU() if relu), encoder_conv.2 / encoder_conv.4 of
+ * 09_…ipynb:1368-1370.  (c_in, c_out) = (64, 128) or (128, 128); 3 <= h_in, w_in and w_in <= 128; bias may be NULL. */
+int pv_conv2d_wide_s2_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                              int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of encoder_conv.2 / encoder_conv.4.  dy zeroed where dy_gate <= 0, dx [n][c_in][h_in][w_in]
+ * zeroed where x_gate <= 0.  Every element of dx is written; the last row / column of an even h_in / w_in, which the
+ * forward never reads, is exactly 0. */
+int pv_conv2d_wide_s2_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                                   int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+/* bytes of the weight-gradient workspace; also serves the stripe layer: c_in = n_hist + 1, c_out = 64 */
+int pv_conv2d_wide_s2_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                                 size_t* bytes);
+/* replaces: the weight and bias gradients of encoder_conv.2 / encoder_conv.4.  dw [c_out][c_in][3][3] and dbias [c_out] are
+ * overwritten; slab partials summed in slab order (no atomics, identical bits run to run). */
+int pv_conv2d_wide_s2_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias,
+                                     int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
+                                     size_t ws_bytes, void* stream);
+/* replaces: nn.ConvTranspose2d(128, 128, 3, stride=2) (+ nn.ReLU() if relu), decoder_conv.0 / decoder_conv.2 of
+ * 09_…ipynb:1375-1378.  x [n][128][h][w] -> y [n][128][2 h + 1][2 w + 1]; w [c_in][c_out][3][3]; 2 w + 1 <= 128; bias may be
+ * NULL. */
+int pv_convt2d_wide_s2_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                               int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of decoder_conv.0 / decoder_conv.2: a stride-2 valid correlation of dy [n][c_out][2 h + 1][2 w
+ * + 1] (zeroed where dy_gate <= 0) with the unmirrored weights; dx [n][c_in][h][w] zeroed where x_gate <= 0. */
+int pv_convt2d_wide_s2_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                                    int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+/* bytes of the workspace of pv_convt2d_wide_s2_bwd_weight_f32: one partial [c_in][c_out * 9 + 1] per slab of tiles, then one
+ * partial [c_out] per slab of images for the bias gradient */
+int pv_convt2d_wide_s2_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                                  size_t* bytes);
+/* replaces: the weight and bias gradients of decoder_conv.0 / decoder_conv.2: dw[ci][co][tap] = sum x[ci][p] dy[co][2 p + tap]
+ * in the [c_in][c_out][3][3] layout, dbias[co] = sum of dy[co] over all of its positions (both with dy zeroed where dy_gate
+ * <= 0); deterministic. */
+int pv_convt2d_wide_s2_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias,
+                                      int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
+                                      size_t ws_bytes, void* stream);
+/* replaces: nn.ConvTranspose2d(128, 1, 3), decoder_conv.4 of 09_…ipynb:1379 (+ ReLU if relu).  c_out = 1, any c_in >= 1,
+ * x [n][c_in][h][w] -> y [n][1][h + 2][w + 2]; w [c_in][1][3][3]; w_in <= 128; vector code, sums in a fixed order; bias may
+ * be NULL. */
+int pv_convt2d_head_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                            int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of decoder_conv.4: dx[ci][i][j] = sum_tap w[ci][tap] dy[i + kh][j + kw], zeroed where x_gate
+ * <= 0.  dy_gate must be NULL (no ReLU follows the head). */
+int pv_convt2d_head_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                                 int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+int pv_convt2d_head_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                               size_t* bytes);
+/* replaces: the weight and bias gradients of decoder_conv.4.  dw [c_in][1][3][3] and dbias [1] (the sum of dy over all of
+ * its positions) are overwritten; slab partials summed in slab order (deterministic).  dy_gate must be NULL. */
+int pv_convt2d_head_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias,
+                                   int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
+                                   size_t ws_bytes, void* stream);
+/* replaces: F.mse_loss(y_hat[:, :, :-1, :-1], y.unsqueeze(1)), 09_…ipynb:1402-1403 (row0 = col0 = 0, target one smaller than
+ * the prediction).  y_hat [n][out_h][out_w], target [n][target_h][target_w] f32; the prediction's window starts at (row0,
+ * col0); a window that leaves y_hat returns PV_ESIZE.  loss: device f32[1]; dy_hat (may be NULL) is written everywhere:
+ * 2 (y_hat - y) / count inside the window, exactly 0 outside.  ws: n floats (one partial sum per example, added in index
+ * order). */
+int pv_mse_pred_window_f32(const float* y_hat, const float* target, int32_t n, int32_t out_h, int32_t out_w,
+                           int32_t target_h, int32_t target_w, int32_t row0, int32_t col0, float* loss, float* dy_hat,
+                           void* ws, size_t ws_bytes, void* stream);
+
 /* MaxPool3d over x[B*C planes][Ti,Hi,Wi]; argmax (may be NULL) = flat winner offset inside the plane stack, first
  * maximum wins, NaN propagates (torch CPU semantics).  bwd overwrites dx by gathering dy through argmax. */
 int pv_maxpool3d_fwd_f32(const float* x, float* y, int32_t* argmax, const pv_conv3d_geom* d, void* stream);

@@ -216,6 +216,12 @@ SIGNATURES = {
     "pv_conv2d_wide_stripe_fwd_f32": _STRIPE_FWD,
     "pv_conv2d_wide_stripe_bwd_weight_f32": _STRIPE_BWD_WEIGHT,
     **_conv2d_family("conv2d_head_s2", _WS_QUERY5),
+    "pv_conv2d_wide_s2_stripe_fwd_f32": _STRIPE_FWD,
+    "pv_conv2d_wide_s2_stripe_bwd_weight_f32": _STRIPE_BWD_WEIGHT,
+    **_conv2d_family("conv2d_wide_s2", _WS_QUERY5),
+    **_conv2d_family("convt2d_wide_s2", _WS_QUERY5),
+    **_conv2d_family("convt2d_head", _WS_QUERY5),
+    "pv_mse_pred_window_f32": [c_vp, c_vp] + [c_i32] * 7 + _MSE_NORM_TAIL,     # y_hat, target, (n, sides, row0, col0)
     "pv_maxpool3d_fwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_maxpool3d_bwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_mse_loss_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp],

@@ -2,7 +2,9 @@
 the 144-channel kernels with fused MaxPool2d(3) of csrc/conv2d_pool_f32.hip (experiments/001) and the encoder / decoder
 kernels of csrc/conv2d_ae_f32.hip (notebooks/16_maxpool.ipynb: Conv2d up to 128 wide, ConvTranspose2d, cropped MSE) and the
 stride-2 Conv2d / ConvTranspose2d kernels of csrc/conv2d_s2_f32.hip (notebooks/14_back_to_2d_conv_AE.ipynb, 15_int16.ipynb) and
-the padded 64 / 128-channel kernels, stripe first layer and stride-2 head of csrc/conv2d_wide_f32.hip (notebooks/10_just_conv.ipynb).
+the padded 64 / 128-channel kernels, stripe first layer and stride-2 head of csrc/conv2d_wide_f32.hip (notebooks/10_just_conv.ipynb)
+and the stride-2 64 / 128-channel Conv2d / ConvTranspose2d kernels, stride-2 stripe first layer, one-channel ConvTranspose2d
+head and prediction-window MSE of csrc/conv2d_wide_s2_f32.hip (notebooks/09_horizon_represented_as_a_stripe.ipynb).
 
 Reference operators replaced:
   experiments/002_cnn_processes_single_sat_image_then_rnn.py
@@ -25,6 +27,11 @@ Reference operators replaced:
   notebooks/10_just_conv.ipynb (raw lines of the .ipynb file)
     self.conv(cat(hist_images, forecast-horizon stripe plane)): nn.Sequential of Conv2d 5 -> 64 -> 128 -> 128 (padding 2) and
     Conv2d 128 -> 1 (stride 2, padding 2), ReLU between                                                        :1386-1410
+  notebooks/09_horizon_represented_as_a_stripe.ipynb (raw lines of the .ipynb file)
+    self.encoder_conv(cat(hist_images, forecast-horizon stripe plane)): Conv2d 5 -> 64 -> 128 -> 128, all stride 2, a
+    ReLU after each                                                                                            :1366-1370, 1382-1397
+    self.decoder_conv(out): ConvTranspose2d 128 -> 128 -> 128 stride 2 with ReLU, ConvTranspose2d 128 -> 1     :1375-1379
+    F.mse_loss(y_hat[:, :, :-1, :-1], y.unsqueeze(1))                                                          :1402-1403
 
 Gating.  As in functional.Conv3dGeneralF32, the ReLU gating of an activation gradient is moved into the kernel that
 produces it.  x_is_relu_output -> this layer's dx leaves already zeroed where x <= 0 (the lower layer's pre-activation
@@ -53,6 +60,13 @@ CONVT2D_S2_OPS = (K.convt2d_s2_fwd_f32, K.convt2d_s2_bwd_data_f32, K.convt2d_s2_
 CONV2D_WIDE_OPS = (K.conv2d_wide_fwd_f32, K.conv2d_wide_bwd_data_f32, K.conv2d_wide_bwd_weight_f32)
 CONV2D_WIDE_P2_OPS = (K.conv2d_wide_p2_fwd_f32, K.conv2d_wide_p2_bwd_data_f32, K.conv2d_wide_p2_bwd_weight_f32)
 CONV2D_HEAD_S2_OPS = (K.conv2d_head_s2_fwd_f32, K.conv2d_head_s2_bwd_data_f32, K.conv2d_head_s2_bwd_weight_f32)
+# notebook 09: the stride-2 wide layers and the one-output-channel ConvTranspose2d head
+CONV2D_WIDE_S2_OPS = (K.conv2d_wide_s2_fwd_f32, K.conv2d_wide_s2_bwd_data_f32, K.conv2d_wide_s2_bwd_weight_f32)
+CONVT2D_WIDE_S2_OPS = (K.convt2d_wide_s2_fwd_f32, K.convt2d_wide_s2_bwd_data_f32, K.convt2d_wide_s2_bwd_weight_f32)
+CONVT2D_HEAD_OPS = (K.convt2d_head_fwd_f32, K.convt2d_head_bwd_data_f32, K.convt2d_head_bwd_weight_f32)
+# ... of the stripe first layer: (forward, weight gradient), stride 1 (notebook 10) and stride 2 (notebook 09)
+STRIPE_WIDE_OPS = (K.conv2d_wide_stripe_fwd_f32, K.conv2d_wide_stripe_bwd_weight_f32)
+STRIPE_WIDE_S2_OPS = (K.conv2d_wide_s2_stripe_fwd_f32, K.conv2d_wide_s2_stripe_bwd_weight_f32)
 # ... of the raw-counts first layer: (forward, weight gradient)
 COUNTS_AE_OPS = (K.conv2d_ae_counts_fwd_f32, K.conv2d_ae_counts_bwd_weight_f32)
 COUNTS_S2_OPS = (K.conv2d_s2_counts_fwd_f32, K.conv2d_s2_counts_bwd_weight_f32)
@@ -327,16 +341,17 @@ STRIPE_WIDTH = 128 // 24          # 10_just_conv.ipynb:1379: a constant, not der
 
 
 class StripeConvReLU(torch.autograd.Function):
-    """First layer of notebook 10: history [N, n_hist, H, W] f32 plus the forecast-horizon stripe plane (1 on columns
+    """First layer of notebooks 09 and 10: history [N, n_hist, H, W] f32 plus the forecast-horizon stripe plane (1 on columns
     stripe_start[i] <= c < stripe_start[i] + stripe_width), built inside the kernels (forward and weight gradient), never
-    stored.  No gradient flows to the inputs."""
+    stored.  ops = STRIPE_WIDE_OPS (stride 1, notebook 10) or STRIPE_WIDE_S2_OPS (stride 2, notebook 09).  No gradient flows
+    to the inputs."""
 
     @staticmethod
-    def forward(ctx, history, stripe_start, weight, bias, stripe_width, dy_pregated):
+    def forward(ctx, ops, history, stripe_start, weight, bias, stripe_width, dy_pregated):
         history, stripe_start = history.contiguous(), stripe_start.contiguous()
-        y = K.conv2d_wide_stripe_fwd_f32(history, stripe_start, weight.contiguous(), bias.contiguous(), stripe_width)
+        y = ops[0](history, stripe_start, weight.contiguous(), bias.contiguous(), stripe_width)
         ctx.save_for_backward(history, stripe_start, None if dy_pregated else y)
-        ctx.stripe_width, ctx.weight_shape = stripe_width, tuple(weight.shape)
+        ctx.ops, ctx.stripe_width, ctx.weight_shape = ops, stripe_width, tuple(weight.shape)
         return y
 
     @staticmethod
@@ -345,8 +360,8 @@ class StripeConvReLU(torch.autograd.Function):
         dy = dy.contiguous()
         if y is not None:
             dy = K.relu_gate_f32(dy, y)
-        dw, db = K.conv2d_wide_stripe_bwd_weight_f32(history, stripe_start, dy, ctx.weight_shape, ctx.stripe_width)
-        return None, None, dw, db, None, None
+        dw, db = ctx.ops[1](history, stripe_start, dy, ctx.weight_shape, ctx.stripe_width)
+        return None, None, None, dw, db, None, None
 
 
 def stripe_start_from_horizon(horizon, stripe_width=STRIPE_WIDTH):
@@ -358,7 +373,7 @@ def stripe_start_from_horizon(horizon, stripe_width=STRIPE_WIDTH):
 
 def stripe_conv_relu(history, stripe_start, weight, bias, stripe_width=STRIPE_WIDTH):
     """relu(conv.0(cat(history, stripe plane))) of 10_just_conv.ipynb:1386-1387, 1398-1409; gradients to weight and bias only."""
-    return StripeConvReLU.apply(history, stripe_start, weight, bias, int(stripe_width), False)
+    return StripeConvReLU.apply(STRIPE_WIDE_OPS, history, stripe_start, weight, bias, int(stripe_width), False)
 
 
 def conv2d_wide_relu(x, weight, bias, relu=True, x_is_relu_output=False, padding=0):
@@ -378,7 +393,66 @@ def nb10_just_conv_f32(history, stripe_start, conv):
     2, 4, 6 nn.Conv2d; the nn.ReLU modules between them are fused into the layers' kernels).  Every inner ReLU output has one
     consumer, the next layer, whose data gradient leaves gated by it (x_is_relu_output), so its producer skips gating the
     arriving gradient (dy_pregated): no ReLU or mask kernel runs on its own.  The pairing only holds inside this chain."""
-    y = StripeConvReLU.apply(history, stripe_start, conv[0].weight, conv[0].bias, STRIPE_WIDTH, True)
+    y = StripeConvReLU.apply(STRIPE_WIDE_OPS, history, stripe_start, conv[0].weight, conv[0].bias, STRIPE_WIDTH, True)
     y = ConvReLU.apply(CONV2D_WIDE_OPS, y, conv[2].weight, conv[2].bias, True, True, True)
     y = ConvReLU.apply(CONV2D_WIDE_P2_OPS, y, conv[4].weight, conv[4].bias, True, True, True)
     return ConvReLU.apply(CONV2D_HEAD_S2_OPS, y, conv[6].weight, conv[6].bias, False, True, False)
+
+
+# ---- notebooks/09_horizon_represented_as_a_stripe.ipynb ------------------------------------------------------------------
+class MsePredWindow(torch.autograd.Function):
+    """F.mse_loss(y_hat[..., row0:row0 + T, col0:col0 + U], target): y_hat [N, P, Q] and target [N, T, U] f32; the gradient,
+    2 (y_hat - y) / count inside the window and exactly 0 outside, is produced in the same pass."""
+
+    @staticmethod
+    def forward(ctx, y_hat, target, row0, col0):
+        out, grad = K.mse_pred_window_f32(y_hat.contiguous(), target.contiguous(), row0, col0, need_grad=True)
+        ctx.save_for_backward(grad)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None
+
+
+def stripe_conv_s2_relu(history, stripe_start, weight, bias, stripe_width=STRIPE_WIDTH):
+    """relu(encoder_conv.0(cat(history, stripe plane))) of 09_horizon_represented_as_a_stripe.ipynb:1366-1367, 1382-1397,
+    stride 2; gradients to weight and bias only."""
+    return StripeConvReLU.apply(STRIPE_WIDE_S2_OPS, history, stripe_start, weight, bias, int(stripe_width), False)
+
+
+def conv2d_wide_s2_relu(x, weight, bias, relu=True, x_is_relu_output=False):
+    """nn.Conv2d(64 or 128, 128, 3, stride=2)(x) (+ ReLU), planes up to 128 wide.  x_is_relu_output: dx leaves gated by x > 0."""
+    return ConvReLU.apply(CONV2D_WIDE_S2_OPS, x, weight, bias, bool(relu), bool(x_is_relu_output), False)
+
+
+def conv_transpose2d_wide_s2_relu(x, weight, bias, relu=True, x_is_relu_output=False):
+    """nn.ConvTranspose2d(128, 128, 3, stride=2)(x) (+ ReLU).  x_is_relu_output: dx leaves gated by x > 0."""
+    return ConvReLU.apply(CONVT2D_WIDE_S2_OPS, x, weight, bias, bool(relu), bool(x_is_relu_output), False)
+
+
+def conv_transpose2d_head(x, weight, bias, x_is_relu_output=False):
+    """nn.ConvTranspose2d(C_in, 1, 3)(x), no ReLU.  x_is_relu_output: dx leaves gated by x > 0."""
+    return ConvReLU.apply(CONVT2D_HEAD_OPS, x, weight, bias, False, bool(x_is_relu_output), False)
+
+
+def mse_pred_window(y_hat, target, row0=0, col0=0):
+    """F.mse_loss(y_hat[..., row0:row0 + T, col0:col0 + U], target); (0, 0) with a target one smaller than y_hat is
+    F.mse_loss(y_hat[:, :, :-1, :-1], y.unsqueeze(1)) of 09_horizon_represented_as_a_stripe.ipynb:1402-1403."""
+    return MsePredWindow.apply(y_hat, target, int(row0), int(col0))
+
+
+def nb09_stripe_ae_f32(history, stripe_start, encoder_conv, decoder_conv):
+    """self.decoder_conv(self.encoder_conv(cat(hist_images, stripe plane))) of 09_horizon_represented_as_a_stripe.ipynb
+    :1366-1398; encoder_conv / decoder_conv = the notebook's two nn.Sequential (modules 0, 2, 4 nn.Conv2d / nn.ConvTranspose2d;
+    the nn.ReLU modules between them are fused into the layers' kernels).  Every inner ReLU output has one consumer, the next
+    layer, whose data gradient leaves gated by it (x_is_relu_output), so its producer skips gating the arriving gradient
+    (dy_pregated): no ReLU or mask kernel runs on its own.  The pairing only holds inside this chain."""
+    enc, dec = encoder_conv, decoder_conv
+    y = StripeConvReLU.apply(STRIPE_WIDE_S2_OPS, history, stripe_start, enc[0].weight, enc[0].bias, STRIPE_WIDTH, True)
+    for i in (2, 4):
+        y = ConvReLU.apply(CONV2D_WIDE_S2_OPS, y, enc[i].weight, enc[i].bias, True, True, True)
+    for i in (0, 2):
+        y = ConvReLU.apply(CONVT2D_WIDE_S2_OPS, y, dec[i].weight, dec[i].bias, True, True, True)
+    return ConvReLU.apply(CONVT2D_HEAD_OPS, y, dec[4].weight, dec[4].bias, False, True, False)

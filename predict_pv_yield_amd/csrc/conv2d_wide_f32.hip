@@ -18,13 +18,12 @@
 // LDS images are laid out against bank conflicts of the 32-lane read groups: the weight rows [tap][c] are 80 floats apart
 // and the input channel stride is 16 mod 32, so the two k-rows a half wave reads fall on disjoint banks; the staged dy rows
 // of the weight gradient are 98 floats apart (2 mod 32).  Staging walks whole rows per wave (lanes along columns): no
-// per-element division.  The slab sum, the input descriptor and the workspace check are shared (conv2d_f32_common.h).
-#include "conv2d_f32_common.h"
+// per-element division.  The slab sum, the input descriptor and the workspace check are shared (conv2d_f32_common.h), the
+// stripe source with the stride-2 file (conv2d_stripe_f32.h).
+#include "conv2d_stripe_f32.h"
 
 namespace pv {
 namespace {
-
-constexpr int SRC_STRIPE = SRC_COUNTS + 1;   // history [n][n_hist][h][w] + the stripe channel (this file only)
 
 // forward / dgrad: 4 x 16 output channels per block, 4 x 16 positions per wave (256 per block), 8 input channels per chunk
 constexpr int kMT = 4, kMB = kMT * 16, kMBP = kMB + 16, kNTW = 4, kCC = 8, kPos = 4 * kNTW * 16;
@@ -33,23 +32,6 @@ constexpr int kMaxTc = 62, kMaxTr = 64;      // the staged band is at most 64 co
 constexpr int kWgCC = 14, kWgNTW = 2, kWgPos = 96, kWgDps = kWgPos + 2, kWgMaxTc = 48, kWgMaxTr = 32;
 constexpr int kMaxWgBlocks = 512;
 constexpr int kMaxW = 128;                   // widest input plane of the wide family
-constexpr int kMaxHist = 7;
-
-struct Stripe {
-  const int32_t* start;    // [n] first column of the stripe (may lie outside the image)
-  int width, n_hist;
-};
-
-// input channel ch (< c_in) of image n at (r, c) inside the image
-template <int SRC>
-__device__ __forceinline__ float load_in(const In& s, const Stripe& sp, int n, int ch, int r, int c) {
-  if (SRC == SRC_STRIPE) {
-    if (ch < sp.n_hist) return s.x[(((size_t)n * sp.n_hist + ch) * s.h + r) * s.w + c];
-    const int st = sp.start[n];
-    return (c >= st && c - st < sp.width) ? 1.0f : 0.0f;
-  }
-  return load_plain(s, n, ch, r, c);
-}
 
 // Stage channels [c0, c0 + cc) x rows [r0, r0 + rows) x columns [col0, col0 + cols) of image n as lds[c * cs + r * sw +
 // col]; outside the image (padding) and beyond c_in: 0.  One row per wave and pass, one column per lane: cols <= 64.
@@ -478,12 +460,6 @@ int run_wgrad(const char* who, const In& in, const Stripe& sp, const In& dy, int
   if (rc) return rc;
   launch_slab_sum(ws, dw, db, dy.c_in, in.c_in * 9, p.n_slabs, st);
   return check_launch(who);
-}
-
-In stripe_in(const float* history, int n_hist, int h, int w) {
-  In s = {};
-  s.x = history, s.c_in = n_hist + 1, s.h = h, s.w = w;
-  return s;
 }
 
 // the head: ho x wo outputs, every tensor within 32-bit indexing

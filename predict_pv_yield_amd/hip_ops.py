@@ -1069,9 +1069,11 @@ def conv3d_general_bwd_weight_f32(x, dy, y_mask, weight_shape, stride=1, padding
 
 
 # ------------------------------------------------------------------------------------------------
-# Conv2d / ConvTranspose2d 3x3, exact f32, for four models: experiments/002 (conv2d_*, 17 / 32 -> 32 / 4 channels),
+# Conv2d / ConvTranspose2d 3x3, exact f32, for six models: experiments/002 (conv2d_*, 17 / 32 -> 32 / 4 channels),
 # experiments/001 (conv2d144_*, 144 -> 144, + MaxPool2d(3)), notebooks/16_maxpool.ipynb (conv2d_ae_* / convt2d_ae_*, + pool,
-# cropped normalised MSE) and notebooks/14, 15 (conv2d_s2_* / convt2d_s2_*, stride 2, windowed normalised MSE).
+# cropped normalised MSE), notebooks/14, 15 (conv2d_s2_* / convt2d_s2_*, stride 2, windowed normalised MSE), notebooks/10
+# (conv2d_wide_*, conv2d_head_s2_*: padded 64 / 128 channels, stripe first layer) and notebooks/09 (conv2d_wide_s2_*,
+# convt2d_wide_s2_*, convt2d_head_*: the same widths at stride 2, MSE over a window of the prediction).
 #
 # A family of entry points is described once, by a _ConvFamily record (its plain forward / data gradient / weight gradient)
 # and, where it has them, a _PoolFamily record (the same three passes with MaxPool2d(3) fused).  _conv_fwd, _conv_bwd_data,
@@ -1209,6 +1211,31 @@ def _check_head(who, x_shape, weight_shape):
                          f"{tuple(x_shape)}")
 
 
+def _check_wide_s2(who, x_shape, weight_shape):
+    _check_ae(who, x_shape, weight_shape)
+    n, ci, h, w = x_shape
+    if (ci, weight_shape[0]) not in WIDE_PAIRS:
+        raise ValueError(f"{who}: (C_in, C_out) = (64, 128) or (128, 128) expected, got ({ci}, {weight_shape[0]})")
+    if min(h, w) < 3 or w > WIDE_MAX_W:
+        raise ValueError(f"{who}: planes of at least 3 x 3 and at most {WIDE_MAX_W} columns expected, got {h} x {w}")
+
+
+def _check_widet_s2(who, x_shape, weight_shape):
+    _check_aet(who, x_shape, weight_shape)
+    n, ci, h, w = x_shape
+    if (ci, weight_shape[1]) != (128, 128):
+        raise ValueError(f"{who}: (C_in, C_out) = (128, 128) expected, got ({ci}, {weight_shape[1]})")
+    if min(h, w) < 1 or 2 * w + 1 > WIDE_MAX_W:
+        raise ValueError(f"{who}: a non-empty plane whose output is at most {WIDE_MAX_W} columns wide expected, got {h} x {w}")
+
+
+def _check_headt(who, x_shape, weight_shape):
+    _check_aet(who, x_shape, weight_shape)
+    if weight_shape[1] != 1 or x_shape[2] < 1 or x_shape[3] < 1 or x_shape[3] > WIDE_MAX_W:
+        raise ValueError(f"{who}: weight [C_in, 1, 3, 3] and a non-empty plane of at most {WIDE_MAX_W} columns expected, got "
+                         f"{tuple(weight_shape)} / {tuple(x_shape)}")
+
+
 def head_s2_out(side):
     """Side of a 3x3 stride-2 padding-2 Conv2d's output."""
     return (side + 1) // 2 + 1
@@ -1258,6 +1285,10 @@ _CONV2D_WIDE_P0 = _ConvFamily("conv2d_wide", lambda *a: _check_wide(*a, pad=0), 
 _CONV2D_WIDE_P2 = _ConvFamily("conv2d_wide", lambda *a: _check_wide(*a, pad=2), lambda h, w: (h + 2, w + 2), ws_args=(2,),
                               pad_args=(2,))
 _CONV2D_HEAD_S2 = _ConvFamily("conv2d_head_s2", lambda *a: _check_head(*a), lambda h, w: (head_s2_out(h), head_s2_out(w)))
+# notebook 09: the stride-2 64 / 128-channel layers and the one-output-channel ConvTranspose2d head (stride 1)
+_CONV2D_WIDE_S2 = _ConvFamily("conv2d_wide_s2", _check_wide_s2, _s2_hw)
+_CONVT2D_WIDE_S2 = _ConvFamily("convt2d_wide_s2", _check_widet_s2, lambda h, w: (2 * h + 1, 2 * w + 1), c_out_axis=1)
+_CONVT2D_HEAD = _ConvFamily("convt2d_head", _check_headt, lambda h, w: (h + 2, w + 2), c_out_axis=1)
 _CONV2D144_POOL = _PoolFamily("conv2d144", _check_c144_pooled, _pooled_shape, False)
 _CONV2D_AE_POOL = _PoolFamily("conv2d_ae", _check_ae, _pooled_shape_c, True)
 
@@ -1693,10 +1724,9 @@ def _check_stripe(who, history, stripe_start, stripe_width):
     return n, n_hist, h, w
 
 
-def conv2d_wide_stripe_fwd_f32(history, stripe_start, weight, bias, stripe_width):
-    """relu(conv2d(cat(history, stripe plane), weight) + bias): history [N, n_hist, H, W] f32, the stripe plane of example i is 1
-    on columns stripe_start[i] <= c < stripe_start[i] + stripe_width (inside the image) -> [N, 64, H - 2, W - 2]."""
-    who = "conv2d_wide_stripe_fwd_f32"
+def _stripe_fwd(fam, history, stripe_start, weight, bias, stripe_width):
+    """pv_{stem}_stripe_fwd_f32 on the family's output rule."""
+    who = f"{fam.stem}_stripe_fwd_f32"
     n, n_hist, h, w = _check_stripe(who, history, stripe_start, stripe_width)
     if tuple(weight.shape) != (STRIPE_C_OUT, n_hist + 1, 3, 3):
         raise ValueError(f"{who}: weight [{STRIPE_C_OUT}, {n_hist + 1}, 3, 3] expected, got {tuple(weight.shape)}")
@@ -1704,29 +1734,39 @@ def conv2d_wide_stripe_fwd_f32(history, stripe_start, weight, bias, stripe_width
         raise ValueError(f"{who}: bias [{STRIPE_C_OUT}] expected")
     require_cuda(weight, bias)
     _f32_contig(weight, bias)
-    y = torch.empty((n, STRIPE_C_OUT, h - 2, w - 2), dtype=torch.float32, device=history.device)
-    check(get_lib().pv_conv2d_wide_stripe_fwd_f32(ptr(history), ptr(stripe_start), ptr(weight), ptr(bias), ptr(y), n, n_hist,
-                                                  h, w, STRIPE_C_OUT, int(stripe_width), current_stream_ptr()),
-          "pv_" + who)
+    y = torch.empty((n, STRIPE_C_OUT, *fam.out_hw(h, w)), dtype=torch.float32, device=history.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(history), ptr(stripe_start), ptr(weight), ptr(bias), ptr(y), n, n_hist, h, w,
+                                          STRIPE_C_OUT, int(stripe_width), current_stream_ptr()), "pv_" + who)
     return y
 
 
-def conv2d_wide_stripe_bwd_weight_f32(history, stripe_start, dy, weight_shape, stripe_width):
-    """(dw [64, n_hist + 1, 3, 3], dbias) of conv2d_wide_stripe_fwd_f32's conv from its pre-activation gradient dy."""
-    who = "conv2d_wide_stripe_bwd_weight_f32"
+def _stripe_bwd_weight(fam, history, stripe_start, dy, weight_shape, stripe_width):
+    """pv_{stem}_stripe_bwd_weight_f32 on the family's output rule and weight-gradient workspace."""
+    who = f"{fam.stem}_stripe_bwd_weight_f32"
     n, n_hist, h, w = _check_stripe(who, history, stripe_start, stripe_width)
-    y_shape = (n, STRIPE_C_OUT, h - 2, w - 2)
+    y_shape = (n, STRIPE_C_OUT, *fam.out_hw(h, w))
     if tuple(weight_shape) != (STRIPE_C_OUT, n_hist + 1, 3, 3) or tuple(dy.shape) != y_shape:
         raise ValueError(f"{who}: weight {(STRIPE_C_OUT, n_hist + 1, 3, 3)} and dy {y_shape} expected, got "
                          f"{tuple(weight_shape)} / {tuple(dy.shape)}")
     require_cuda(dy)
     _f32_contig(dy)
-    ws, nbytes = _wgrad_ws("conv2d_wide", history.device, n, n_hist + 1, STRIPE_C_OUT, h, w, 0)
+    ws, nbytes = _wgrad_ws(fam.stem, history.device, n, n_hist + 1, STRIPE_C_OUT, h, w, *fam.ws_args)
     dw, db = _grads_out(weight_shape, STRIPE_C_OUT, history.device)
-    check(get_lib().pv_conv2d_wide_stripe_bwd_weight_f32(ptr(history), ptr(stripe_start), ptr(dy), ptr(dw), ptr(db), n, n_hist,
-                                                         h, w, STRIPE_C_OUT, int(stripe_width), ptr(ws), nbytes,
-                                                         current_stream_ptr()), "pv_" + who)
+    check(getattr(get_lib(), "pv_" + who)(ptr(history), ptr(stripe_start), ptr(dy), ptr(dw), ptr(db), n, n_hist, h, w,
+                                          STRIPE_C_OUT, int(stripe_width), ptr(ws), nbytes, current_stream_ptr()),
+          "pv_" + who)
     return dw, db
+
+
+def conv2d_wide_stripe_fwd_f32(history, stripe_start, weight, bias, stripe_width):
+    """relu(conv2d(cat(history, stripe plane), weight) + bias): history [N, n_hist, H, W] f32, the stripe plane of example i is 1
+    on columns stripe_start[i] <= c < stripe_start[i] + stripe_width (inside the image) -> [N, 64, H - 2, W - 2]."""
+    return _stripe_fwd(_CONV2D_WIDE_P0, history, stripe_start, weight, bias, stripe_width)
+
+
+def conv2d_wide_stripe_bwd_weight_f32(history, stripe_start, dy, weight_shape, stripe_width):
+    """(dw [64, n_hist + 1, 3, 3], dbias) of conv2d_wide_stripe_fwd_f32's conv from its pre-activation gradient dy."""
+    return _stripe_bwd_weight(_CONV2D_WIDE_P0, history, stripe_start, dy, weight_shape, stripe_width)
 
 
 def _wide_family(padding):
@@ -1782,6 +1822,85 @@ def mse_window_norm_f32(y_hat, target, row0=0, col0=0, need_grad=True):
     """mse_loss(y_hat, normalise(target)[..., row0:row0 + P, col0:col0 + Q]) for y_hat [N, P, Q] f32 and target [N, T, U]
     counts (int16 or f32).  Returns (loss f32[1], dy_hat or None)."""
     return _mse_norm("mse_window_norm", y_hat, target, (row0, col0), need_grad)
+
+
+# ---- notebooks/09_horizon_represented_as_a_stripe.ipynb: Conv2d 5 -> 64 -> 128 -> 128 and ConvTranspose2d 128 -> 128 -> 128,
+# all 3x3 stride 2, then ConvTranspose2d 128 -> 1 stride 1 (csrc/conv2d_wide_s2_f32.hip); planes up to 128 wide ----
+def conv2d_wide_s2_stripe_fwd_f32(history, stripe_start, weight, bias, stripe_width):
+    """relu(conv2d(cat(history, stripe plane), weight, stride=2) + bias) -> [N, 64, (H - 3) // 2 + 1, (W - 3) // 2 + 1]; the
+    stripe plane as in conv2d_wide_stripe_fwd_f32."""
+    return _stripe_fwd(_CONV2D_WIDE_S2, history, stripe_start, weight, bias, stripe_width)
+
+
+def conv2d_wide_s2_stripe_bwd_weight_f32(history, stripe_start, dy, weight_shape, stripe_width):
+    """(dw [64, n_hist + 1, 3, 3], dbias) of conv2d_wide_s2_stripe_fwd_f32's conv from its pre-activation gradient dy."""
+    return _stripe_bwd_weight(_CONV2D_WIDE_S2, history, stripe_start, dy, weight_shape, stripe_width)
+
+
+def conv2d_wide_s2_fwd_f32(x, weight, bias, relu=True):
+    """conv2d(x, weight, stride=2) + bias (+ ReLU) for (C_in, C_out) = (64, 128) or (128, 128), W <= 128."""
+    return _conv_fwd(_CONV2D_WIDE_S2, x, weight, bias, relu)
+
+
+def conv2d_wide_s2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of conv2d_wide_s2_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None).  The last
+    row / column of an even-sized x, which the forward never reads, is exactly 0."""
+    return _conv_bwd_data(_CONV2D_WIDE_S2, dy, dy_gate, weight, x_gate, x_shape)
+
+
+def conv2d_wide_s2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw, dbias) of conv2d_wide_s2_fwd_f32; deterministic (fixed slabs summed in order)."""
+    return _conv_bwd_weight(_CONV2D_WIDE_S2, x, dy, dy_gate, weight_shape)
+
+
+def convt2d_wide_s2_fwd_f32(x, weight, bias, relu=True):
+    """conv_transpose2d(x, weight [128, 128, 3, 3], stride=2) + bias (+ ReLU): [N, 128, H, W] -> [N, 128, 2H+1, 2W+1], 2W+1 <=
+    128."""
+    return _conv_fwd(_CONVT2D_WIDE_S2, x, weight, bias, relu)
+
+
+def convt2d_wide_s2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of convt2d_wide_s2_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
+    return _conv_bwd_data(_CONVT2D_WIDE_S2, dy, dy_gate, weight, x_gate, x_shape)
+
+
+def convt2d_wide_s2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw [128, 128, 3, 3], dbias) of convt2d_wide_s2_fwd_f32; deterministic."""
+    return _conv_bwd_weight(_CONVT2D_WIDE_S2, x, dy, dy_gate, weight_shape)
+
+
+def convt2d_head_fwd_f32(x, weight, bias, relu=False):
+    """conv_transpose2d(x, weight [C_in, 1, 3, 3]) + bias (+ ReLU): [N, C_in, H, W] -> [N, 1, H + 2, W + 2], W <= 128."""
+    return _conv_fwd(_CONVT2D_HEAD, x, weight, bias, relu)
+
+
+def convt2d_head_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of convt2d_head_fwd_f32, zeroed where x_gate <= 0 (may be None); dy_gate must be None (no ReLU follows the head)."""
+    return _conv_bwd_data(_CONVT2D_HEAD, dy, dy_gate, weight, x_gate, x_shape)
+
+
+def convt2d_head_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw [C_in, 1, 3, 3], dbias [1]) of convt2d_head_fwd_f32; deterministic; dy_gate must be None."""
+    return _conv_bwd_weight(_CONVT2D_HEAD, x, dy, dy_gate, weight_shape)
+
+
+def mse_pred_window_f32(y_hat, target, row0=0, col0=0, need_grad=True):
+    """mse_loss(y_hat[..., row0:row0 + T, col0:col0 + U], target) for y_hat [N, P, Q] and target [N, T, U], both f32.  Returns
+    (loss f32[1], dy_hat or None); dy_hat covers all of y_hat and is exactly 0 outside the window."""
+    who = "mse_pred_window_f32"
+    if not (y_hat.dim() == 3 and target.dim() == 3 and target.shape[0] == y_hat.shape[0]):
+        raise ValueError(f"{who}: y_hat [N, P, Q] and target [N, T, U] expected, got {tuple(y_hat.shape)} / "
+                         f"{tuple(target.shape)}")
+    require_cuda(y_hat, target)
+    _f32_contig(y_hat, target)
+    n, oh, ow = y_hat.shape
+    loss = torch.empty((1,), dtype=torch.float32, device=y_hat.device)
+    grad = torch.empty_like(y_hat) if need_grad else None
+    ws = _workspace("mse_pred_window", 4 * n, y_hat.device)
+    check(get_lib().pv_mse_pred_window_f32(ptr(y_hat), ptr(target), n, oh, ow, target.shape[1], target.shape[2], int(row0),
+                                           int(col0), ptr(loss), ptr(grad), ptr(ws), 4 * n, current_stream_ptr()),
+          "pv_" + who)
+    return loss, grad
 
 
 def maxpool3d_fwd_f32(x, kernel=3, stride=None, padding=0):

@@ -1,0 +1,209 @@
+"""Train-step time of notebooks/09_horizon_represented_as_a_stripe.ipynb's LitAutoEncoder (B x 4 x 128 x 128 normalised
+frames plus the horizon stripe, stride-2 Conv2d 5 -> 64 -> 128 -> 128, stride-2 ConvTranspose2d 128 -> 128 -> 128, ConvTranspose2d
+128 -> 1), eager and replayed as a HIP graph, and the device time of every conv launch of the step with its fraction of the
+f32 matrix peak.  Alongside, in the same process and on the same device: the same passes on the general Conv3d f32 route
+(kernel 1x3x3, stride 1x2x2) wherever it can express them -- a Conv2d's three passes as they stand (the 5-channel input
+materialised outside the timing); a ConvTranspose2d's forward as the data gradient of the convolution with the same weight
+tensor (no bias, no ReLU: the route has no epilogue there), its data gradient as that convolution's forward (no dy gate)
+and its weight gradient as that convolution's with x and dy swapped (no bias gradient), as tools/time_nb15.py does; the
+stride-1 head likewise at stride 1 -- and torch's own kernels (comparison only: the package never calls them).  Warm-up
+first, device-side event timing of INNER back-to-back calls per sample, the median of REPS alternating samples, inputs
+resident before the timed region.  Passes the general route refuses (128-channel weights beyond its LDS tile) are left out
+of both sums and named.  Prints a table and one JSON line; exits non-zero when the compared launches sum to more than the
+general route's (the requirement is a ratio <= 1.0).
+   python tools/time_nb09.py [batch=64] [reps=10]"""
+import json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import torch.nn.functional as F
+from predict_pv_yield_amd import hip_ops as K
+from predict_pv_yield_amd.conv2d_functional import STRIPE_WIDTH, stripe_start_from_horizon
+from predict_pv_yield_amd.graphs import GraphedTrainStep
+from predict_pv_yield_amd.models.conv2d.nb09_stripe_ae import LitAutoEncoder, target_side
+from predict_pv_yield_amd.optim import HipAdam
+
+dev = torch.device("cuda:0")
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+S = 128
+T = target_side(S)
+PEAK_TFLOPS = 157.3      # f32 matrix peak of the MI355X at its 2.4 GHz engine clock
+
+g = torch.Generator().manual_seed(1)
+batch = {"HISTORICAL_SAT_IMAGES": torch.randn(B, 4, S, S, generator=g).to(dev),
+         "FORECAST_HORIZON": torch.randint(1, 24, (B,), generator=g).to(dev),
+         "TARGET_SAT_IMAGE": torch.randn(B, T, T, generator=g).to(dev)}
+
+# ---- the train step ------------------------------------------------------------------------------------------------
+torch.manual_seed(0)
+model = LitAutoEncoder().to(dev)
+opt = model.configure_optimizers()
+
+
+def step():
+    opt.zero_grad(set_to_none=True)
+    model.training_step(batch, 0).backward()
+    opt.step()
+
+
+def wall(fn):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(REPS):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / REPS
+
+
+eager = wall(step)
+torch.manual_seed(0)
+gmodel = LitAutoEncoder().to(dev)
+gopt = HipAdam(gmodel.parameters(), lr=0.001, capturable=True)
+graphed = GraphedTrainStep(gmodel, gopt, batch, warmup=3)
+replay = wall(lambda: graphed(batch))
+graphed.close()
+
+# ---- every conv launch of the step -------------------------------------------------------------------------------------
+hist = batch["HISTORICAL_SAT_IMAGES"]
+start = stripe_start_from_horizon(batch["FORECAST_HORIZON"])
+P = lambda seq, i: (seq[i].weight.detach().contiguous(), seq[i].bias.detach().contiguous())      # noqa: E731
+(w1, b1), (w2, b2), (w3, b3) = (P(model.encoder_conv, i) for i in (0, 2, 4))
+(u1, c1), (u2, c2), (u3, c3) = (P(model.decoder_conv, i) for i in (0, 2, 4))
+y1 = K.conv2d_wide_s2_stripe_fwd_f32(hist, start, w1, b1, STRIPE_WIDTH)
+y2 = K.conv2d_wide_s2_fwd_f32(y1, w2, b2)
+y3 = K.conv2d_wide_s2_fwd_f32(y2, w3, b3)
+z1 = K.convt2d_wide_s2_fwd_f32(y3, u1, c1)
+z2 = K.convt2d_wide_s2_fwd_f32(z1, u2, c2)
+z3 = K.convt2d_head_fwd_f32(z2, u3, c3)
+rnd = lambda t: torch.randn(t.shape, generator=g).to(dev)      # noqa: E731
+dz3, dz2, dz1, dy3, dy2, dy1 = (rnd(t) for t in (z3, z2, z1, y3, y2, y1))
+cols = torch.arange(S, device=dev).view(1, 1, 1, S)
+stripe = ((cols >= start.view(-1, 1, 1, 1)) & (cols < start.view(-1, 1, 1, 1) + STRIPE_WIDTH)).float().expand(B, 1, S, S)
+x5 = torch.cat((hist, stripe), 1).contiguous()
+v5 = lambda t: t.unsqueeze(2)      # noqa: E731  [N, C, H, W] -> [N, C, 1, H, W] (a view; the kernels take NC(D)HW memory)
+
+
+def conv_rows(name, x, w, b, dy, ours_fwd, ours_dgrad, ours_wgrad, first=False):
+    """(name, GFLOP, ours, general Conv3d route, torch) of one stride-2 Conv2d layer's launches.  Both routes gate dx by the
+    layer input, as the step does."""
+    n, ci, h, wd = x.shape
+    co = w.shape[0]
+    gf = 2 * n * co * ci * 9 * dy.shape[2] * dy.shape[3] / 1e9
+    w5, shp5, st3 = v5(w), tuple(v5(x).shape), (1, 2, 2)
+    rows = [(f"{name} fwd", gf, ours_fwd, lambda: K.conv3d_general_fwd_f32(v5(x), w5, b, stride=st3, relu=True),
+             lambda: F.conv2d(x, w, b, stride=2))]
+    if not first:
+        rows.append((f"{name} dgrad", gf, ours_dgrad,
+                     lambda: K.conv3d_general_bwd_data_f32(v5(dy), None, w5, shp5, stride=st3, x_mask=v5(x)),
+                     lambda: torch.nn.grad.conv2d_input(tuple(x.shape), w, dy, stride=2)))
+    rows.append((f"{name} wgrad + db", gf, ours_wgrad,
+                 lambda: K.conv3d_general_bwd_weight_f32(v5(x), v5(dy), None, tuple(w5.shape), stride=st3),
+                 lambda: torch.nn.grad.conv2d_weight(x, tuple(w.shape), dy, stride=2)))
+    return rows
+
+
+def convt_rows(name, x, u, b, dy, stride, ours):
+    """... of one ConvTranspose2d layer's launches; ours = its (forward, data gradient, weight gradient) entry points."""
+    n, ci, h, wd = x.shape
+    co = u.shape[1]
+    gf = 2 * n * co * ci * 9 * h * wd / 1e9
+    u5, yshp5, st3 = v5(u), tuple(v5(dy).shape), (1, stride, stride)
+    relu = stride == 2
+    return [
+        (f"{name} fwd", gf, lambda: ours[0](x, u, b, relu=relu),
+         lambda: K.conv3d_general_bwd_data_f32(v5(x), None, u5, yshp5, stride=st3),
+         lambda: F.conv_transpose2d(x, u, b, stride=stride)),
+        (f"{name} dgrad", gf, lambda: ours[1](dy, None, u, x, tuple(x.shape)),
+         lambda: K.conv3d_general_fwd_f32(v5(dy), u5, None, stride=st3), lambda: F.conv2d(dy, u, stride=stride)),
+        (f"{name} wgrad + db", gf, lambda: ours[2](x, dy, None, tuple(u.shape)),
+         lambda: K.conv3d_general_bwd_weight_f32(v5(dy), v5(x), None, tuple(u5.shape), stride=st3, need_bias=False),
+         lambda: torch.nn.grad.conv2d_weight(dy, tuple(u.shape), x, stride=stride)),
+    ]
+
+
+WIDE_T = (K.convt2d_wide_s2_fwd_f32, K.convt2d_wide_s2_bwd_data_f32, K.convt2d_wide_s2_bwd_weight_f32)
+HEAD_T = (K.convt2d_head_fwd_f32, K.convt2d_head_bwd_data_f32, K.convt2d_head_bwd_weight_f32)
+cases = []
+cases += conv_rows("encoder_conv.0 5->64 (stripe synthesised)", x5, w1, b1, dy1,
+                   lambda: K.conv2d_wide_s2_stripe_fwd_f32(hist, start, w1, b1, STRIPE_WIDTH), None,
+                   lambda: K.conv2d_wide_s2_stripe_bwd_weight_f32(hist, start, dy1, tuple(w1.shape), STRIPE_WIDTH), first=True)
+for nm, x, w, b, dy in (("encoder_conv.2 64->128", y1, w2, b2, dy2), ("encoder_conv.4 128->128", y2, w3, b3, dy3)):
+    cases += conv_rows(nm, x, w, b, dy, lambda x=x, w=w, b=b: K.conv2d_wide_s2_fwd_f32(x, w, b),
+                       lambda x=x, w=w, dy=dy: K.conv2d_wide_s2_bwd_data_f32(dy, None, w, x, tuple(x.shape)),
+                       lambda x=x, w=w, dy=dy: K.conv2d_wide_s2_bwd_weight_f32(x, dy, None, tuple(w.shape)))
+cases += convt_rows("decoder_conv.0 T 128->128", y3, u1, c1, dz1, 2, WIDE_T)
+cases += convt_rows("decoder_conv.2 T 128->128", z1, u2, c2, dz2, 2, WIDE_T)
+cases += convt_rows("decoder_conv.4 T 128->1 (head)", z2, u3, c3, dz3, 1, HEAD_T)
+
+
+INNER = 4      # back-to-back calls per event pair
+
+
+def device_ms(fn):
+    e0, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(INNER):
+        fn()
+    e1_.record()
+    e1_.synchronize()
+    return e0.elapsed_time(e1_) / INNER
+
+
+def usable(fn, what):
+    try:
+        fn()
+        torch.cuda.synchronize()
+        return True
+    except Exception as e:            # a route that does not take a shape is reported, not timed
+        print(f"{what}: {type(e).__name__}: {str(e)[:200]}")
+        return False
+
+
+rows_out = []
+tot = {"ours": 0.0, "general": 0.0, "torch": 0.0, "gflop": 0.0}
+print(f"nb09 LitAutoEncoder B={B} {S}x{S}: eager {eager * 1e3:.3f} ms/step ({B / eager:.0f} samples/s), HIP graph "
+      f"{replay * 1e3:.3f} ms/step ({B / replay:.0f} samples/s)", flush=True)
+print(f"{'launch':50s} {'GFLOP':>7s} {'ours ms':>8s} {'of peak':>7s} {'general ms':>10s} {'torch ms':>9s}")
+unexpressed = []      # passes the general route refuses: left out of both sums of the ratio, and named
+tot_cmp = 0.0
+for name, gflop, ours, general, torch_fn in cases:
+    for _ in range(3):
+        ours()
+    ok_g, ok_t = usable(general, f"{name}: general Conv3d route"), usable(torch_fn, f"{name}: torch")
+    ta, tg, tt = [], [], []
+    for _ in range(REPS):     # alternate the three
+        ta.append(device_ms(ours))
+        if ok_g:
+            tg.append(device_ms(general))
+        if ok_t:
+            tt.append(device_ms(torch_fn))
+    med = lambda v: sorted(v)[len(v) // 2] if v else float("nan")      # noqa: E731
+    ma, mg, mt = med(ta), med(tg), med(tt)
+    if ok_g:
+        tot_cmp += ma
+    else:
+        unexpressed.append(name)
+    tot["ours"] += ma
+    tot["general"] += mg if ok_g else 0.0
+    tot["torch"] += mt if ok_t else 0.0
+    tot["gflop"] += gflop
+    rows_out.append({"launch": name, "gflop": round(gflop, 3), "ours_ms": round(ma, 4),
+                     "of_peak": round(gflop / ma / PEAK_TFLOPS, 4),
+                     "general_ms": round(mg, 4) if ok_g else None, "torch_ms": round(mt, 4) if ok_t else None})
+    print(f"{name:50s} {gflop:7.2f} {ma:8.3f} {gflop / ma / PEAK_TFLOPS:7.3f} {mg:10.3f} {mt:9.3f}", flush=True)
+ratio = tot_cmp / tot["general"] if tot["general"] > 0 else None
+print(f"the step's launches the general Conv3d f32 route can express: {tot_cmp:.3f} ms against its {tot['general']:.3f} ms, "
+      f"ratio {ratio} (required <= 1.0); it refuses: {unexpressed}")
+print(f"{'conv launches of a step (median each, summed)':50s} {tot['gflop']:7.2f} {tot['ours']:8.3f} "
+      f"{tot['gflop'] / tot['ours'] / PEAK_TFLOPS:7.3f} {tot['general']:10.3f} {tot['torch']:9.3f}")
+print(json.dumps({"tool": "time_nb09", "batch": B, "image": S, "reps": REPS, "eager_ms": round(eager * 1e3, 4),
+                  "graph_ms": round(replay * 1e3, 4), "samples_per_s_graph": round(B / replay, 1),
+                  "step_gflop": round(tot["gflop"], 2), "step_of_peak_graph": round(tot["gflop"] / replay / 1e3 / PEAK_TFLOPS, 4),
+                  "launches_ours_ms": round(tot["ours"], 4), "launches_ours_compared_ms": round(tot_cmp, 4),
+                  "general_route_refuses": unexpressed, "launches_general_ms": round(tot["general"], 4),
+                  "launches_torch_ms": round(tot["torch"], 4), "ours_over_general": round(ratio, 4) if ratio else None,
+                  "calls_per_sample": INNER, "launches": rows_out}))
+if ratio is None or ratio > 1.0:
+    sys.exit(f"time_nb09: the step's launches take {ratio} x the general Conv3d f32 route's time; the requirement is <= 1.0")
