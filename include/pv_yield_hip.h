@@ -586,6 +586,63 @@ int pv_mse_pred_window_f32(const float* y_hat, const float* target, int32_t n, i
                            int32_t target_h, int32_t target_w, int32_t row0, int32_t col0, float* loss, float* dy_hat,
                            void* ws, size_t ws_bytes, void* stream);
 
+/* ---- notebooks/12_just_3d_conv.ipynb: Conv3d (2, 3, 3) on 64 / 128 channels, horizon channel, stride-2 head ---- */
+/* (line numbers: the raw 12_just_3d_conv.ipynb file; the LitAutoEncoder cell starts at 1388, its nn.Sequential is at
+ * 1397-1407, forward at 1409-1420.)  NCDHW f32, exact f32; gates (NULL = none) and weight-gradient slabs follow the
+ * conventions of the pv_conv2d_wide_* entry points above.  (d_in, h_in, w_in) is always the extent of the layer's input x.
+ * pv_conv3d_wide_*: kernel (2, 3, 3), stride 1, pad_hw = 1, pad_d = 0 or 1 (zeros), d -> d + 2 pad_d - 1 >= 1; (c_in, c_out)
+ * = (64, 128) or (128, 128); w_in <= 128; every tensor below 2^31 elements.  Unsupported shapes return PV_ESIZE, null
+ * pointers PV_EINVAL, before any launch. */
+/* replaces: nn.Conv3d(64, 128, KERNEL, padding=(0, 1, 1)) / nn.Conv3d(128, 128, KERNEL, padding=(1, 1, 1) | (0, 1, 1)) (+
+ * nn.ReLU() if relu), conv.2 / conv.4 / conv.6 of 12_just_3d_conv.ipynb:1400-1405.  w [c_out][c_in][2][3][3]; bias may be
+ * NULL. */
+int pv_conv3d_wide_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                           int32_t c_out, int32_t d_in, int32_t h_in, int32_t w_in, int32_t pad_d, int32_t pad_hw,
+                           int32_t relu, void* stream);
+/* replaces: the input gradient of conv.2 / conv.4 / conv.6 (autograd of 12_just_3d_conv.ipynb:1400-1405): the same kernel
+ * on dy with depth padding 1 - pad_d and weights mirrored in all three axes, channel roles swapped.  dy zeroed where
+ * dy_gate <= 0, dx zeroed where x_gate <= 0. */
+int pv_conv3d_wide_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                                int32_t n, int32_t c_in, int32_t c_out, int32_t d_in, int32_t h_in, int32_t w_in,
+                                int32_t pad_d, int32_t pad_hw, void* stream);
+/* bytes of the weight-gradient workspace: one partial [c_out][c_in * 18 + 1] per slab of tiles, and with pad_d = 1 a second
+ * bias partial [c_out] per slab (from the blocks of depth tap 1, for the output slice whose tap 0 reads padding) */
+int pv_conv3d_wide_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t d_in, int32_t h_in,
+                                              int32_t w_in, int32_t pad_d, int32_t pad_hw, size_t* bytes);
+/* replaces: the weight and bias gradients of conv.2 / conv.4 / conv.6.  dw [c_out][c_in][2][3][3] and dbias [c_out] are
+ * overwritten; slab partials summed in slab order (no atomics, identical bits run to run). */
+int pv_conv3d_wide_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias,
+                                  int32_t n, int32_t c_in, int32_t c_out, int32_t d_in, int32_t h_in, int32_t w_in,
+                                  int32_t pad_d, int32_t pad_hw, void* ws, size_t ws_bytes, void* stream);
+/* replaces: x[FORECAST_HORIZON].view(-1, 1, 1, 1, 1).expand(...); torch.cat((hist_images.unsqueeze(1), forecast_horizon),
+ * dim=1); nn.Conv3d(2, 64, KERNEL, padding=(0, 1, 1)); nn.ReLU(), 12_just_3d_conv.ipynb:1398-1399, 1413-1418.  history
+ * [n][d_in][h][w], d_in >= 2; horizon [n] (device f32): input channel 1 is horizon[i] inside the image and 0 in the spatial
+ * padding, synthesised in the kernel; w [64][2][2][3][3]; y [n][64][d_in - 1][h][w]; c_out = 64; w_img <= 128. */
+int pv_conv3d_wide_horizon_fwd_f32(const float* history, const float* horizon, const float* w, const float* bias, float* y,
+                                   int32_t n, int32_t d_in, int32_t h, int32_t w_img, int32_t c_out, void* stream);
+int pv_conv3d_wide_horizon_bwd_weight_workspace_bytes(int32_t n, int32_t d_in, int32_t h, int32_t w_img, int32_t c_out,
+                                                      size_t* bytes);
+/* replaces: the weight and bias gradients of conv.0 (autograd of 12_just_3d_conv.ipynb:1398), re-synthesising the horizon
+ * channel as the forward does; dy is the pre-activation gradient.  dw [64][2][2][3][3]. */
+int pv_conv3d_wide_horizon_bwd_weight_f32(const float* history, const float* horizon, const float* dy, float* dw,
+                                          float* dbias, int32_t n, int32_t d_in, int32_t h, int32_t w_img, int32_t c_out,
+                                          void* ws, size_t ws_bytes, void* stream);
+/* replaces: nn.Conv3d(128, 1, KERNEL, stride=(1, 2, 2), padding=(0, 1, 1)), conv.8 of 12_just_3d_conv.ipynb:1406, on an
+ * input of depth 2, where it equals a 3x3 stride-2 padding-1 Conv2d on the views x [n][2 c][h][w], w [1][2 c][3][3] (+ ReLU
+ * if relu).  c_out = 1, any c_in >= 1, h -> (h - 1) / 2 + 1; vector code, sums in a fixed order; bias may be NULL. */
+int pv_conv2d_head_s2p1_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                                int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of conv.8: every dx element written once from the at most four taps of its parity class,
+ * zeroed where x_gate <= 0.  dy_gate must be NULL (no ReLU follows the head). */
+int pv_conv2d_head_s2p1_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                                     int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+int pv_conv2d_head_s2p1_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                                   size_t* bytes);
+/* replaces: the weight and bias gradients of conv.8: dw [1][c_in][3][3], dbias [1]; deterministic; dy_gate must be NULL. */
+int pv_conv2d_head_s2p1_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias,
+                                       int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
+                                       size_t ws_bytes, void* stream);
+
 /* MaxPool3d over x[B*C planes][Ti,Hi,Wi]; argmax (may be NULL) = flat winner offset inside the plane stack, first
  * maximum wins, NaN propagates (torch CPU semantics).  bwd overwrites dx by gathering dy through argmax. */
 int pv_maxpool3d_fwd_f32(const float* x, float* y, int32_t* argmax, const pv_conv3d_geom* d, void* stream);

@@ -104,6 +104,14 @@ _PAD_BWD_DATA = [c_vp] * 5 + _DIMS5 + [c_i32, c_vp]                  # dy, dy_ga
 _PAD_BWD_WEIGHT = [c_vp] * 5 + _DIMS5 + [c_i32] + _WORKSPACE + [c_vp]      # x, dy, dy_gate, dw, dbias, dims, pad
 _STRIPE_FWD = [c_vp] * 5 + [c_i32] * 6 + [c_vp]                      # history, stripe_start, weight, bias, y
 _STRIPE_BWD_WEIGHT = [c_vp] * 5 + [c_i32] * 6 + _WORKSPACE + [c_vp]  # history, stripe_start, dy, dw, dbias
+# ... the (2, 3, 3) Conv3d wide family (notebook 12) takes (n, c_in, c_out, d, h, w, pad_d, pad_hw); its horizon first layer
+# takes (n, d, h, w, c_out) after its pointers
+_DIMS3D = [c_i32] * 8
+_C3D_FWD = [c_vp] * 4 + _DIMS3D + [c_i32, c_vp]                      # x, weight, bias, y, dims, relu
+_C3D_BWD_DATA = [c_vp] * 5 + _DIMS3D + [c_vp]                        # dy, dy_gate, weight, dx, x_gate, dims
+_C3D_BWD_WEIGHT = [c_vp] * 5 + _DIMS3D + _WORKSPACE + [c_vp]         # x, dy, dy_gate, dw, dbias, dims
+_HORIZON_FWD = [c_vp] * 5 + [c_i32] * 5 + [c_vp]                     # history, horizon, weight, bias, y
+_HORIZON_BWD_WEIGHT = [c_vp] * 5 + [c_i32] * 5 + _WORKSPACE + [c_vp]  # history, horizon, dy, dw, dbias
 _MSE_NORM_TAIL = [c_vp, c_vp] + _WORKSPACE + [c_vp]                  # loss, grad, workspace, stream
 
 
@@ -222,6 +230,14 @@ SIGNATURES = {
     **_conv2d_family("convt2d_wide_s2", _WS_QUERY5),
     **_conv2d_family("convt2d_head", _WS_QUERY5),
     "pv_mse_pred_window_f32": [c_vp, c_vp] + [c_i32] * 7 + _MSE_NORM_TAIL,     # y_hat, target, (n, sides, row0, col0)
+    "pv_conv3d_wide_fwd_f32": _C3D_FWD,
+    "pv_conv3d_wide_bwd_data_f32": _C3D_BWD_DATA,
+    "pv_conv3d_wide_bwd_weight_workspace_bytes": _DIMS3D + [ctypes.POINTER(c_sz)],
+    "pv_conv3d_wide_bwd_weight_f32": _C3D_BWD_WEIGHT,
+    "pv_conv3d_wide_horizon_fwd_f32": _HORIZON_FWD,
+    "pv_conv3d_wide_horizon_bwd_weight_workspace_bytes": _DIMS5 + [ctypes.POINTER(c_sz)],
+    "pv_conv3d_wide_horizon_bwd_weight_f32": _HORIZON_BWD_WEIGHT,
+    **_conv2d_family("conv2d_head_s2p1", _WS_QUERY5),
     "pv_maxpool3d_fwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_maxpool3d_bwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_mse_loss_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp],

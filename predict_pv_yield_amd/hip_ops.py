@@ -1903,6 +1903,187 @@ def mse_pred_window_f32(y_hat, target, row0=0, col0=0, need_grad=True):
     return loss, grad
 
 
+# ---- notebooks/12_just_3d_conv.ipynb: Conv3d 2 -> 64 -> 128 -> 128 -> 128 -> 1, kernel (2, 3, 3), spatial padding 1, the
+# second input channel the forecast horizon (csrc/conv3d_wide_f32.hip); planes up to 128 wide.  The depth axis does not fit a
+# _ConvFamily record, so the family's one shape rule is _check_conv3d_wide and its three passes are written once below. ----
+HORIZON_C_OUT = 64
+
+
+def head_s2p1_out(side):
+    """Side of a 3x3 stride-2 padding-1 Conv2d's output."""
+    return (side - 1) // 2 + 1
+
+
+_CONV2D_HEAD_S2P1 = _ConvFamily("conv2d_head_s2p1", lambda *a: _check_head(*a),
+                                lambda h, w: (head_s2p1_out(h), head_s2p1_out(w)))
+
+
+def _check_conv3d_wide(who, x_shape, weight_shape, padding):
+    """The shape rule of pv_conv3d_wide_*: x [N, C_in, D, H, W], weight [C_out, C_in, 2, 3, 3], padding (0 | 1, 1, 1).
+    Returns the entry points' (n, c_in, c_out, d, h, w, pad_d, pad_hw) and the output's shape."""
+    if not (len(x_shape) == 5 and len(weight_shape) == 5 and tuple(weight_shape[1:]) == (x_shape[1], 2, 3, 3)):
+        raise ValueError(f"{who}: x [N, C_in, D, H, W] and weight [C_out, C_in, 2, 3, 3] expected, got {tuple(x_shape)} / "
+                         f"{tuple(weight_shape)}")
+    n, ci, d, h, w = (int(v) for v in x_shape)
+    co = int(weight_shape[0])
+    if (ci, co) not in WIDE_PAIRS:
+        raise ValueError(f"{who}: (C_in, C_out) = (64, 128) or (128, 128) expected, got ({ci}, {co})")
+    padding = tuple(int(p) for p in padding)
+    if len(padding) != 3 or padding[0] not in (0, 1) or padding[1:] != (1, 1):
+        raise ValueError(f"{who}: padding (0, 1, 1) or (1, 1, 1) expected, got {padding}")
+    d_out = d + 2 * padding[0] - 1
+    if d_out < 1 or min(h, w) < 1 or w > WIDE_MAX_W:
+        raise ValueError(f"{who}: an output of at least one slice and planes of 1 to {WIDE_MAX_W} columns expected, got "
+                         f"{tuple(x_shape)} with padding {padding}")
+    return (n, ci, co, d, h, w, padding[0], 1), (n, co, d_out, h, w)
+
+
+def conv3d_wide_fwd_f32(x, weight, bias, relu=True, padding=(0, 1, 1)):
+    """conv3d(x, weight, stride 1, padding (0 | 1, 1, 1)) + bias (+ ReLU): [N, 64 | 128, D, H, W] f32 -> [N, 128, D + 2 pd - 1,
+    H, W]; weight [128, C_in, 2, 3, 3]."""
+    who = "conv3d_wide_fwd_f32"
+    dims, y_shape = _check_conv3d_wide(who, x.shape, weight.shape, padding)
+    _check_bias(who, bias, dims[2])
+    require_cuda(x, weight, bias)
+    _f32_contig(x, weight, bias)
+    y = torch.empty(y_shape, dtype=torch.float32, device=x.device)
+    check(get_lib().pv_conv3d_wide_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), *dims, int(relu), current_stream_ptr()),
+          "pv_" + who)
+    return y
+
+
+def conv3d_wide_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape, padding=(0, 1, 1)):
+    """dx of conv3d_wide_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
+    who = "conv3d_wide_bwd_data_f32"
+    dims, y_shape = _check_conv3d_wide(who, x_shape, weight.shape, padding)
+    if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
+        raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    if x_gate is not None and tuple(x_gate.shape) != tuple(x_shape):
+        raise ValueError(f"{who}: x_gate {tuple(x_shape)} expected")
+    require_cuda(dy, dy_gate, weight, x_gate)
+    _f32_contig(dy, dy_gate, weight, x_gate)
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
+    check(get_lib().pv_conv3d_wide_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), *dims,
+                                                current_stream_ptr()), "pv_" + who)
+    return dx
+
+
+def conv3d_wide_bwd_weight_f32(x, dy, dy_gate, weight_shape, padding=(0, 1, 1)):
+    """(dw, dbias) of conv3d_wide_fwd_f32; deterministic (fixed slabs summed in order)."""
+    who = "conv3d_wide_bwd_weight_f32"
+    dims, y_shape = _check_conv3d_wide(who, x.shape, weight_shape, padding)
+    if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
+        raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    require_cuda(x, dy, dy_gate)
+    _f32_contig(x, dy, dy_gate)
+    ws, nbytes = _wgrad_ws("conv3d_wide", x.device, *dims)
+    dw, db = _grads_out(weight_shape, dims[2], x.device)
+    check(get_lib().pv_conv3d_wide_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), *dims, ptr(ws), nbytes,
+                                                  current_stream_ptr()), "pv_" + who)
+    return dw, db
+
+
+def _check_horizon(who, history, horizon, weight_shape):
+    if history.dim() != 4 or history.shape[1] < 2:
+        raise ValueError(f"{who}: history [N, D >= 2, H, W] expected, got {tuple(history.shape)}")
+    n, d, h, w = (int(v) for v in history.shape)
+    if tuple(horizon.shape) != (n,):
+        raise ValueError(f"{who}: horizon [{n}] expected, got {tuple(horizon.shape)}")
+    if tuple(weight_shape) != (HORIZON_C_OUT, 2, 2, 3, 3):
+        raise ValueError(f"{who}: weight [{HORIZON_C_OUT}, 2, 2, 3, 3] expected, got {tuple(weight_shape)}")
+    if min(h, w) < 1 or w > WIDE_MAX_W:
+        raise ValueError(f"{who}: planes of 1 to {WIDE_MAX_W} columns expected, got {h} x {w}")
+    require_cuda(history, horizon)
+    _f32_contig(history, horizon)
+    return n, d, h, w
+
+
+def conv3d_wide_horizon_fwd_f32(history, horizon, weight, bias):
+    """relu(conv3d(cat(history.unsqueeze(1), horizon plane), weight, padding (0, 1, 1)) + bias): history [N, D, H, W] f32, the
+    second input channel of example i is horizon[i] everywhere inside the image -> [N, 64, D - 1, H, W]."""
+    who = "conv3d_wide_horizon_fwd_f32"
+    n, d, h, w = _check_horizon(who, history, horizon, weight.shape)
+    if bias is None or tuple(bias.shape) != (HORIZON_C_OUT,):
+        raise ValueError(f"{who}: bias [{HORIZON_C_OUT}] expected")
+    require_cuda(weight, bias)
+    _f32_contig(weight, bias)
+    y = torch.empty((n, HORIZON_C_OUT, d - 1, h, w), dtype=torch.float32, device=history.device)
+    check(get_lib().pv_conv3d_wide_horizon_fwd_f32(ptr(history), ptr(horizon), ptr(weight), ptr(bias), ptr(y), n, d, h, w,
+                                                   HORIZON_C_OUT, current_stream_ptr()), "pv_" + who)
+    return y
+
+
+def conv3d_wide_horizon_bwd_weight_f32(history, horizon, dy, weight_shape):
+    """(dw [64, 2, 2, 3, 3], dbias) of conv3d_wide_horizon_fwd_f32's conv from its pre-activation gradient dy."""
+    who = "conv3d_wide_horizon_bwd_weight_f32"
+    n, d, h, w = _check_horizon(who, history, horizon, weight_shape)
+    y_shape = (n, HORIZON_C_OUT, d - 1, h, w)
+    if tuple(dy.shape) != y_shape:
+        raise ValueError(f"{who}: dy {y_shape} expected, got {tuple(dy.shape)}")
+    require_cuda(dy)
+    _f32_contig(dy)
+    ws, nbytes = _wgrad_ws("conv3d_wide_horizon", history.device, n, d, h, w, HORIZON_C_OUT)
+    dw, db = _grads_out(weight_shape, HORIZON_C_OUT, history.device)
+    check(get_lib().pv_conv3d_wide_horizon_bwd_weight_f32(ptr(history), ptr(horizon), ptr(dy), ptr(dw), ptr(db), n, d, h, w,
+                                                          HORIZON_C_OUT, ptr(ws), nbytes, current_stream_ptr()), "pv_" + who)
+    return dw, db
+
+
+def conv2d_head_s2p1_fwd_f32(x, weight, bias, relu=False):
+    """conv2d(x, weight, stride 2, padding 1) + bias (+ ReLU): [N, C_in, H, W] f32 -> [N, 1, (H - 1) // 2 + 1, (W - 1) // 2 + 1]."""
+    return _conv_fwd(_CONV2D_HEAD_S2P1, x, weight, bias, relu)
+
+
+def conv2d_head_s2p1_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of conv2d_head_s2p1_fwd_f32, zeroed where x_gate <= 0 (may be None); dy_gate must be None (no ReLU follows the head)."""
+    return _conv_bwd_data(_CONV2D_HEAD_S2P1, dy, dy_gate, weight, x_gate, x_shape)
+
+
+def conv2d_head_s2p1_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw [1, C_in, 3, 3], dbias [1]) of conv2d_head_s2p1_fwd_f32; deterministic; dy_gate must be None."""
+    return _conv_bwd_weight(_CONV2D_HEAD_S2P1, x, dy, dy_gate, weight_shape)
+
+
+def _head_d2_views(who, x_shape, weight_shape):
+    """conv3d(x, weight, stride (1, 2, 2), padding (0, 1, 1)) with weight [1, C, 2, 3, 3] on an input of depth 2 is the 3x3
+    stride-2 padding-1 Conv2d on x [N, 2 C, H, W] and weight [1, 2 C, 3, 3]: both are views (depth is the axis after the
+    channels).  Any other depth is refused."""
+    if not (len(x_shape) == 5 and len(weight_shape) == 5 and tuple(weight_shape) == (1, x_shape[1], 2, 3, 3)):
+        raise ValueError(f"{who}: x [N, C, 2, H, W] and weight [1, C, 2, 3, 3] expected, got {tuple(x_shape)} / "
+                         f"{tuple(weight_shape)}")
+    n, c, d, h, w = (int(v) for v in x_shape)
+    if d != 2:
+        raise ValueError(f"{who}: an input of depth 2 expected (one output slice), got depth {d}")
+    return (n, 2 * c, h, w), (1, 2 * c, 3, 3)
+
+
+def conv3d_head_d2_fwd_f32(x, weight, bias, relu=False):
+    """conv3d(x [N, C, 2, H, W], weight [1, C, 2, 3, 3], stride (1, 2, 2), padding (0, 1, 1)) + bias -> [N, 1, 1, H', W']."""
+    x2, w2 = _head_d2_views("conv3d_head_d2_fwd_f32", x.shape, weight.shape)
+    _f32_contig(x, weight)
+    return conv2d_head_s2p1_fwd_f32(x.view(x2), weight.view(w2), bias, relu).unsqueeze(2)
+
+
+def conv3d_head_d2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx [N, C, 2, H, W] of conv3d_head_d2_fwd_f32 from dy [N, 1, 1, H', W'], zeroed where x_gate <= 0; dy_gate must be None."""
+    x2, w2 = _head_d2_views("conv3d_head_d2_bwd_data_f32", x_shape, weight.shape)
+    _f32_contig(dy, weight, x_gate)
+    if dy.dim() != 5 or dy.shape[2] != 1:
+        raise ValueError(f"conv3d_head_d2_bwd_data_f32: dy [N, 1, 1, H', W'] expected, got {tuple(dy.shape)}")
+    dx = conv2d_head_s2p1_bwd_data_f32(dy.squeeze(2), dy_gate, weight.view(w2), None if x_gate is None else x_gate.view(x2), x2)
+    return dx.view(tuple(x_shape))
+
+
+def conv3d_head_d2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw [1, C, 2, 3, 3], dbias [1]) of conv3d_head_d2_fwd_f32; deterministic; dy_gate must be None."""
+    x2, w2 = _head_d2_views("conv3d_head_d2_bwd_weight_f32", x.shape, weight_shape)
+    _f32_contig(x, dy)
+    if dy.dim() != 5 or dy.shape[2] != 1:
+        raise ValueError(f"conv3d_head_d2_bwd_weight_f32: dy [N, 1, 1, H', W'] expected, got {tuple(dy.shape)}")
+    dw, db = conv2d_head_s2p1_bwd_weight_f32(x.view(x2), dy.squeeze(2), dy_gate, w2)
+    return dw.view(tuple(weight_shape)), db
+
+
 def maxpool3d_fwd_f32(x, kernel=3, stride=None, padding=0):
     require_cuda(x)
     b, c, t, h, w = x.shape

@@ -1,0 +1,373 @@
+"""GPU: the 64 / 128-channel (2, 3, 3) Conv3d frame predictor of notebooks/12_just_3d_conv.ipynb (csrc/conv3d_wide_f32.hip,
+conv3d_wide_functional, models/conv3d/nb12_just_3d_conv.py) against float64 on the CPU.
+
+Tolerances are the project's own for exact-f32 conv kernels (conv2d_f32_helpers): ELEM_TOL = 1e-6 per element relative to the
+element's float64 sum of |products|, NORM_TOL = 1e-5 relative norm for reductions (weight and bias gradients).  A float32
+running sum's error relative to sum|p| does not grow with K, so the 2 304 products of a 128-channel output need no wider
+bound; torch float32 on the CPU is itself 6.4e-8 (elements) and 6.2e-7 (weight gradient) from float64 at these shapes, which
+leaves the reference more than 15 x margin.
+
+Parameters after three Adam steps (golden), the rule stated at the top of tests/test_gpu_nb15.py scaled to the notebook's lr =
+1e-4: Adam's step is about lr whatever the gradient's size, so 99 % of the (stored) entries of every tensor must agree to 1e-6;
+the rest are entries whose gradient is ~ 0 and may take either sign in two correct implementations: 2 * lr per step, 3 * 2e-4
+(+ 1e-6) in all; and the median entry must have moved by at least 1e-5.
+"""
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import nb12_reference as R
+from conv2d_f32_helpers import NORM_TOL, ROOT, _ops, _rel, _to, _within
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "nb12_small.npz")
+# (batch, depth, height, width) of the layer's input.  Depth padding 0: one voxel (eight of nine taps padding); odd sides;
+# several row bands; full width (three column bands); an odd width over one band.  Depth padding 1: each output slice sees one
+# real and one skipped slice; small; wide
+WIDE_SHAPES = {0: [(1, 2, 1, 1), (2, 3, 5, 7), (2, 4, 9, 50), (1, 2, 6, 128), (2, 3, 7, 47)],
+               1: [(1, 1, 1, 1), (2, 2, 2, 5), (1, 2, 12, 124)]}
+HORIZON_SHAPES = [(1, 128, 128), (2, 9, 50), (3, 5, 7)]
+HEAD_SHAPES = [(1, 1, 1), (2, 4, 5), (3, 10, 47), (2, 9, 46), (1, 128, 128)]
+GATES = ((True, True), (False, False))      # (dy_gate, x_gate): every gradient with and without its gates
+
+
+def _g(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _randn(g, *shape, scale=1.0):
+    return torch.randn(*shape, generator=g) * scale
+
+
+def _conv_params(g, c_out, c_in, kernel=(2, 3, 3)):
+    return _randn(g, c_out, c_in, *kernel, scale=(int(np.prod(kernel)) * c_in) ** -0.5), _randn(g, c_out, scale=0.1)
+
+
+# ---- 1. the wide family ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("c_in", [64, 128])
+@pytest.mark.parametrize("pd, n, d, h, w", [(p, *s) for p, shapes in WIDE_SHAPES.items() for s in shapes])
+def test_wide_conv3d_against_float64(device, c_in, pd, n, d, h, w):
+    """Forward, data gradient (128 -> c_in, so also 128 -> 64) and weight / bias gradient against float64 F.conv3d."""
+    K = _ops()
+    pad = (pd, 1, 1)
+    g = _g(300 + 7 * w + c_in + pd + 13 * d)
+    x = _randn(g, n, c_in, d, h, w)
+    wt, b = _conv_params(g, 128, c_in)
+    x64, w64, b64 = x.double(), wt.double(), b.double()
+    pre = F.conv3d(x64, w64, b64, padding=pad)
+    absref = F.conv3d(x64.abs(), w64.abs(), b64.abs(), padding=pad)
+    assert tuple(pre.shape) == (n, 128, d + 2 * pd - 1, h, w)
+    xd, wd, bd = x.to(device), wt.to(device), b.to(device)
+    y = K.conv3d_wide_fwd_f32(xd, wd, bd, relu=True, padding=pad)
+    assert tuple(y.shape) == tuple(pre.shape)
+    _within(y, pre.relu(), absref, what="forward relu")
+    _within(K.conv3d_wide_fwd_f32(xd, wd, bd, relu=False, padding=pad), pre, absref, what="forward without relu")
+    _within(K.conv3d_wide_fwd_f32(xd, wd, None, relu=False, padding=pad), pre - b64.view(1, -1, 1, 1, 1), absref,
+            what="forward plain")
+    dy = _randn(g, *pre.shape)
+    dy_gate, x_gate = _randn(g, *pre.shape), _randn(g, *x.shape)
+    for use_dg, use_xg in GATES:
+        dyg = dy.double() * (dy_gate > 0) if use_dg else dy.double()
+        gate_d = dy_gate.to(device) if use_dg else None
+        dx64 = F.conv_transpose3d(dyg, w64, padding=pad)
+        absdx = F.conv_transpose3d(dyg.abs(), w64.abs(), padding=pad)
+        assert tuple(dx64.shape) == tuple(x.shape)
+        if use_xg:
+            dx64 = dx64 * (x_gate > 0)
+        dx = K.conv3d_wide_bwd_data_f32(dy.to(device), gate_d, wd, x_gate.to(device) if use_xg else None, tuple(x.shape),
+                                        padding=pad)
+        assert tuple(dx.shape) == tuple(x.shape)
+        _within(dx, dx64, absdx, what=f"dx gates {use_dg} {use_xg}")
+        dw, db = K.conv3d_wide_bwd_weight_f32(xd, dy.to(device), gate_d, tuple(wt.shape), padding=pad)
+        dw2, db2 = K.conv3d_wide_bwd_weight_f32(xd, dy.to(device), gate_d, tuple(wt.shape), padding=pad)
+        assert torch.equal(dw, dw2) and torch.equal(db, db2), "the weight gradient's bits differ run to run"
+        assert tuple(dw.shape) == tuple(wt.shape) and tuple(db.shape) == (128,)
+        err_w = _rel(dw, torch.nn.grad.conv3d_weight(x64, tuple(wt.shape), dyg, padding=pad))
+        err_b = _rel(db, dyg.sum((0, 2, 3, 4)))
+        print(f"wide3d {c_in} pd {pd} {(n, d, h, w)} gates {use_dg}: dw {err_w:.2e} db {err_b:.2e} (bound {NORM_TOL})")
+        assert err_w <= NORM_TOL and err_b <= NORM_TOL
+
+
+# ---- 2. the horizon first layer ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("d_in", [4, 2])
+@pytest.mark.parametrize("n, h, w", HORIZON_SHAPES)
+def test_horizon_layer_against_float64(device, d_in, n, h, w):
+    """Against F.conv3d on the materialised float64 input; the horizons rotate through 0.0, a negative and positive ones, then
+    all are 0: the horizon channel's weight gradient is then exactly 0."""
+    K = _ops()
+    g = _g(100 + w + d_in)
+    hist = _randn(g, n, d_in, h, w)
+    wt, b = _conv_params(g, 64, 2)
+    w64, b64 = wt.double(), b.double()
+    dy = _randn(g, n, 64, d_in - 1, h, w)
+    pool = [0.0, -1.6613, 0.5055, 1.5168]
+    rounds = [[pool[(k + i) % len(pool)] for i in range(n)] for k in range(len(pool))] + [[0.0] * n]
+    for values in rounds:
+        horizon = torch.tensor(values, dtype=torch.float32)
+        x64 = R.input64(hist, horizon)
+        ref = F.conv3d(x64, w64, b64, padding=(0, 1, 1))
+        absref = F.conv3d(x64.abs(), w64.abs(), b64.abs(), padding=(0, 1, 1))
+        y = K.conv3d_wide_horizon_fwd_f32(hist.to(device), horizon.to(device), wt.to(device), b.to(device))
+        assert tuple(y.shape) == (n, 64, d_in - 1, h, w)
+        _within(y, ref.relu(), absref, what=f"horizon forward {values}")
+        dw, db = K.conv3d_wide_horizon_bwd_weight_f32(hist.to(device), horizon.to(device), dy.to(device), tuple(wt.shape))
+        dw2, db2 = K.conv3d_wide_horizon_bwd_weight_f32(hist.to(device), horizon.to(device), dy.to(device), tuple(wt.shape))
+        assert torch.equal(dw, dw2) and torch.equal(db, db2), "the weight gradient's bits differ run to run"
+        dw64 = torch.nn.grad.conv3d_weight(x64, tuple(wt.shape), dy.double(), padding=(0, 1, 1))
+        err_w, err_b = _rel(dw, dw64), _rel(db, dy.double().sum((0, 2, 3, 4)))
+        print(f"horizon d {d_in} {(n, h, w)} {values}: dw {err_w:.2e} db {err_b:.2e} (bound {NORM_TOL})")
+        assert err_w <= NORM_TOL and err_b <= NORM_TOL, values
+        if not any(values):
+            assert (dw[:, 1] == 0).all(), "the horizon channel's gradient is not exactly 0 under all-zero horizons"
+
+
+# ---- 3. the stride-2 padding-1 head ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("c_in", [256, 32])
+@pytest.mark.parametrize("n, h, w", HEAD_SHAPES)
+def test_head_against_float64(device, c_in, n, h, w):
+    K = _ops()
+    g = _g(500 + w + c_in)
+    x = _randn(g, n, c_in, h, w)
+    wt, b = _conv_params(g, 1, c_in, kernel=(3, 3))
+    x64, w64, b64 = x.double(), wt.double(), b.double()
+    pre = F.conv2d(x64, w64, b64, stride=2, padding=1)
+    absref = F.conv2d(x64.abs(), w64.abs(), b64.abs(), stride=2, padding=1)
+    assert tuple(pre.shape) == (n, 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
+    xd, wd, bd = x.to(device), wt.to(device), b.to(device)
+    y = K.conv2d_head_s2p1_fwd_f32(xd, wd, bd)
+    assert tuple(y.shape) == tuple(pre.shape)
+    _within(y, pre, absref, what="head forward")
+    _within(K.conv2d_head_s2p1_fwd_f32(xd, wd, None), pre - b64.view(1, -1, 1, 1), absref, what="head forward without bias")
+    assert torch.equal(y, K.conv2d_head_s2p1_fwd_f32(xd, wd, bd))
+    dy, x_gate = _randn(g, *pre.shape), _randn(g, *x.shape)
+    opad = ((h + 1) % 2, (w + 1) % 2)              # the last row / column of an even side, which the forward never reads
+    dx64 = F.conv_transpose2d(dy.double(), w64, stride=2, padding=1, output_padding=opad)
+    absdx = F.conv_transpose2d(dy.double().abs(), w64.abs(), stride=2, padding=1, output_padding=opad)
+    assert tuple(dx64.shape) == tuple(x.shape)
+    for use_xg in (True, False):
+        dx = K.conv2d_head_s2p1_bwd_data_f32(dy.to(device), None, wd, x_gate.to(device) if use_xg else None, tuple(x.shape))
+        _within(dx, dx64 * (x_gate > 0) if use_xg else dx64, absdx, what=f"head dx gate {use_xg}")
+    dw, db = K.conv2d_head_s2p1_bwd_weight_f32(xd, dy.to(device), None, tuple(wt.shape))
+    dw2, db2 = K.conv2d_head_s2p1_bwd_weight_f32(xd, dy.to(device), None, tuple(wt.shape))
+    assert torch.equal(dw, dw2) and torch.equal(db, db2), "the head's weight gradient differs run to run"
+    assert tuple(dw.shape) == tuple(wt.shape) and tuple(db.shape) == (1,)
+    err_w = _rel(dw, torch.nn.grad.conv2d_weight(x64, tuple(wt.shape), dy.double(), stride=2, padding=1))
+    err_b = _rel(db, dy.double().sum((0, 2, 3)))
+    print(f"head p1 {c_in} {(n, h, w)}: dw {err_w:.2e} db {err_b:.2e} (bound {NORM_TOL})")
+    assert err_w <= NORM_TOL and err_b <= NORM_TOL
+
+
+@pytest.mark.parametrize("n, h, w", [(2, 9, 46), (1, 1, 1), (2, 10, 47)])
+def test_head_depth2_view_against_float64_conv3d(device, n, h, w):
+    """conv.8 on depth 2: the Conv2d head on the views [n][2 c][h][w] / [1][2 c][3][3] against F.conv3d itself."""
+    K = _ops()
+    g = _g(600 + w)
+    x = _randn(g, n, 128, 2, h, w)
+    wt, b = _conv_params(g, 1, 128)
+    x64, w64, b64 = x.double().requires_grad_(True), wt.double().requires_grad_(True), b.double().requires_grad_(True)
+    pre = F.conv3d(x64, w64, b64, stride=(1, 2, 2), padding=(0, 1, 1))
+    absref = F.conv3d(x64.detach().abs(), w64.detach().abs(), b64.detach().abs(), stride=(1, 2, 2), padding=(0, 1, 1))
+    assert tuple(pre.shape) == (n, 1, 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
+    xd, wd, bd = x.to(device), wt.to(device), b.to(device)
+    y = K.conv3d_head_d2_fwd_f32(xd, wd, bd)
+    assert tuple(y.shape) == tuple(pre.shape)
+    _within(y, pre.detach(), absref, what="depth-2 head forward")
+    dy = _randn(g, *pre.shape)
+    pre.backward(dy.double())
+    absdx = torch.autograd.grad(F.conv3d(x64, w64.detach().abs(), None, stride=(1, 2, 2), padding=(0, 1, 1)), x64,
+                                dy.double().abs())[0]
+    dx = K.conv3d_head_d2_bwd_data_f32(dy.to(device), None, wd, None, tuple(x.shape))
+    assert tuple(dx.shape) == tuple(x.shape)
+    _within(dx, x64.grad, absdx, what="depth-2 head dx")
+    dw, db = K.conv3d_head_d2_bwd_weight_f32(xd, dy.to(device), None, tuple(wt.shape))
+    assert tuple(dw.shape) == tuple(wt.shape)
+    assert _rel(dw, w64.grad) <= NORM_TOL and _rel(db, b64.grad) <= NORM_TOL
+
+
+# ---- 4. refusals before any launch -------------------------------------------------------------------------------------
+def test_refusals_raise_before_any_launch(device):
+    import ctypes
+    from predict_pv_yield_amd import _lib
+    from predict_pv_yield_amd.hip_ops import ptr
+    K = _ops()
+    z = lambda *s: torch.zeros(*s, device=device)      # noqa: E731
+    with pytest.raises(ValueError, match="C_in, C_out"):                         # unsupported channel pair
+        K.conv3d_wide_fwd_f32(z(1, 32, 3, 8, 8), z(128, 32, 2, 3, 3), z(128))
+    with pytest.raises(ValueError, match="C_in, C_out"):
+        K.conv3d_wide_bwd_data_f32(z(1, 64, 2, 8, 8), None, z(64, 128, 2, 3, 3), None, (1, 128, 3, 8, 8))
+    with pytest.raises(ValueError, match="padding"):                             # depth padding 2
+        K.conv3d_wide_fwd_f32(z(1, 64, 3, 8, 8), z(128, 64, 2, 3, 3), z(128), padding=(2, 1, 1))
+    with pytest.raises(ValueError, match="padding"):                             # spatial padding other than 1
+        K.conv3d_wide_fwd_f32(z(1, 64, 3, 8, 8), z(128, 64, 2, 3, 3), z(128), padding=(0, 0, 0))
+    with pytest.raises(ValueError, match="128"):                                 # 129 columns
+        K.conv3d_wide_fwd_f32(z(1, 64, 3, 8, 129), z(128, 64, 2, 3, 3), z(128))
+    with pytest.raises(ValueError, match="one slice"):                           # depth 1 without depth padding
+        K.conv3d_wide_fwd_f32(z(1, 64, 1, 8, 8), z(128, 64, 2, 3, 3), z(128))
+    with pytest.raises(ValueError, match="horizon"):
+        K.conv3d_wide_horizon_fwd_f32(z(2, 4, 8, 8), z(3), z(64, 2, 2, 3, 3), z(64))
+    with pytest.raises(ValueError, match="depth 2"):                             # the head's view at depth 3
+        K.conv3d_head_d2_fwd_f32(z(1, 128, 3, 8, 8), z(1, 128, 2, 3, 3), z(1))
+    with pytest.raises(ValueError, match="depth 2"):
+        K.conv3d_head_d2_bwd_weight_f32(z(1, 128, 3, 8, 8), z(1, 1, 1, 4, 4), None, (1, 128, 2, 3, 3))
+    with pytest.raises(RuntimeError, match="status -1"):                         # the head takes no dy_gate
+        K.conv2d_head_s2p1_bwd_data_f32(z(1, 1, 4, 4), z(1, 1, 4, 4), z(1, 32, 3, 3), None, (1, 32, 8, 8))
+    # the ABI itself, from device pointers: the error code, nothing launched
+    lib = _lib.get_lib()
+    x, wt, y = z(1, 64, 3, 8, 8), z(128, 64, 2, 3, 3), torch.full((1, 128, 2, 8, 8), 7.0, device=device)
+    fwd = lib.pv_conv3d_wide_fwd_f32
+    assert fwd(ptr(x), ptr(wt), None, ptr(y), 1, 32, 128, 3, 8, 8, 0, 1, 0, None) == -2      # channel pair
+    assert fwd(ptr(x), ptr(wt), None, ptr(y), 1, 64, 64, 3, 8, 8, 0, 1, 0, None) == -2
+    assert fwd(ptr(x), ptr(wt), None, ptr(y), 1, 64, 128, 3, 8, 8, 2, 1, 0, None) == -2      # depth padding 2
+    assert fwd(ptr(x), ptr(wt), None, ptr(y), 1, 64, 128, 3, 8, 8, 0, 0, 0, None) == -2      # spatial padding 0
+    assert fwd(ptr(x), ptr(wt), None, ptr(y), 1, 64, 128, 3, 8, 8, 0, 2, 0, None) == -2      # spatial padding 2
+    assert fwd(ptr(x), ptr(wt), None, ptr(y), 1, 64, 128, 3, 8, 129, 0, 1, 0, None) == -2    # 129 columns
+    assert fwd(ptr(x), ptr(wt), None, ptr(y), 1, 64, 128, 1, 8, 8, 0, 1, 0, None) == -2      # depth 1, no depth padding
+    assert "depth" in lib.pv_last_error().decode()
+    assert fwd(ptr(x), None, None, ptr(y), 1, 64, 128, 3, 8, 8, 0, 1, 0, None) == -1         # null pointer
+    assert lib.pv_conv3d_wide_bwd_data_f32(ptr(y), None, ptr(wt), ptr(y), None, 1, 64, 128, 3, 8, 8, 2, 1, None) == -2
+    assert lib.pv_conv3d_wide_horizon_fwd_f32(ptr(x), ptr(x), ptr(wt), ptr(wt), ptr(y), 1, 3, 8, 8, 128, None) == -2
+    assert lib.pv_conv3d_wide_horizon_fwd_f32(ptr(x), None, ptr(wt), ptr(wt), ptr(y), 1, 3, 8, 8, 64, None) == -1
+    assert lib.pv_conv2d_head_s2p1_fwd_f32(ptr(x), ptr(wt), None, ptr(y), 1, 64, 2, 8, 8, 0, None) == -2
+    torch.cuda.synchronize()
+    assert (y == 7.0).all(), "a refused call wrote its output"
+    need = ctypes.c_size_t(0)
+    assert lib.pv_conv3d_wide_bwd_weight_workspace_bytes(1, 64, 128, 3, 8, 8, 0, 1, ctypes.byref(need)) == 0 and need.value > 0
+    assert lib.pv_conv3d_wide_bwd_weight_workspace_bytes(1, 64, 128, 3, 8, 8, 2, 1, ctypes.byref(need)) == -2
+    dw, db, ws = z(128, 64, 2, 3, 3), z(128), z(1 << 20)
+    assert lib.pv_conv3d_wide_bwd_weight_workspace_bytes(1, 64, 128, 3, 8, 8, 0, 1, ctypes.byref(need)) == 0
+    assert lib.pv_conv3d_wide_bwd_weight_f32(ptr(x), ptr(y), None, ptr(dw), ptr(db), 1, 64, 128, 3, 8, 8, 0, 1, ptr(ws),
+                                             need.value - 1, None) == -1
+    assert "workspace" in lib.pv_last_error().decode()
+    assert lib.pv_conv2d_head_s2p1_bwd_weight_workspace_bytes(1, 256, 1, 8, 8, ctypes.byref(need)) == 0 and need.value > 0
+    assert lib.pv_conv2d_head_s2p1_bwd_weight_f32(ptr(x), ptr(y), None, ptr(dw), ptr(db), 1, 256, 1, 8, 8, ptr(ws),
+                                                  need.value - 1, None) == -1
+    torch.cuda.synchronize()
+    assert (dw == 0).all() and (db == 0).all(), "a refused call wrote its output"
+
+
+# ---- 5. the model against the golden -----------------------------------------------------------------------------------
+def _load_model(device, init):
+    from predict_pv_yield_amd.models.conv3d.nb12_just_3d_conv import LitAutoEncoder
+    model = LitAutoEncoder()
+    model.load_state_dict(init)
+    return model.to(device)
+
+
+@pytest.mark.parametrize("tag", ["a", "b"])
+def test_model_against_golden(device, tag):
+    gold = np.load(GOLDEN)
+    batch, init = R.G.draw_batch(tag), R.G.draw_parameters()
+    model = _load_model(device, init)
+    dbatch = _to(batch, device)
+    y_hat = model(dbatch)
+    assert tuple(y_hat.shape) == tuple(gold[f"{tag}/y_hat"].shape)
+    R.check_stored(gold, f"{tag}/y_hat", y_hat, NORM_TOL)
+    opt = model.configure_optimizers()
+    losses = []
+    for step in range(3):
+        opt.zero_grad(set_to_none=True)
+        loss = model.training_step(dbatch, 0)
+        loss.backward()
+        if step == 0:
+            for k, p in model.named_parameters():       # every figure first, then the assertions
+                err = R.check_stored(gold, f"{tag}/grad/{k}", p.grad, NORM_TOL, entries_only=True)
+                print(f"{tag} grad {k}: rel {err:.3e} (bound {NORM_TOL})")
+            for k, p in model.named_parameters():
+                R.check_stored(gold, f"{tag}/grad/{k}", p.grad, NORM_TOL)
+        opt.step()
+        losses.append(loss.item())
+    for got, want in zip(losses, gold[f"{tag}/losses"]):
+        assert abs(got - want) <= 1e-5 * want, (losses, gold[f"{tag}/losses"])
+    for k, p in model.named_parameters():
+        got, _ = R.stored(f"{tag}/step3/{k}", p)
+        first, _ = R.stored(f"{tag}/step3/{k}", init[k])
+        want = torch.from_numpy(gold[f"{tag}/step3/{k}"]).double().reshape(got.shape)
+        err = (got - want).abs()
+        moved = (want - first).abs()
+        q99 = err.flatten().sort().values[int(0.99 * (err.numel() - 1))].item()
+        print(f"{tag} step3 {k}: max {err.max().item():.3e} 99% {q99:.3e} moved median {moved.median().item():.3e}")
+        assert moved.median().item() >= 1e-5, k       # the fixture's parameters did move (three steps of lr = 1e-4)
+        assert q99 <= 1e-6, (k, q99)
+        assert err.max().item() <= 3 * 2e-4 + 1e-6, k
+
+
+# ---- 6. full size, determinism and HIP-graph replay --------------------------------------------------------------------
+def _full_batch(seed, b=2, s=128):
+    g = _g(seed)
+    steps = torch.randint(1, 25, (b,), generator=g)
+    return {"HISTORICAL_SAT_IMAGES": _randn(g, b, 4, s, s),
+            "FORECAST_HORIZON": torch.tensor([float(R.G.normalise_forecast_horizon(int(t))) for t in steps]),
+            "TARGET_SAT_IMAGE": _randn(g, b, (s - 1) // 2 + 1, (s - 1) // 2 + 1)}
+
+
+def test_full_size_forward_and_loss(device):
+    """The notebook's size (S = 128 -> [B, 1, 1, 64, 64]) against float64."""
+    from predict_pv_yield_amd.models.conv3d.nb12_just_3d_conv import LitAutoEncoder
+    torch.manual_seed(5)
+    model = LitAutoEncoder().to(device)
+    batch = _full_batch(50)
+    y_hat = model(_to(batch, device))
+    assert tuple(y_hat.shape) == (2, 1, 1, 64, 64)
+    loss = model.training_step(_to(batch, device), 0)
+    y64 = R.forward64(R.params64(model.state_dict(), requires_grad=False), batch)
+    assert _rel(y_hat.detach(), y64) <= NORM_TOL
+    ref = R.loss64(y64, batch["TARGET_SAT_IMAGE"]).item()
+    assert abs(loss.item() - ref) <= 1e-5 * ref, (loss.item(), ref)
+
+
+def test_train_step_replays_as_a_hip_graph(device):
+    """Three steps through GraphedTrainStep: losses and parameters bit-identical to three eager steps from the same state."""
+    from predict_pv_yield_amd.graphs import GraphedTrainStep
+    from predict_pv_yield_amd.models.conv3d.nb12_just_3d_conv import LitAutoEncoder
+    from predict_pv_yield_amd.optim import HipAdam
+    batches = [_to(_full_batch(70 + s), device) for s in range(3)]
+
+    def make(capturable):
+        torch.manual_seed(11)
+        model = LitAutoEncoder().to(device)
+        return model, HipAdam(model.parameters(), lr=0.0001, capturable=capturable)
+
+    model_e, opt_e = make(False)
+    model_g, opt_g = make(True)
+    step = GraphedTrainStep(model_g, opt_g, batches[0], warmup=2)
+    try:
+        for _ in range(2):                      # the warm-up steps are training steps: the eager model takes them too
+            opt_e.zero_grad(set_to_none=True)
+            model_e.training_step(batches[0], 0).backward()
+            opt_e.step()
+        for p, q in zip(model_g.parameters(), model_e.parameters()):
+            assert torch.equal(p, q)
+        for i in range(3):
+            opt_e.zero_grad(set_to_none=True)
+            loss = model_e.training_step(batches[i], 0)
+            loss.backward()
+            opt_e.step()
+            assert float(step(batches[i])) == float(loss), f"step {i}"
+        for p, q in zip(model_g.parameters(), model_e.parameters()):
+            assert torch.equal(p, q)
+    finally:
+        step.close()
+
+
+def test_trainer_fit_on_the_fake_datamodule(device):
+    """`run.py model=nb12_just_3d_conv datamodule=nb12_fake` in small: an epoch, eagerly and graph-replayed, same parameters."""
+    from predict_pv_yield_amd import lightning as pl
+    from predict_pv_yield_amd.data.nb12_datamodule import Nb12DataModule
+    from predict_pv_yield_amd.models.conv3d.nb12_just_3d_conv import LitAutoEncoder
+    dm = Nb12DataModule(batch_size=2, n_train_data=pl.Trainer.GRAPH_EAGER_STEPS + 2, n_val_data=1, n_super_batches=1,
+                        n_timesteps=12)
+    results = []
+    for graph in (False, True):
+        torch.manual_seed(2)
+        model = LitAutoEncoder()
+        trainer = pl.Trainer(gpus=1, max_epochs=1, hip_graph=graph, log_every_n_steps=1)
+        trainer.fit(model, datamodule=dm)
+        results.append(({k: v.detach().clone() for k, v in model.state_dict().items()}, dict(trainer.callback_metrics)))
+    (sd_e, log_e), (sd_g, log_g) = results
+    for k in sd_e:
+        assert torch.equal(sd_e[k], sd_g[k]), k
+    assert np.isfinite(float(log_g["Loss/Train_epoch"])) and float(log_g["Loss/Train_epoch"]) == float(log_e["Loss/Train_epoch"])
