@@ -4,7 +4,9 @@
 // ConvTranspose2d layout), the MaxPool2d(3) + ReLU window rule and its backward, the descriptor of what a pass reads (In) with
 // its plain and pooled-gradient loads, the five synthesised input channels of the two experiments and the argument checks
 // they all repeat.  The 144-channel main loops (weights in LDS, K streamed in chunks) stay in their file; the files whose
-// weights fit the VGPRs share theirs in conv2d_tile_f32.h.
+// weights fit the VGPRs share theirs in conv2d_tile_f32.h.  The 64 / 128-channel families (conv2d_wide_f32.hip,
+// conv2d_wide_s2_f32.hip, conv3d_wide_f32.hip) and their one-output-channel heads (conv2d_head_f32.hip) use the slab sum, In
+// and the checks of this header too; their tiles are in conv_wide_f32.h.
 #pragma once
 #include "pv_common.h"
 

@@ -1,7 +1,7 @@
 // Conv2d 3x3 on wide channel counts in exact f32 (v_mfma_f32_16x16x4_f32: one rounding per product, f32 accumulation) for
 // the frame predictor of notebooks/10_just_conv.ipynb (the nn.Sequential of LitAutoEncoder, raw lines 1386-1392 of the
 // .ipynb file: Conv2d 5 -> 64 -> 128 -> 128 (padding 2) -> 1 (stride 2, padding 2); forward with the stripe channel at
-// 1395-1410).  Three groups of entry points:
+// 1395-1410).  Two groups of entry points (the model's last layer, pv_conv2d_head_s2_*, is in conv2d_head_f32.hip):
 //   pv_conv2d_wide_*         stride 1, padding 0 or 2, (c_in, c_out) = (64, 128) or (128, 128); the weights (up to 590 KB)
 //                            do not fit the VGPRs, so all passes are implicit GEMMs over LDS tiles with K streamed in
 //                            channel chunks, as in conv2d_pool_f32.hip:
@@ -13,45 +13,23 @@
 //   pv_conv2d_wide_stripe_*  the first layer, (n_hist + 1) -> 64, padding 0, ReLU: the forecast-horizon stripe channel (1 on
 //                            columns [start, start + width), 0 elsewhere) is synthesised while staging, in the forward and
 //                            in the weight gradient, and never stored.
-//   pv_conv2d_head_s2_*      3x3, stride 2, padding 2, one output channel, any c_in: bandwidth-bound, so plain vector code
-//                            (one output channel would use 1/16 of a matrix tile).
-// LDS images are laid out against bank conflicts of the 32-lane read groups: the weight rows [tap][c] are 80 floats apart
-// and the input channel stride is 16 mod 32, so the two k-rows a half wave reads fall on disjoint banks; the staged dy rows
-// of the weight gradient are 98 floats apart (2 mod 32).  Staging walks whole rows per wave (lanes along columns): no
-// per-element division.  The slab sum, the input descriptor and the workspace check are shared (conv2d_f32_common.h), the
-// stripe source with the stride-2 file (conv2d_stripe_f32.h).
+// The tiles of both passes, their LDS layouts, the band staging (whole rows per wave, lanes along columns: no per-element
+// division) and the tile planners are those of conv_wide_f32.h, shared with conv2d_wide_s2_f32.hip and conv3d_wide_f32.hip;
+// this file holds the two kernels' block and item decode, the 2-D source, the extents checks and the entry points.  The slab
+// sum, the input descriptor and the workspace check are shared (conv2d_f32_common.h), the stripe source with the stride-2
+// file (conv2d_stripe_f32.h).
 #include "conv2d_stripe_f32.h"
+#include "conv_wide_f32.h"
 
 namespace pv {
 namespace {
 
-// forward / dgrad: 4 x 16 output channels per block, 4 x 16 positions per wave (256 per block), 8 input channels per chunk
-constexpr int kMT = 4, kMB = kMT * 16, kMBP = kMB + 16, kNTW = 4, kCC = 8, kPos = 4 * kNTW * 16;
-constexpr int kMaxTc = 62, kMaxTr = 64;      // the staged band is at most 64 columns (one lane each) x 66 rows
-// wgrad: 14 input channels per chunk -> 126 (ci, tap) columns + a ones column + a zero column = 8 tiles, 2 per wave
-constexpr int kWgCC = 14, kWgNTW = 2, kWgPos = 96, kWgDps = kWgPos + 2, kWgMaxTc = 48, kWgMaxTr = 32;
-constexpr int kMaxWgBlocks = 512;
-constexpr int kMaxW = 128;                   // widest input plane of the wide family
-
-// Stage channels [c0, c0 + cc) x rows [r0, r0 + rows) x columns [col0, col0 + cols) of image n as lds[c * cs + r * sw +
-// col]; outside the image (padding) and beyond c_in: 0.  One row per wave and pass, one column per lane: cols <= 64.
+// the band of stage_rows (conv_wide_f32.h) from image n of a 2-D source
 template <int SRC>
-__device__ __forceinline__ void stage_rows(float* lds, const In& s, const Stripe& sp, int n, int c0, int cc, int r0,
-                                           int rows, int col0, int cols, int sw, int cs) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int ic = col0 + lane;
-  const bool col_ok = ic >= 0 && ic < s.w;
-  if (lane >= cols) return;
-  int ch = 0, r = wave;
-  while (r >= rows) r -= rows, ++ch;
-  while (ch < cc) {
-    const int gc = c0 + ch, ir = r0 + r;
-    float v = 0.0f;
-    if (col_ok && gc < s.c_in && ir >= 0 && ir < s.h) v = load_in<SRC>(s, sp, n, gc, ir, ic);
-    lds[ch * cs + r * sw + lane] = v;
-    r += 4;
-    while (r >= rows) r -= rows, ++ch;
-  }
+__device__ __forceinline__ void stage_rows2(float* lds, const In& s, const Stripe& sp, int n, int c0, int cc, int r0,
+                                            int rows, int col0, int cols, int sw, int cs) {
+  stage_rows(lds, [&](int ch, int r, int c) { return load_in<SRC>(s, sp, n, ch, r, c); }, true, s.c_in, s.h, s.w, c0, cc, r0,
+             rows, col0, cols, sw, cs);
 }
 
 struct Fwd {
@@ -64,107 +42,35 @@ struct Fwd {
   int m_out, pad, h_out, w_out, tr, tc, n_rb, n_cb, n_mg, w_sm, w_sc, flip, relu;
 };
 
-// channel stride of the staged band: >= rows * sw and 16 mod 32
-__host__ __device__ inline int band_stride(int rows, int sw) {
-  const int cs = rows * sw;
-  return cs + ((16 - cs % 32) + 32) % 32;
-}
-
-// Forward / dgrad.  Block = (image, row band, column band, group of 64 output channels); the band is tr x tc output positions
-// (<= 256) flattened row-major, wave w takes the 16-position tiles 4 w .. 4 w + 3.  Per chunk of 8 input channels the
-// weights [tap][c][m] and the input band [c][tr + 2][tc + 2] are staged, then 18 k-steps each read 4 A and 4 B values and
-// issue 16 MFMAs.
+// Forward / dgrad.  Block = (image, row band, column band, group of 64 output channels); the tile and its steps are those
+// of conv_wide_f32.h, once per chunk of 8 input channels.
 template <int SRC>
 __global__ __launch_bounds__(kBlock) void wide_fwd(Fwd a) {
-  constexpr int MT = kMT, NTW = kNTW, CC = kCC, KS = CC / 4, MB = kMB, MBP = kMBP;
   extern __shared__ float lds[];
-  float* wl = lds;                     // [9][CC][MBP]
-  float* xl = lds + 9 * CC * MBP;      // [CC][csp]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* wl = lds;                       // [9][kCC][kMBP]
+  float* xl = lds + 9 * kCC * kMBP;      // [kCC][csp]
   int bid = blockIdx.x;
   const int mg = bid % a.n_mg; bid /= a.n_mg;
   const int cb = bid % a.n_cb; bid /= a.n_cb;
   const int rb = bid % a.n_rb;
   const int n = bid / a.n_rb;
-  const int m0 = mg * MB, r0 = rb * a.tr, c0 = cb * a.tc;
-  const int rows = min(a.tr, a.h_out - r0), cols = min(a.tc, a.w_out - c0);
-  const int sw = cols + 2, csp = band_stride(a.tr + 2, a.tc + 2), npos = rows * cols;
+  int xoff[kNTW];
+  acc4 acc[kMT][kNTW];
+  const FwdBand t = fwd_band(a, rb, cb, mg, xoff, acc);
 
-  int xoff[NTW];
-#pragma unroll
-  for (int j = 0; j < NTW; ++j) {
-    const int p = (wave * NTW + j) * 16 + (lane & 15);
-    const int pp = p < npos ? p : 0;
-    const int oh = pp / cols, ow = pp - oh * cols;
-    xoff[j] = (lane >> 4) * csp + oh * sw + ow;
-  }
-  acc4 acc[MT][NTW];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int j = 0; j < NTW; ++j) acc[mt][j] = (acc4){0.0f, 0.0f, 0.0f, 0.0f};
-  const bool busy = wave * NTW * 16 < npos;
-
-  for (int k0 = 0; k0 < a.in.c_in; k0 += CC) {
+  for (int k0 = 0; k0 < a.in.c_in; k0 += kCC) {
     __syncthreads();   // the previous chunk's reads are done
-    // weights: walk the global array along its contiguous axis, (c, tap) per m forward, (m, tap) per c mirrored
-    for (int i = threadIdx.x; i < 9 * CC * MB; i += kBlock) {
-      int ml, c, tap;
-      if (a.flip) c = i / (MB * 9), ml = (i % (MB * 9)) / 9, tap = i % 9;
-      else ml = i / (CC * 9), c = (i % (CC * 9)) / 9, tap = i % 9;
-      const int m = m0 + ml, gc = k0 + c;
-      const float v = (m < a.m_out && gc < a.in.c_in) ? a.w[(size_t)m * a.w_sm + (size_t)gc * a.w_sc + tap] : 0.0f;
-      wl[((a.flip ? 8 - tap : tap) * CC + c) * MBP + ml] = v;
-    }
-    stage_rows<SRC>(xl, a.in, a.sp, n, k0, CC, r0 - a.pad, rows + 2, c0 - a.pad, sw, sw, csp);
+    fwd_stage_weights(wl, a, a.in.c_in, t.m0, k0, 0);
+    stage_rows2<SRC>(xl, a.in, a.sp, n, k0, kCC, t.r0 - a.pad, t.rows + 2, t.c0 - a.pad, t.sw, t.sw, t.csp);
     __syncthreads();
-    if (busy) {
-#pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const int toff = (tap / 3) * sw + (tap % 3);
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-          float av[MT], bv[NTW];
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt) av[mt] = wl[(tap * CC + s * 4 + (lane >> 4)) * MBP + mt * 16 + (lane & 15)];
-#pragma unroll
-          for (int j = 0; j < NTW; ++j) bv[j] = xl[xoff[j] + s * 4 * csp + toff];
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int j = 0; j < NTW; ++j) acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], bv[j], acc[mt][j], 0, 0, 0);
-        }
-      }
-    }
+    fwd_multiply(wl, xl, t, xoff, acc);
   }
-
-  if (!busy) return;
-#pragma unroll
-  for (int j = 0; j < NTW; ++j) {
-    const int p = (wave * NTW + j) * 16 + (lane & 15);
-    if (p >= npos) continue;
-    const int oh = p / cols, ow = p - oh * cols;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int m = m0 + mt * 16 + (lane >> 4) * 4 + i;
-        if (m < a.m_out) {
-          const size_t off = (((size_t)n * a.m_out + m) * a.h_out + r0 + oh) * a.w_out + c0 + ow;
-          float v = acc[mt][j][i] + (a.bias ? a.bias[m] : 0.0f);
-          if (a.relu) v = v > 0.0f ? v : 0.0f;
-          if (a.out_gate && !(a.out_gate[off] > 0.0f)) v = 0.0f;
-          a.y[off] = v;
-        }
-      }
-  }
+  fwd_store(a, t, n, 1, 0, acc);
 }
 
-// wgrad.  Block = (slab, chunk of 14 input channels); D[co][col] over every position of the slab's tiles, col = ci * 9 + tap
-// (local to the chunk) for col < 126, col 126 a column of ones (dbias, written by chunk 0), col 127 zero.  Wave w owns the
-// 16-column tiles 2 w, 2 w + 1 against all MT output-channel tiles; a k-step is 4 positions (A: dy, 16 channels x 4
-// positions; B: 4 positions x 16 columns).  The tile's dy lives in LDS as [c_out][98] (zero beyond the tile), x as
-// [14][tr + 2][tc + 2], plus xo[pos] = the position's offset in the x tile.
+// wgrad.  Block = (slab, chunk of 14 input channels) over the slab's items (image, row band, column band); the tile is that
+// of conv_wide_f32.h at position stride 1: the tile's dy lives in LDS as [c_out][98] (zero beyond the tile), x as
+// [14][tr + 2][tc + 2].  The ones column (dbias) is written by chunk 0.
 struct Wg {
   In in;                    // layer input (SRC_PLAIN or SRC_STRIPE)
   Stripe sp;
@@ -175,9 +81,8 @@ struct Wg {
 
 template <int SRC, int MT>
 __global__ __launch_bounds__(kBlock) void wide_wgrad(Wg q) {
-  constexpr int NTW = kWgNTW, CC = kWgCC, DPS = kWgDps, M = MT * 16;
+  constexpr int CC = kWgCC, DPS = kWg1Dps, M = MT * 16;
   extern __shared__ float lds[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int slab = blockIdx.x, chunk = blockIdx.y, ci0 = chunk * CC;
   const int sw = q.tc + 2, cs = (q.tr + 2) * sw;
   float* xl = lds;                     // [CC][cs]
@@ -185,22 +90,11 @@ __global__ __launch_bounds__(kBlock) void wide_wgrad(Wg q) {
   int* xo = (int*)(dl + M * DPS);      // [DPS]
   const Stripe none = {};
 
-  int coff[NTW];
-  float bmul[NTW], badd[NTW];
-#pragma unroll
-  for (int j = 0; j < NTW; ++j) {
-    const int col = (wave * NTW + j) * 16 + (lane & 15);
-    const bool real = col < CC * 9 && ci0 + col / 9 < q.in.c_in;
-    const int ci = real ? col / 9 : 0, tap = real ? col % 9 : 0;
-    coff[j] = ci * cs + (tap / 3) * sw + tap % 3;
-    bmul[j] = real ? 1.0f : 0.0f;
-    badd[j] = col == CC * 9 ? 1.0f : 0.0f;
-  }
-  acc4 acc[MT][NTW];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int j = 0; j < NTW; ++j) acc[mt][j] = (acc4){0.0f, 0.0f, 0.0f, 0.0f};
+  int coff[kWgNTW];
+  float bmul[kWgNTW], badd[kWgNTW];
+  wg_columns(ci0, q.in.c_in, cs, sw, coff, bmul, badd);
+  acc4 acc[MT][kWgNTW];
+  zero_acc(acc);
 
   const int it0 = slab * q.per, it1 = min(it0 + q.per, q.items);
   for (int it = it0; it < it1; ++it) {
@@ -208,200 +102,29 @@ __global__ __launch_bounds__(kBlock) void wide_wgrad(Wg q) {
     const int r0 = rb * q.tr, c0 = cb * q.tc;
     const int rows = min(q.tr, q.h_out - r0), cols = min(q.tc, q.w_out - c0), npos = rows * cols;
     __syncthreads();   // the previous item's reads are done
-    stage_rows<SRC>(xl, q.in, q.sp, n, ci0, CC, r0 - q.pad, q.tr + 2, c0 - q.pad, sw, sw, cs);
-    // dy rows [co][oh] of the tile, packed to cols per row; the (up to 3) positions that round the tile to a k-step: 0
-    stage_rows<SRC_PLAIN>(dl, q.dy, none, n, 0, M, r0, rows, c0, cols, cols, DPS);
-    for (int i = threadIdx.x; i < M * 4; i += kBlock) {
-      const int p = npos + (i & 3);
-      if (p < DPS) dl[(i >> 2) * DPS + p] = 0.0f;
-    }
-    for (int p = threadIdx.x; p < DPS; p += kBlock) {
-      const int oh = p / cols, ow = p - oh * cols;
-      xo[p] = p < npos ? oh * sw + ow : 0;
-    }
+    stage_rows2<SRC>(xl, q.in, q.sp, n, ci0, CC, r0 - q.pad, q.tr + 2, c0 - q.pad, sw, sw, cs);
+    // dy rows [co][oh] of the tile, packed to cols per row
+    stage_rows2<SRC_PLAIN>(dl, q.dy, none, n, 0, M, r0, rows, c0, cols, cols, DPS);
+    wg_item_tail<MT, 1, DPS>(dl, xo, npos, cols, sw);
     __syncthreads();
-    const int steps = (npos + 3) / 4;
-    for (int s = 0; s < steps; ++s) {
-      const int p = s * 4 + (lane >> 4);
-      const int xoff = xo[p];
-      float av[MT];
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) av[mt] = dl[(mt * 16 + (lane & 15)) * DPS + p];
-#pragma unroll
-      for (int j = 0; j < NTW; ++j) {
-        const float b = xl[coff[j] + xoff] * bmul[j] + badd[j];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], b, acc[mt][j], 0, 0, 0);
-      }
-    }
+    wg_ksteps<MT, DPS>(xl, dl, xo, npos, coff, bmul, badd, 1.0f, acc);
   }
-  // this slab's partial sums of the chunk's columns: row co = mt * 16 + (lane / 16) * 4 + i
   const int ncols = q.in.c_in * 9 + 1;
-  float* out = q.slabs + (size_t)slab * M * ncols;
-#pragma unroll
-  for (int j = 0; j < NTW; ++j) {
-    const int col = (wave * NTW + j) * 16 + (lane & 15);
-    int gcol = -1;
-    if (col < CC * 9 && ci0 + col / 9 < q.in.c_in) gcol = ci0 * 9 + col;
-    else if (col == CC * 9 && chunk == 0) gcol = ncols - 1;
-    if (gcol < 0) continue;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) out[(size_t)(mt * 16 + (lane >> 4) * 4 + i) * ncols + gcol] = acc[mt][j][i];
-  }
-}
-
-// ---- the stride-2 head: 3x3, stride 2, padding 2, one output channel -------------------------------------------------------
-// x [n][c_in][h][w] -> y [n][1][ho][wo], ho = (h + 1) / 2 + 1; output (oh, ow) reads rows 2 oh - 2 + kh, columns 2 ow - 2 + kw.
-
-// forward: one output per thread; the 9 taps of a channel are one fma chain, the channels go round-robin into four partial
-// sums added in a fixed order
-__global__ __launch_bounds__(kBlock) void head_fwd(const float* __restrict__ x, const float* __restrict__ w,
-                                                   const float* __restrict__ bias, float* __restrict__ y, int total,
-                                                   int c_in, int h, int wi, int ho, int wo, int relu) {
-  const int idx = blockIdx.x * kBlock + threadIdx.x;
-  if (idx >= total) return;
-  const int ow = idx % wo, oh = (idx / wo) % ho, b = idx / (wo * ho);
-  int off[9];
-  bool ok[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const int ir = 2 * oh - 2 + t / 3, ic = 2 * ow - 2 + t % 3;
-    ok[t] = ir >= 0 && ir < h && ic >= 0 && ic < wi;
-    off[t] = ok[t] ? ir * wi + ic : 0;
-  }
-  const size_t plane = (size_t)h * wi;
-  const float* xb = x + (size_t)b * c_in * plane;
-  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  for (int ci = 0; ci < c_in; ++ci) {
-    const float* xp = xb + ci * plane;
-    const float* wp = w + ci * 9;
-    float s = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) s = fmaf(wp[t], ok[t] ? xp[off[t]] : 0.0f, s);
-    acc[ci & 3] += s;
-  }
-  float v = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + (bias ? bias[0] : 0.0f);
-  if (relu) v = v > 0.0f ? v : 0.0f;
-  y[idx] = v;
-}
-
-// data gradient: every dx element is written once, from the at most four taps of its parity class.  Block = (1024 elements
-// of a plane, input channel, image): the channel's nine weights are uniform over the block, one division per element
-constexpr int kHeadDxPerBlock = 4 * kBlock;
-__global__ __launch_bounds__(kBlock) void head_bwd_data(const float* __restrict__ dy, const float* __restrict__ w,
-                                                        float* __restrict__ dx, const float* __restrict__ x_gate,
-                                                        int c_in, int h, int wi, int ho, int wo) {
-  const int ci = blockIdx.y, b = blockIdx.z, plane = h * wi;
-  const float* dyb = dy + (size_t)b * ho * wo;
-  const float* wp = w + ci * 9;
-  const size_t base = ((size_t)b * c_in + ci) * plane;
-  const int p1 = min(plane, (int)(blockIdx.x + 1) * kHeadDxPerBlock);
-  for (int p = blockIdx.x * kHeadDxPerBlock + threadIdx.x; p < p1; p += kBlock) {
-    const int r = p / wi, c = p - r * wi;
-    float s = 0.0f;
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh) {
-      const int tr = r + 2 - kh;
-      if ((tr & 1) || (tr >> 1) >= ho) continue;
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const int tc = c + 2 - kw;
-        if ((tc & 1) || (tc >> 1) >= wo) continue;
-        s = fmaf(wp[kh * 3 + kw], dyb[(tr >> 1) * wo + (tc >> 1)], s);
-      }
-    }
-    if (x_gate && !(x_gate[base + p] > 0.0f)) s = 0.0f;
-    dx[base + p] = s;
-  }
-}
-
-// weight / bias gradient.  Block = (input channel, slab of (image, band of 16 output rows) items); every thread sums its
-// positions' nine products (and dy itself), then the block adds the threads' sums in a fixed tree.  slabs [n_slabs][c_in *
-// 9 + 1], the last column the bias gradient (written by channel 0).
-constexpr int kHeadBand = 16, kHeadMaxSlabs = 128;
-
-__global__ __launch_bounds__(kBlock) void head_wgrad(const float* __restrict__ x, const float* __restrict__ dy,
-                                                     float* __restrict__ slabs, int c_in, int h, int wi, int ho, int wo,
-                                                     int n_rb, int items, int per) {
-  __shared__ float part[kBlock / 64][10];
-  const int ci = blockIdx.x, slab = blockIdx.y;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float a[10];
-#pragma unroll
-  for (int t = 0; t < 10; ++t) a[t] = 0.0f;
-  const int it0 = slab * per, it1 = min(it0 + per, items);
-  for (int it = it0; it < it1; ++it) {
-    const int rb = it % n_rb, b = it / n_rb;
-    const int oh0 = rb * kHeadBand, rows = min(kHeadBand, ho - oh0);
-    const float* xp = x + ((size_t)b * c_in + ci) * h * wi;
-    const float* dyb = dy + (size_t)b * ho * wo;
-    for (int p = threadIdx.x; p < rows * wo; p += kBlock) {
-      const int oh = oh0 + p / wo, ow = p % wo;
-      const float g = dyb[oh * wo + ow];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        const int ir = 2 * oh - 2 + t / 3, ic = 2 * ow - 2 + t % 3;
-        const float v = (ir >= 0 && ir < h && ic >= 0 && ic < wi) ? xp[ir * wi + ic] : 0.0f;
-        a[t] = fmaf(g, v, a[t]);
-      }
-      a[9] += g;
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 10; ++t) {
-    float v = a[t];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-    if (lane == 0) part[wave][t] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 10) {
-    const int t = threadIdx.x;
-    const float v = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
-    const int ncols = c_in * 9 + 1;
-    if (t < 9) slabs[(size_t)slab * ncols + ci * 9 + t] = v;
-    else if (ci == 0) slabs[(size_t)slab * ncols + ncols - 1] = v;
-  }
+  wg_store<MT>(q.slabs + (size_t)slab * M * ncols, ncols, ci0, q.in.c_in, chunk == 0, nullptr,
+               [&](int col) { return ci0 * 9 + col; }, acc);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
-size_t fwd_lds_bytes(int tr, int tc) {
-  return ((size_t)9 * kCC * kMBP + (size_t)kCC * band_stride(tr + 2, tc + 2)) * sizeof(float);
-}
-
-// forward tile: up to 62 columns x (256 / columns, at most 64) rows, bands of equal size
-void fwd_tiles(Fwd& a) {
-  a.n_cb = (a.w_out + kMaxTc - 1) / kMaxTc;
-  a.tc = (a.w_out + a.n_cb - 1) / a.n_cb;
-  a.tr = std::max(1, std::min(std::min(a.h_out, kMaxTr), kPos / a.tc));
-  a.n_rb = (a.h_out + a.tr - 1) / a.tr;
-  a.tr = (a.h_out + a.n_rb - 1) / a.n_rb;
-  a.n_mg = (a.m_out + kMB - 1) / kMB;
-}
-
-struct WgPlan {
-  int h_out, w_out, tr, tc, n_rb, n_cb, items, n_chunks, n_slabs, per;
+struct WgPlan : WgTiles {
   size_t lds, ws;
 };
 
+// fixed slabs: at most kWg1MaxBlocks blocks over (slab, chunk); 128 -> 128 at 64 x 126 x 126: 51 slabs x 590 KB = 30 MB
 WgPlan wg_plan(int n, int c_in, int c_out, int h_out, int w_out) {
   WgPlan p;
-  p.h_out = h_out, p.w_out = w_out;
-  p.n_cb = (w_out + kWgMaxTc - 1) / kWgMaxTc;
-  p.tc = (w_out + p.n_cb - 1) / p.n_cb;
-  p.tr = std::max(1, std::min(std::min(h_out, kWgMaxTr), kWgPos / p.tc));
-  p.n_rb = (h_out + p.tr - 1) / p.tr;
-  p.tr = (h_out + p.n_rb - 1) / p.n_rb;
-  p.items = n * p.n_rb * p.n_cb;
-  p.n_chunks = (c_in + kWgCC - 1) / kWgCC;
-  // fixed slabs: at most kMaxWgBlocks blocks over (slab, chunk); 128 -> 128 at 64 x 126 x 126: 51 slabs x 590 KB = 30 MB
-  const int want = std::max(1, std::min(p.items, kMaxWgBlocks / p.n_chunks));
-  p.per = (p.items + want - 1) / want;
-  p.n_slabs = (p.items + p.per - 1) / p.per;
-  p.lds = ((size_t)kWgCC * (p.tr + 2) * (p.tc + 2) + (size_t)c_out * kWgDps) * sizeof(float) + kWgDps * sizeof(int);
+  (WgTiles&)p = wg_tiles(n, c_in, h_out, w_out, kWg1MaxTc, kWg1MaxTr, kWg1Pos, kWg1MaxBlocks, 1);
+  p.lds = ((size_t)kWgCC * (p.tr + 2) * (p.tc + 2) + (size_t)c_out * kWg1Dps) * sizeof(float) + kWg1Dps * sizeof(int);
   p.ws = (size_t)p.n_slabs * c_out * (c_in * 9 + 1) * sizeof(float);
   return p;
 }
@@ -422,25 +145,22 @@ int check_wide_dims(const char* who, int n, int c_in, int c_out, int h_in, int w
 int check_wide(const char* who, int n, int c_in, int c_out, int h_in, int w_in, int pad) {
   int rc = check_wide_dims(who, n, c_in, c_out, h_in, w_in, pad);
   if (rc) return rc;
-  PV_REQUIRE((c_in == 64 || c_in == 128) && c_out == 128, PV_ESIZE,
-             "%s: unsupported channel counts c_in=%d c_out=%d ((64 | 128) -> 128)", who, c_in, c_out);
-  return PV_OK;
+  return check_wide_channels(who, c_in, c_out);
 }
 
 int check_stripe(const char* who, int n, int n_hist, int h, int w, int c_out, int stripe_width) {
-  PV_REQUIRE(n_hist >= 1 && n_hist <= kMaxHist, PV_ESIZE, "%s: unsupported channel count: %d history frames (1..%d)", who,
-             n_hist, kMaxHist);
-  PV_REQUIRE(c_out == 64, PV_ESIZE, "%s: unsupported channel count c_out=%d (64)", who, c_out);
-  PV_REQUIRE(stripe_width >= 0, PV_EINVAL, "%s: negative stripe width", who);
+  int rc = check_stripe_args(who, n_hist, c_out, stripe_width);
+  if (rc) return rc;
   return check_wide_dims(who, n, n_hist + 1, c_out, h, w, 0);
 }
 
 template <int SRC>
 int run_fwd(const char* who, Fwd a, int n, hipStream_t st) {
-  fwd_tiles(a);
+  const FwdTiles t = fwd_tiles(a.m_out, a.h_out, a.w_out);
+  a.tr = t.tr, a.tc = t.tc, a.n_rb = t.n_rb, a.n_cb = t.n_cb, a.n_mg = t.n_mg;
   const long long blocks = (long long)n * a.n_rb * a.n_cb * a.n_mg;
   PV_REQUIRE(blocks < (1LL << 31), PV_ESIZE, "%s: grid beyond 2^31 blocks", who);
-  wide_fwd<SRC><<<dim3((unsigned)blocks), dim3(kBlock), fwd_lds_bytes(a.tr, a.tc), st>>>(a);
+  wide_fwd<SRC><<<dim3((unsigned)blocks), dim3(kBlock), wide_fwd_lds_bytes(a.tr, a.tc), st>>>(a);
   return check_launch(who);
 }
 
@@ -460,34 +180,6 @@ int run_wgrad(const char* who, const In& in, const Stripe& sp, const In& dy, int
   if (rc) return rc;
   launch_slab_sum(ws, dw, db, dy.c_in, in.c_in * 9, p.n_slabs, st);
   return check_launch(who);
-}
-
-// the head: ho x wo outputs, every tensor within 32-bit indexing
-int check_head(const char* who, int n, int c_in, int c_out, int h_in, int w_in) {
-  PV_REQUIRE(n > 0 && c_in > 0 && h_in > 0 && w_in > 0, PV_EINVAL, "%s: non-positive dimension", who);
-  PV_REQUIRE(c_out == 1, PV_ESIZE, "%s: unsupported channel count c_out=%d (1)", who, c_out);
-  PV_REQUIRE((long long)n * c_in * h_in * w_in < (1LL << 31), PV_ESIZE, "%s: tensor beyond 2^31 elements (32-bit indexing)",
-             who);
-  return PV_OK;
-}
-
-inline int head_out(int side) { return (side + 1) / 2 + 1; }
-
-struct HeadPlan {
-  int ho, wo, n_rb, items, per, n_slabs;
-  size_t ws;
-};
-
-HeadPlan head_plan(int n, int c_in, int h, int w) {
-  HeadPlan p;
-  p.ho = head_out(h), p.wo = head_out(w);
-  p.n_rb = (p.ho + kHeadBand - 1) / kHeadBand;
-  p.items = n * p.n_rb;
-  const int want = std::min(p.items, kHeadMaxSlabs);
-  p.per = (p.items + want - 1) / want;
-  p.n_slabs = (p.items + p.per - 1) / p.per;
-  p.ws = (size_t)p.n_slabs * (c_in * 9 + 1) * sizeof(float);
-  return p;
 }
 
 }  // namespace
@@ -585,61 +277,6 @@ int pv_conv2d_wide_stripe_bwd_weight_f32(const float* history, const int32_t* st
   sp.start = stripe_start, sp.width = stripe_width, sp.n_hist = n_hist;
   return run_wgrad<SRC_STRIPE>(who, stripe_in(history, n_hist, h, w_img), sp, plain_in(dy, nullptr, c_out, h - 2, w_img - 2),
                                0, p, dw, dbias, ws, ws_bytes, as_stream(stream));
-}
-
-int pv_conv2d_head_s2_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
-                              int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream) {
-  const char* who = "pv_conv2d_head_s2_fwd_f32";
-  PV_REQUIRE(x && w && y, PV_EINVAL, "%s: null pointer", who);
-  int rc = check_head(who, n, c_in, c_out, h_in, w_in);
-  if (rc) return rc;
-  const int ho = head_out(h_in), wo = head_out(w_in), total = n * ho * wo;
-  head_fwd<<<dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream)>>>(
-      x, w, bias, y, total, c_in, h_in, w_in, ho, wo, relu ? 1 : 0);
-  return check_launch(who);
-}
-
-int pv_conv2d_head_s2_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
-                                   int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream) {
-  const char* who = "pv_conv2d_head_s2_bwd_data_f32";
-  PV_REQUIRE(dy && w && dx, PV_EINVAL, "%s: null pointer", who);
-  PV_REQUIRE(!dy_gate, PV_EINVAL, "%s: the head has no ReLU, so it takes no dy_gate", who);
-  int rc = check_head(who, n, c_in, c_out, h_in, w_in);
-  if (rc) return rc;
-  PV_REQUIRE(c_in <= 65535 && n <= 65535, PV_ESIZE, "%s: more than 65535 channels or images (grid axes)", who);
-  head_bwd_data<<<dim3((unsigned)((h_in * w_in + kHeadDxPerBlock - 1) / kHeadDxPerBlock), (unsigned)c_in, (unsigned)n), dim3(kBlock), 0,
-                  as_stream(stream)>>>(dy, w, dx, x_gate, c_in, h_in, w_in, head_out(h_in), head_out(w_in));
-  return check_launch(who);
-}
-
-int pv_conv2d_head_s2_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
-                                                 size_t* bytes) {
-  const char* who = "pv_conv2d_head_s2_bwd_weight_workspace_bytes";
-  PV_REQUIRE(bytes, PV_EINVAL, "%s: null pointer", who);
-  int rc = check_head(who, n, c_in, c_out, h_in, w_in);
-  if (rc) return rc;
-  *bytes = head_plan(n, c_in, h_in, w_in).ws;
-  return PV_OK;
-}
-
-int pv_conv2d_head_s2_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias,
-                                     int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
-                                     size_t ws_bytes, void* stream) {
-  const char* who = "pv_conv2d_head_s2_bwd_weight_f32";
-  PV_REQUIRE(x && dy && dw && dbias, PV_EINVAL, "%s: null pointer", who);
-  PV_REQUIRE(!dy_gate, PV_EINVAL, "%s: the head has no ReLU, so it takes no dy_gate", who);
-  int rc = check_head(who, n, c_in, c_out, h_in, w_in);
-  if (rc) return rc;
-  const HeadPlan p = head_plan(n, c_in, h_in, w_in);
-  rc = check_workspace(who, ws, ws_bytes, p.ws);
-  if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  head_wgrad<<<dim3((unsigned)c_in, (unsigned)p.n_slabs), dim3(kBlock), 0, st>>>(x, dy, (float*)ws, c_in, h_in, w_in, p.ho,
-                                                                                    p.wo, p.n_rb, p.items, p.per);
-  rc = check_launch(who);
-  if (rc) return rc;
-  launch_slab_sum(ws, dw, dbias, 1, c_in * 9, p.n_slabs, st);
-  return check_launch(who);
 }
 
 }  // extern "C"

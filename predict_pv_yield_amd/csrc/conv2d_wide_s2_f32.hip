@@ -5,7 +5,8 @@
 // f32 accumulation).  Planes are up to 128 wide on the wide side (a Conv2d's input, a ConvTranspose2d's output).
 //
 // The passes are the three forms of conv2d_s2_f32.hip, but 64 / 128-channel weights (up to 590 KB) do not fit the VGPRs, so K
-// is streamed through LDS in channel chunks as in conv2d_wide_f32.hip:
+// is streamed through LDS in channel chunks as in conv2d_wide_f32.hip (the chunk layout, band_stride and the whole
+// weight-gradient tile of form C are conv_wide_f32.h's; forms A and B keep their own loops and parity layouts):
 //   A  strided gather   D[m][oh][ow] = sum_{tap, c} W[m][c][tap] X[c][2 oh + kh][2 ow + kw]
 //      Conv2d forward (also the stripe first layer); ConvTranspose2d data gradient (over dy, weights [c_in][c_out] read as
 //      [m][c], unmirrored).  Per chunk of 8 channels the (2 tr + 1) x (2 tc + 1) band is staged split by column parity (even
@@ -24,33 +25,27 @@
 //      of its positions) is a plane sum in slabs of its own.  Block = (slab of tiles, chunk of 14 sliding channels); slabs
 //      are cut across images and tiles, so small planes still fill the device.  Fixed slabs, added in slab order by the
 //      shared conv2d_slab_sum_f32: no atomics, identical bits run to run.
-// The one-output-channel ConvTranspose2d head (stride 1) is bandwidth-bound: plain vector code, sums in a fixed order, as
-// pv_conv2d_head_s2_*.  pv_mse_pred_window_f32 is the loss over a window of the prediction.
+// The model's last layer, the one-output-channel ConvTranspose2d head pv_convt2d_head_*, is in conv2d_head_f32.hip.
+// pv_mse_pred_window_f32 is the loss over a window of the prediction.
 #include "conv2d_stripe_f32.h"
+#include "conv_wide_f32.h"
 
 namespace pv {
 namespace {
 
-// A / B: 4 x 16 output channels per block, 8 input channels per chunk; weight rows [tap][c] are 80 floats apart and the
-// band's channel stride is 16 mod 32 (the two k-rows a half wave reads fall on disjoint banks); the taps are 644 floats
-// apart (4 mod 32), so the nine taps of one (c, m), which neighbouring threads stage, fall on different banks
-constexpr int kMT = 4, kMB = kMT * 16, kMBP = kMB + 16, kCC = 8, kTapStride = kCC * kMBP + 4;
+// A / B: the 4 x 16 output channels per block, 8 input channels per chunk and 80-float weight rows of conv_wide_f32.h; here
+// the taps are 644 floats apart (4 mod 32), so the nine taps of one (c, m), which neighbouring threads stage, fall on
+// different banks
+constexpr int kTapStride = kCC * kMBP + 4;
 constexpr int kWPer = 9 * kCC * kMB / 256;   // weights per thread and chunk (18)
 constexpr int kBandSlots = 6;                // B: elements of the staged source band per thread and chunk
 constexpr int kWantBlocks = 512;             // two blocks per CU: below this the planner takes smaller tiles
-// C: 14 sliding channels per chunk -> 126 (c, tap) columns + a ones column + a zero column = 8 tiles, 2 per wave
-constexpr int kWgCC = 14, kWgNTW = 2, kWgPos = 64, kWgDps = kWgPos + 2, kWgMaxTc = 24;
+// C: the 14-channel chunks of conv_wide_f32.h over tiles of at most 64 positions and 24 columns
+constexpr int kWgPos = 64, kWgDps = kWgPos + 2, kWgMaxTc = 24;
 constexpr size_t kLdsBytes = 64 * 1024;    // per block: every tile below is planned inside it
 constexpr int kMaxWgBlocks = 768;            // three blocks per CU
-constexpr int kMaxW = 128;                   // widest plane on the wide side
 
 inline int conv_out(int s) { return (s - 3) / 2 + 1; }
-
-// channel stride of a staged band: >= rows * sw and 16 mod 32
-__host__ __device__ inline int band_stride(int rows, int sw) {
-  const int cs = rows * sw;
-  return cs + ((16 - cs % 32) + 32) % 32;
-}
 
 // Stage channels [c0, c0 + cc) x rows [r0, r0 + rows) x columns [col0, col0 + ncols) of image n as lds[ch * cs + r * sw +
 // slot]; outside the image and beyond c_in: 0.  slot = the column's offset, or with SPLIT the even offsets first (offset / 2)
@@ -331,10 +326,9 @@ __global__ __launch_bounds__(kBlock) void wide_s2_scatter(Fwd a) {
     }
 }
 
-// C.  Block = (slab, chunk of 14 sliding channels); D[m][col] over every position of the slab's tiles, col = c * 9 + tap
-// (local to the chunk) for col < 126, col 126 a column of ones (written by chunk 0), col 127 zero.  Wave w owns the
-// 16-column tiles 2 w, 2 w + 1 against all MT row tiles; a k-step is 4 positions.  The tile's G lives in LDS as [M][66]
-// (zero beyond the tile), the sliding operand as [14][2 tr + 1][2 tc + 1], plus xo[pos] = the position's offset in it.
+// C.  Block = (slab, chunk of 14 sliding channels) over the slab's items (image, row band, column band); the tile is that of
+// conv_wide_f32.h at position stride 2, its ones column written by chunk 0.  The tile's G lives in LDS as [M][66] (zero
+// beyond the tile), the sliding operand as [14][2 tr + 1][2 tc + 1].
 struct Wg {
   In in;                    // the sliding operand (SRC_PLAIN with its gate, or SRC_STRIPE)
   Stripe sp;
@@ -345,9 +339,8 @@ struct Wg {
 
 template <int SRC, int MT>
 __global__ __launch_bounds__(kBlock) void wide_s2_wgrad(Wg q) {
-  constexpr int NTW = kWgNTW, CC = kWgCC, DPS = kWgDps, M = MT * 16;
+  constexpr int CC = kWgCC, DPS = kWgDps, M = MT * 16;
   extern __shared__ float lds[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int slab = blockIdx.x, chunk = blockIdx.y, ci0 = chunk * CC;
   const int sw = 2 * q.tc + 1, cs = (2 * q.tr + 1) * sw;
   float* xl = lds;                     // [CC][cs]
@@ -355,25 +348,15 @@ __global__ __launch_bounds__(kBlock) void wide_s2_wgrad(Wg q) {
   int* xo = (int*)(dl + M * DPS);      // [DPS]
   const Stripe none = {};
 
-  int coff[NTW];
-  float bmul[NTW], badd[NTW];
+  int coff[kWgNTW];
+  float bmul[kWgNTW], badd[kWgNTW];
+  wg_columns(ci0, q.in.c_in, cs, sw, coff, bmul, badd);
   bool any = false;                    // a wave whose 32 columns are all padding only stages
 #pragma unroll
-  for (int j = 0; j < NTW; ++j) {
-    const int col = (wave * NTW + j) * 16 + (lane & 15);
-    const bool real = col < CC * 9 && ci0 + col / 9 < q.in.c_in;
-    const int ci = real ? col / 9 : 0, tap = real ? col % 9 : 0;
-    coff[j] = ci * cs + (tap / 3) * sw + tap % 3;
-    bmul[j] = real ? 1.0f : 0.0f;
-    badd[j] = col == CC * 9 ? 1.0f : 0.0f;
-    any = any || real || col == CC * 9;
-  }
+  for (int j = 0; j < kWgNTW; ++j) any = any || bmul[j] != 0.0f || badd[j] != 0.0f;
   any = __any(any);
-  acc4 acc[MT][NTW];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int j = 0; j < NTW; ++j) acc[mt][j] = (acc4){0.0f, 0.0f, 0.0f, 0.0f};
+  acc4 acc[MT][kWgNTW];
+  zero_acc(acc);
 
   const int it0 = slab * q.per, it1 = min(it0 + q.per, q.items);
   for (int it = it0; it < it1; ++it) {
@@ -382,48 +365,16 @@ __global__ __launch_bounds__(kBlock) void wide_s2_wgrad(Wg q) {
     const int rows = min(q.tr, q.h_out - r0), cols = min(q.tc, q.w_out - c0), npos = rows * cols;
     __syncthreads();   // the previous item's reads are done
     stage_band<SRC, false>(xl, q.in, q.sp, n, ci0, CC, 2 * r0, 2 * q.tr + 1, 2 * c0, sw, sw, cs, 0);
-    // G rows [m][oh] of the tile, packed to cols per row; the (up to 3) positions that round the tile to a k-step: 0
+    // G rows [m][oh] of the tile, packed to cols per row
     stage_band<SRC_PLAIN, false>(dl, q.g, none, n, 0, M, r0, rows, c0, cols, cols, DPS, 0);
-    for (int i = threadIdx.x; i < M * 4; i += kBlock) {
-      const int p = npos + (i & 3);
-      if (p < DPS) dl[(i >> 2) * DPS + p] = 0.0f;
-    }
-    for (int p = threadIdx.x; p < DPS; p += kBlock) {
-      const int oh = p / cols, ow = p - oh * cols;
-      xo[p] = p < npos ? 2 * oh * sw + 2 * ow : 0;
-    }
+    wg_item_tail<MT, 2, DPS>(dl, xo, npos, cols, sw);
     __syncthreads();
     if (!any) continue;
-    const int steps = (npos + 3) / 4;
-    for (int s = 0; s < steps; ++s) {
-      const int p = s * 4 + (lane >> 4);
-      const int xoff = xo[p];
-      float av[MT];
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt) av[mt] = dl[(mt * 16 + (lane & 15)) * DPS + p];
-#pragma unroll
-      for (int j = 0; j < NTW; ++j) {
-        const float b = xl[coff[j] + xoff] * bmul[j] + badd[j];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], b, acc[mt][j], 0, 0, 0);
-      }
-    }
+    wg_ksteps<MT, DPS>(xl, dl, xo, npos, coff, bmul, badd, 1.0f, acc);
   }
-  // this slab's partial sums of the chunk's columns: row m = mt * 16 + (lane / 16) * 4 + i
   const int ncols = q.in.c_in * 9 + 1;
-  float* out = q.slabs + (size_t)slab * M * ncols;
-#pragma unroll
-  for (int j = 0; j < NTW; ++j) {
-    const int col = (wave * NTW + j) * 16 + (lane & 15);
-    int gcol = -1;
-    if (col < CC * 9 && ci0 + col / 9 < q.in.c_in) gcol = ci0 * 9 + col;
-    else if (col == CC * 9 && chunk == 0) gcol = ncols - 1;
-    if (gcol < 0) continue;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) out[(size_t)(mt * 16 + (lane >> 4) * 4 + i) * ncols + gcol] = acc[mt][j][i];
-  }
+  wg_store<MT>(q.slabs + (size_t)slab * M * ncols, ncols, ci0, q.in.c_in, chunk == 0, nullptr,
+               [&](int col) { return ci0 * 9 + col; }, acc);
 }
 
 // The ConvTranspose2d bias gradient's slabs: block (channel, slab) adds dy (zeroed where the gate <= 0) over the channel's
@@ -447,112 +398,6 @@ __global__ __launch_bounds__(kBlock) void plane_sum_slabs(const float* __restric
     __syncthreads();
   }
   if (threadIdx.x == 0) slabs[(size_t)blockIdx.y * c + ch] = part[0];
-}
-
-// ---- the ConvTranspose2d head: 3x3, stride 1, one output channel ---------------------------------------------------------
-// x [n][c_in][h][w] -> y [n][1][h + 2][w + 2]; output (oh, ow) reads x (oh - kh, ow - kw) with weight w[ci][0][kh][kw].
-
-// forward: one output per thread; the 9 taps of a channel are one fma chain, the channels go round-robin into four partial
-// sums added in a fixed order
-__global__ __launch_bounds__(kBlock) void headt_fwd(const float* __restrict__ x, const float* __restrict__ w,
-                                                    const float* __restrict__ bias, float* __restrict__ y, int total,
-                                                    int c_in, int h, int wi, int relu) {
-  const int idx = blockIdx.x * kBlock + threadIdx.x;
-  if (idx >= total) return;
-  const int ho = h + 2, wo = wi + 2;
-  const int ow = idx % wo, oh = (idx / wo) % ho, b = idx / (wo * ho);
-  int off[9];
-  bool ok[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    const int ir = oh - t / 3, ic = ow - t % 3;
-    ok[t] = ir >= 0 && ir < h && ic >= 0 && ic < wi;
-    off[t] = ok[t] ? ir * wi + ic : 0;
-  }
-  const size_t plane = (size_t)h * wi;
-  const float* xb = x + (size_t)b * c_in * plane;
-  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  for (int ci = 0; ci < c_in; ++ci) {
-    const float* xp = xb + ci * plane;
-    const float* wp = w + ci * 9;
-    float s = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) s = fmaf(wp[t], ok[t] ? xp[off[t]] : 0.0f, s);
-    acc[ci & 3] += s;
-  }
-  float v = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + (bias ? bias[0] : 0.0f);
-  if (relu) v = v > 0.0f ? v : 0.0f;
-  y[idx] = v;
-}
-
-// data gradient: dx[ci][i][j] = sum_tap w[ci][tap] dy[i + kh][j + kw], every tap inside dy.  Block = (1024 elements of a
-// plane, input channel, image): the channel's nine weights are uniform over the block
-constexpr int kHeadDxPerBlock = 4 * kBlock;
-__global__ __launch_bounds__(kBlock) void headt_bwd_data(const float* __restrict__ dy, const float* __restrict__ w,
-                                                         float* __restrict__ dx, const float* __restrict__ x_gate,
-                                                         int c_in, int h, int wi) {
-  const int ci = blockIdx.y, b = blockIdx.z, plane = h * wi, wo = wi + 2;
-  const float* dyb = dy + (size_t)b * (h + 2) * wo;
-  const float* wp = w + ci * 9;
-  const size_t base = ((size_t)b * c_in + ci) * plane;
-  const int p1 = min(plane, (int)(blockIdx.x + 1) * kHeadDxPerBlock);
-  for (int p = blockIdx.x * kHeadDxPerBlock + threadIdx.x; p < p1; p += kBlock) {
-    const int r = p / wi, c = p - r * wi;
-    float s = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 9; ++t) s = fmaf(wp[t], dyb[(r + t / 3) * wo + c + t % 3], s);
-    if (x_gate && !(x_gate[base + p] > 0.0f)) s = 0.0f;
-    dx[base + p] = s;
-  }
-}
-
-// weight / bias gradient.  Block = (input channel, slab of (image, band of 16 input rows) items); every thread sums its
-// positions' nine products, then the block adds the threads' sums in a fixed tree.  The bias gradient runs over dy's own
-// positions: channel 0's blocks add the band's dy rows (the last band also the two rows below it).  slabs [n_slabs][c_in *
-// 9 + 1], the last column the bias gradient.
-constexpr int kHeadBand = 16, kHeadMaxSlabs = 128;
-
-__global__ __launch_bounds__(kBlock) void headt_wgrad(const float* __restrict__ x, const float* __restrict__ dy,
-                                                      float* __restrict__ slabs, int c_in, int h, int wi, int n_rb,
-                                                      int items, int per) {
-  __shared__ float part[kBlock / 64][10];
-  const int ci = blockIdx.x, slab = blockIdx.y, wo = wi + 2;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float a[10];
-#pragma unroll
-  for (int t = 0; t < 10; ++t) a[t] = 0.0f;
-  const int it0 = slab * per, it1 = min(it0 + per, items);
-  for (int it = it0; it < it1; ++it) {
-    const int rb = it % n_rb, b = it / n_rb;
-    const int i0 = rb * kHeadBand, rows = min(kHeadBand, h - i0);
-    const float* xp = x + ((size_t)b * c_in + ci) * h * wi;
-    const float* dyb = dy + (size_t)b * (h + 2) * wo;
-    for (int p = threadIdx.x; p < rows * wi; p += kBlock) {
-      const int i = i0 + p / wi, j = p % wi;
-      const float v = xp[i * wi + j];
-#pragma unroll
-      for (int t = 0; t < 9; ++t) a[t] = fmaf(v, dyb[(i + t / 3) * wo + j + t % 3], a[t]);
-    }
-    if (ci == 0) {
-      const int drows = rows + (rb == n_rb - 1 ? 2 : 0);
-      for (int p = threadIdx.x; p < drows * wo; p += kBlock) a[9] += dyb[i0 * wo + p];
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 10; ++t) {
-    float v = a[t];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-    if (lane == 0) part[wave][t] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 10) {
-    const int t = threadIdx.x;
-    const float v = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
-    const int ncols = c_in * 9 + 1;
-    if (t < 9) slabs[(size_t)slab * ncols + ci * 9 + t] = v;
-    else if (ci == 0) slabs[(size_t)slab * ncols + ncols - 1] = v;
-  }
 }
 
 // ---- the loss over a window of the prediction ------------------------------------------------------------------------------
@@ -671,8 +516,7 @@ Fwd scatter_args(const float* w, const float* bias, float* y, int m_out, int h_o
   return a;
 }
 
-struct WgPlan {
-  int h_out, w_out, tr, tc, n_rb, n_cb, items, n_chunks, n_slabs, per;
+struct WgPlan : WgTiles {
   size_t lds, ws;
 };
 
@@ -681,17 +525,7 @@ struct WgPlan {
 // are dealt to at most kMaxWgBlocks blocks over (slab, chunk), so a slab may hold a part of one image or several images.
 WgPlan wg_plan(int n, int c, int rows, int h_out, int w_out) {
   WgPlan p;
-  p.h_out = h_out, p.w_out = w_out;
-  p.n_cb = (w_out + kWgMaxTc - 1) / kWgMaxTc;
-  p.tc = (w_out + p.n_cb - 1) / p.n_cb;
-  p.tr = std::max(1, std::min(h_out, kWgPos / p.tc));
-  p.n_rb = (h_out + p.tr - 1) / p.tr;
-  p.tr = (h_out + p.n_rb - 1) / p.n_rb;
-  p.items = n * p.n_rb * p.n_cb;
-  p.n_chunks = (c + kWgCC - 1) / kWgCC;
-  const int want = std::max(1, std::min(p.items, kMaxWgBlocks / p.n_chunks));
-  p.per = (p.items + want - 1) / want;
-  p.n_slabs = (p.items + p.per - 1) / p.per;
+  (WgTiles&)p = wg_tiles(n, c, h_out, w_out, kWgMaxTc, kWgPos, kWgPos, kMaxWgBlocks, 1);   // rows bounded by positions only
   p.lds = ((size_t)kWgCC * (2 * p.tr + 1) * (2 * p.tc + 1) + (size_t)rows * kWgDps) * sizeof(float) + kWgDps * sizeof(int);
   p.ws = (size_t)p.n_slabs * rows * (c * 9 + 1) * sizeof(float);
   return p;
@@ -735,20 +569,15 @@ int check_dims(const char* who, int n, int c_in, int c_out, int h_in, int w_in, 
 int check_ws2(const char* who, int n, int c_in, int c_out, int h_in, int w_in, Kind kind) {
   int rc = check_dims(who, n, c_in, c_out, h_in, w_in, kind);
   if (rc) return rc;
-  if (kind == KIND_CONVT)
-    PV_REQUIRE(c_in == 128 && c_out == 128, PV_ESIZE, "%s: unsupported channel counts c_in=%d c_out=%d (128 -> 128)", who,
-               c_in, c_out);
-  else
-    PV_REQUIRE((c_in == 64 || c_in == 128) && c_out == 128, PV_ESIZE,
-               "%s: unsupported channel counts c_in=%d c_out=%d ((64 | 128) -> 128)", who, c_in, c_out);
+  if (kind == KIND_CONV) return check_wide_channels(who, c_in, c_out);
+  PV_REQUIRE(c_in == 128 && c_out == 128, PV_ESIZE, "%s: unsupported channel counts c_in=%d c_out=%d (128 -> 128)", who,
+             c_in, c_out);
   return PV_OK;
 }
 
 int check_stripe(const char* who, int n, int n_hist, int h, int w, int c_out, int stripe_width) {
-  PV_REQUIRE(n_hist >= 1 && n_hist <= kMaxHist, PV_ESIZE, "%s: unsupported channel count: %d history frames (1..%d)", who,
-             n_hist, kMaxHist);
-  PV_REQUIRE(c_out == 64, PV_ESIZE, "%s: unsupported channel count c_out=%d (64)", who, c_out);
-  PV_REQUIRE(stripe_width >= 0, PV_EINVAL, "%s: negative stripe width", who);
+  int rc = check_stripe_args(who, n_hist, c_out, stripe_width);
+  if (rc) return rc;
   return check_dims(who, n, n_hist + 1, c_out, h, w, KIND_CONV);
 }
 
@@ -759,32 +588,6 @@ void bias_slabs(int n, int& n_slabs, int& per) {
   const int want = std::min(n, 32);
   per = (n + want - 1) / want;
   n_slabs = (n + per - 1) / per;
-}
-
-// the head: any c_in, output (h + 2) x (w + 2) at most kMaxW + 2 wide, every tensor within 32-bit indexing
-int check_headt(const char* who, int n, int c_in, int c_out, int h_in, int w_in) {
-  PV_REQUIRE(n > 0 && c_in > 0 && h_in > 0 && w_in > 0, PV_EINVAL, "%s: non-positive dimension", who);
-  PV_REQUIRE(c_out == 1, PV_ESIZE, "%s: unsupported channel count c_out=%d (1)", who, c_out);
-  PV_REQUIRE(w_in <= kMaxW, PV_ESIZE, "%s: width %d beyond %d", who, w_in, kMaxW);
-  PV_REQUIRE((long long)n * c_in * h_in * w_in < (1LL << 31) && (long long)n * (h_in + 2) * (w_in + 2) < (1LL << 31),
-             PV_ESIZE, "%s: tensor beyond 2^31 elements (32-bit indexing)", who);
-  return PV_OK;
-}
-
-struct HeadPlan {
-  int n_rb, items, per, n_slabs;
-  size_t ws;
-};
-
-HeadPlan headt_plan(int n, int c_in, int h) {
-  HeadPlan p;
-  p.n_rb = (h + kHeadBand - 1) / kHeadBand;
-  p.items = n * p.n_rb;
-  const int want = std::min(p.items, kHeadMaxSlabs);
-  p.per = (p.items + want - 1) / want;
-  p.n_slabs = (p.items + p.per - 1) / p.per;
-  p.ws = (size_t)p.n_slabs * (c_in * 9 + 1) * sizeof(float);
-  return p;
 }
 
 }  // namespace
@@ -939,62 +742,6 @@ int pv_convt2d_wide_s2_bwd_weight_f32(const float* x, const float* dy, const flo
   rc = check_launch(who);
   if (rc) return rc;
   launch_slab_sum(bslabs, nullptr, dbias, c_out, 0, nb, st);
-  return check_launch(who);
-}
-
-int pv_convt2d_head_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
-                            int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream) {
-  const char* who = "pv_convt2d_head_fwd_f32";
-  PV_REQUIRE(x && w && y, PV_EINVAL, "%s: null pointer", who);
-  int rc = check_headt(who, n, c_in, c_out, h_in, w_in);
-  if (rc) return rc;
-  const int total = n * (h_in + 2) * (w_in + 2);
-  headt_fwd<<<dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream)>>>(
-      x, w, bias, y, total, c_in, h_in, w_in, relu ? 1 : 0);
-  return check_launch(who);
-}
-
-int pv_convt2d_head_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
-                                 int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream) {
-  const char* who = "pv_convt2d_head_bwd_data_f32";
-  PV_REQUIRE(dy && w && dx, PV_EINVAL, "%s: null pointer", who);
-  PV_REQUIRE(!dy_gate, PV_EINVAL, "%s: the head has no ReLU, so it takes no dy_gate", who);
-  int rc = check_headt(who, n, c_in, c_out, h_in, w_in);
-  if (rc) return rc;
-  PV_REQUIRE(c_in <= 65535 && n <= 65535, PV_ESIZE, "%s: more than 65535 channels or images (grid axes)", who);
-  headt_bwd_data<<<dim3((unsigned)((h_in * w_in + kHeadDxPerBlock - 1) / kHeadDxPerBlock), (unsigned)c_in, (unsigned)n),
-                   dim3(kBlock), 0, as_stream(stream)>>>(dy, w, dx, x_gate, c_in, h_in, w_in);
-  return check_launch(who);
-}
-
-int pv_convt2d_head_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
-                                               size_t* bytes) {
-  const char* who = "pv_convt2d_head_bwd_weight_workspace_bytes";
-  PV_REQUIRE(bytes, PV_EINVAL, "%s: null pointer", who);
-  int rc = check_headt(who, n, c_in, c_out, h_in, w_in);
-  if (rc) return rc;
-  *bytes = headt_plan(n, c_in, h_in).ws;
-  return PV_OK;
-}
-
-int pv_convt2d_head_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias,
-                                   int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
-                                   size_t ws_bytes, void* stream) {
-  const char* who = "pv_convt2d_head_bwd_weight_f32";
-  PV_REQUIRE(x && dy && dw && dbias, PV_EINVAL, "%s: null pointer", who);
-  PV_REQUIRE(!dy_gate, PV_EINVAL, "%s: the head has no ReLU, so it takes no dy_gate", who);
-  int rc = check_headt(who, n, c_in, c_out, h_in, w_in);
-  if (rc) return rc;
-  PV_REQUIRE(c_in <= 65535, PV_ESIZE, "%s: more than 65535 channels (grid axis)", who);
-  const HeadPlan p = headt_plan(n, c_in, h_in);
-  rc = check_workspace(who, ws, ws_bytes, p.ws);
-  if (rc) return rc;
-  hipStream_t st = as_stream(stream);
-  headt_wgrad<<<dim3((unsigned)c_in, (unsigned)p.n_slabs), dim3(kBlock), 0, st>>>(x, dy, (float*)ws, c_in, h_in, w_in, p.n_rb,
-                                                                                 p.items, p.per);
-  rc = check_launch(who);
-  if (rc) return rc;
-  launch_slab_sum(ws, dw, dbias, 1, c_in * 9, p.n_slabs, st);
   return check_launch(who);
 }
 

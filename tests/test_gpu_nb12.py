@@ -161,6 +161,32 @@ def test_head_against_float64(device, c_in, n, h, w):
     assert err_w <= NORM_TOL and err_b <= NORM_TOL
 
 
+def test_strided_heads_are_one_kernel_set_at_two_paddings(device):
+    """The padding-2 head on x and the padding-1 head on x with a ring of zeros are the same kernels at PAD = 2 and 1, so they
+    agree bit for bit: a tap in the zero ring is fmaf(w, 0.0f, s), exactly what the out-of-image predicate gives, and the
+    thread -> position maps and slab plans depend only on the output extent ((s + 1) // 2 + 1 on both sides).  c_in = 5 is
+    no multiple of the four partial sums, the sides are odd and even, 18 output rows are two bands of 16."""
+    K = _ops()
+    g = _g(700)
+    x = _randn(g, 2, 5, 33, 6)
+    wt, b = _conv_params(g, 1, 5, kernel=(3, 3))
+    xp = F.pad(x, (1, 1, 1, 1))
+    xd, xpd, wd, bd = x.to(device), xp.to(device).contiguous(), wt.to(device), b.to(device)
+    y2, y1 = K.conv2d_head_s2_fwd_f32(xd, wd, bd), K.conv2d_head_s2p1_fwd_f32(xpd, wd, bd)
+    assert tuple(y2.shape) == tuple(y1.shape) == (2, 1, 18, 4)
+    assert torch.equal(y2, y1), "forward"
+    dy = _randn(g, *y2.shape).to(device)
+    dw2, db2 = K.conv2d_head_s2_bwd_weight_f32(xd, dy, None, tuple(wt.shape))
+    dw1, db1 = K.conv2d_head_s2p1_bwd_weight_f32(xpd, dy, None, tuple(wt.shape))
+    assert torch.equal(dw2, dw1) and torch.equal(db2, db1), "weight / bias gradient"
+    x_gate = _randn(g, *x.shape)
+    gate_p = F.pad(x_gate, (1, 1, 1, 1)).to(device).contiguous()
+    dx2 = K.conv2d_head_s2_bwd_data_f32(dy, None, wd, x_gate.to(device), tuple(x.shape))
+    dx1 = K.conv2d_head_s2p1_bwd_data_f32(dy, None, wd, gate_p, tuple(xp.shape))
+    assert torch.equal(dx2, dx1[:, :, 1:-1, 1:-1]), "data gradient"
+    assert dx2.abs().sum() > 0 and dw2.abs().sum() > 0
+
+
 @pytest.mark.parametrize("n, h, w", [(2, 9, 46), (1, 1, 1), (2, 10, 47)])
 def test_head_depth2_view_against_float64_conv3d(device, n, h, w):
     """conv.8 on depth 2: the Conv2d head on the views [n][2 c][h][w] / [1][2 c][3][3] against F.conv3d itself."""
