@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void linear_fwd_bf16_kernel(const uint16_t* __
     for (int s = 0; s < 4; ++s) {
       const long long kk = kbase + 32 * hh + 8 * s;
       const bool ok = kk + 8 <= k;
-      const long long kc = ok ? kbase + 8 * s : 0;
+      const long long kc = ok ? kbase + 8 * s : -32 * hh;      // (wp / xp already point 32 hh into the row: its first 16 bytes, in bounds for every k >= 8)
       bf16x8 wv = *reinterpret_cast<const bf16x8*>(wp + kc);
       wv = ok ? wv : zero8;
 #pragma unroll
