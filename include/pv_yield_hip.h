@@ -643,6 +643,50 @@ int pv_conv2d_head_s2p1_bwd_weight_f32(const float* x, const float* dy, const fl
                                        int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
                                        size_t ws_bytes, void* stream);
 
+/* ---- notebooks/08_multiple_historical_images_as_separate_channels.ipynb: strided depth-2 Conv3d, horizon ConvTranspose2d ---- */
+/* (line numbers: the raw 08_...ipynb file; the LitAutoEncoder cell starts at 1356, encoder_conv is at 1365-1372, decoder_conv
+ * at 1374-1380, forward at 1382-1392.)  NCDHW / NCHW f32, exact f32; gates (NULL = none) and weight-gradient slabs follow the
+ * conventions of the pv_conv2d_s2_* entry points above.  (d_in, h_in, w_in) is always the extent of the layer's input x.
+ * pv_conv3d_s2_*: kernel (2, 3, 3), stride (1, 2, 2), no padding: d -> d - 1 (d_in >= 2), h -> (h - 3) / 2 + 1 (h_in, w_in >= 3);
+ * (c_in, c_out) = (1, 8), (8, 32) or (32, 32); w_in <= 128; every tensor below 2^31 elements.  No permuted or concatenated
+ * copy of an activation is made: the depth taps are read in place as a second set of channels of a stride-2 Conv2d.
+ * Unsupported shapes return PV_ESIZE, null pointers PV_EINVAL, before any launch. */
+/* replaces: nn.Conv3d(c_in, c_out, kernel_size=KERNEL_SIZE, stride=STRIDE) (+ nn.ReLU() if relu), encoder_conv.0 / .2 / .4 of
+ * 08_...ipynb:1366-1370.  x [n][c_in][d][h][w], w [c_out][c_in][2][3][3], y [n][c_out][d - 1][h_out][w_out]; bias may be
+ * NULL. */
+int pv_conv3d_s2_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in, int32_t c_out,
+                         int32_t d_in, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of encoder_conv.2 / .4 (autograd of 08_...ipynb:1368-1370; (1, 8) has none and returns
+ * PV_ESIZE).  Input depth z receives from output depths z and z - 1; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <=
+ * 0; the last row / column of an even-sized input, which the forward never reads, is written as exact 0. */
+int pv_conv3d_s2_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate, int32_t n,
+                              int32_t c_in, int32_t c_out, int32_t d_in, int32_t h_in, int32_t w_in, void* stream);
+/* bytes of the weight-gradient workspace: one partial [c_out][c_in * 9 + 1] per slab of tiles (the two depth taps use the
+ * same slabs one after the other) */
+int pv_conv3d_s2_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t d_in, int32_t h_in, int32_t w_in,
+                                            size_t* bytes);
+/* replaces: the weight and bias gradients of encoder_conv.0 / .2 / .4.  dw [c_out][c_in][2][3][3] and dbias [c_out] are
+ * overwritten; slab partials summed in slab order (no atomics, identical bits run to run). */
+int pv_conv3d_s2_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias, int32_t n,
+                                int32_t c_in, int32_t c_out, int32_t d_in, int32_t h_in, int32_t w_in, void* ws,
+                                size_t ws_bytes, void* stream);
+/* replaces: x[FORECAST_HORIZON].view(-1, 1, 1, 1).expand(...); torch.cat((encoder_out, forecast_horizon), dim=1);
+ * nn.ConvTranspose2d(CHANNELS + 1, CHANNELS, kernel_size=3, stride=2) (+ nn.ReLU() if relu), 08_...ipynb:1375, 1388-1391.  x
+ * [n][32][h][w]; horizon [n] (device f32): input channel 32 is horizon[i] inside the image, synthesised in the kernel; w
+ * [33][32][3][3]; y [n][32][2 h + 1][2 w + 1]; 2 w + 1 <= 128; bias may be NULL.  The input gradient of the 32 real channels
+ * is pv_convt2d_s2_bwd_data_f32 on the first 32 rows of w. */
+int pv_convt2d_s2_horizon_fwd_f32(const float* x, const float* horizon, const float* w, const float* bias, float* y, int32_t n,
+                                  int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* bytes of the workspace of pv_convt2d_s2_horizon_bwd_weight_f32: one partial [33][32 * 9 + 1] per slab of tiles, then one
+ * partial [32] per slab of images for the bias gradient */
+int pv_convt2d_s2_horizon_bwd_weight_workspace_bytes(int32_t n, int32_t h_in, int32_t w_in, size_t* bytes);
+/* replaces: the weight and bias gradients of decoder_conv.0 (autograd of 08_...ipynb:1375), re-synthesising the horizon
+ * channel as the forward does: dw [33][32][3][3], row 32 = sum_n horizon[n] sum_pos dy[n][co][2 pos + tap]; dbias [32] = the
+ * sum of dy (both with dy zeroed where dy_gate <= 0); deterministic. */
+int pv_convt2d_s2_horizon_bwd_weight_f32(const float* x, const float* horizon, const float* dy, const float* dy_gate, float* dw,
+                                         float* dbias, int32_t n, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
+                                         void* stream);
+
 /* MaxPool3d over x[B*C planes][Ti,Hi,Wi]; argmax (may be NULL) = flat winner offset inside the plane stack, first
  * maximum wins, NaN propagates (torch CPU semantics).  bwd overwrites dx by gathering dy through argmax. */
 int pv_maxpool3d_fwd_f32(const float* x, float* y, int32_t* argmax, const pv_conv3d_geom* d, void* stream);

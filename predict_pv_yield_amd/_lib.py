@@ -112,6 +112,14 @@ _C3D_BWD_DATA = [c_vp] * 5 + _DIMS3D + [c_vp]                        # dy, dy_ga
 _C3D_BWD_WEIGHT = [c_vp] * 5 + _DIMS3D + _WORKSPACE + [c_vp]         # x, dy, dy_gate, dw, dbias, dims
 _HORIZON_FWD = [c_vp] * 5 + [c_i32] * 5 + [c_vp]                     # history, horizon, weight, bias, y
 _HORIZON_BWD_WEIGHT = [c_vp] * 5 + [c_i32] * 5 + _WORKSPACE + [c_vp]  # history, horizon, dy, dw, dbias
+# ... the strided (2, 3, 3) Conv3d family (notebook 08) takes (n, c_in, c_out, d, h, w); its horizon ConvTranspose2d takes
+# (n, h, w) after its pointers
+_DIMS6 = [c_i32] * 6
+_C3D_S2_FWD = [c_vp] * 4 + _DIMS6 + [c_i32, c_vp]                    # x, weight, bias, y, dims, relu
+_C3D_S2_BWD_DATA = [c_vp] * 5 + _DIMS6 + [c_vp]                      # dy, dy_gate, weight, dx, x_gate, dims
+_C3D_S2_BWD_WEIGHT = [c_vp] * 5 + _DIMS6 + _WORKSPACE + [c_vp]       # x, dy, dy_gate, dw, dbias, dims
+_CONVT_HORIZON_FWD = [c_vp] * 5 + [c_i32] * 3 + [c_i32, c_vp]        # x, horizon, weight, bias, y, (n, h, w), relu
+_CONVT_HORIZON_BWD_WEIGHT = [c_vp] * 6 + [c_i32] * 3 + _WORKSPACE + [c_vp]   # x, horizon, dy, dy_gate, dw, dbias, (n, h, w)
 _MSE_NORM_TAIL = [c_vp, c_vp] + _WORKSPACE + [c_vp]                  # loss, grad, workspace, stream
 
 
@@ -238,6 +246,13 @@ SIGNATURES = {
     "pv_conv3d_wide_horizon_bwd_weight_workspace_bytes": _DIMS5 + [ctypes.POINTER(c_sz)],
     "pv_conv3d_wide_horizon_bwd_weight_f32": _HORIZON_BWD_WEIGHT,
     **_conv2d_family("conv2d_head_s2p1", _WS_QUERY5),
+    "pv_conv3d_s2_fwd_f32": _C3D_S2_FWD,
+    "pv_conv3d_s2_bwd_data_f32": _C3D_S2_BWD_DATA,
+    "pv_conv3d_s2_bwd_weight_workspace_bytes": _DIMS6 + [ctypes.POINTER(c_sz)],
+    "pv_conv3d_s2_bwd_weight_f32": _C3D_S2_BWD_WEIGHT,
+    "pv_convt2d_s2_horizon_fwd_f32": _CONVT_HORIZON_FWD,
+    "pv_convt2d_s2_horizon_bwd_weight_workspace_bytes": [c_i32] * 3 + [ctypes.POINTER(c_sz)],
+    "pv_convt2d_s2_horizon_bwd_weight_f32": _CONVT_HORIZON_BWD_WEIGHT,
     "pv_maxpool3d_fwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_maxpool3d_bwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_mse_loss_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp],

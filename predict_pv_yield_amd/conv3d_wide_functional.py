@@ -1,8 +1,14 @@
-"""torch.autograd.Function wrappers over the exact-f32 (2, 3, 3) Conv3d kernels of csrc/conv3d_wide_f32.hip.
+"""torch.autograd.Function wrappers over the exact-f32 (2, 3, 3) Conv3d kernels of csrc/conv3d_wide_f32.hip and
+csrc/conv3d_s2_f32.hip.
 
 Reference operators replaced: notebooks/12_just_3d_conv.ipynb (raw lines of the .ipynb file)
     self.conv(cat(hist_images.unsqueeze(1), forecast horizon broadcast as a second channel)): nn.Sequential of Conv3d 2 -> 64
     -> 128 -> 128 -> 128 (kernel (2, 3, 3), padding (0 | 1, 1, 1)) and Conv3d 128 -> 1 (stride (1, 2, 2)), ReLU between :1397-1420
+notebooks/08_multiple_historical_images_as_separate_channels.ipynb (raw lines of the .ipynb file)
+    self.encoder_conv(hist_images.unsqueeze(1)): Conv3d 1 -> 8 -> 32 -> 32, kernel (2, 3, 3), stride (1, 2, 2), a ReLU after
+    each                                                                                                       :1365-1372, 1383-1385
+    self.decoder_conv(cat(encoder_out, forecast horizon plane)): ConvTranspose2d 33 -> 32 -> 32 stride 2 with ReLU,
+    ConvTranspose2d 32 -> 1                                                                                    :1374-1380, 1388-1392
 
 Gating follows conv2d_functional: ConvReLU (which only hands tensors to its family's three entry points, so it serves
 NCDHW tensors unchanged) lets each data gradient leave gated by the layer's input (x_is_relu_output), and the layer below then
@@ -21,6 +27,8 @@ CONV3D_WIDE_OPS = {pd: (partial(K.conv3d_wide_fwd_f32, padding=(pd, 1, 1)),
                         partial(K.conv3d_wide_bwd_data_f32, padding=(pd, 1, 1)),
                         partial(K.conv3d_wide_bwd_weight_f32, padding=(pd, 1, 1))) for pd in (0, 1)}
 CONV3D_HEAD_D2_OPS = (K.conv3d_head_d2_fwd_f32, K.conv3d_head_d2_bwd_data_f32, K.conv3d_head_d2_bwd_weight_f32)
+# notebook 08: the strided depth-2 Conv3d layers
+CONV3D_S2_OPS = (K.conv3d_s2_fwd_f32, K.conv3d_s2_bwd_data_f32, K.conv3d_s2_bwd_weight_f32)
 
 
 class HorizonConvReLU(torch.autograd.Function):
@@ -78,3 +86,58 @@ def nb12_just_3d_conv_f32(history, horizon, conv):
     y = ConvReLU.apply(CONV3D_WIDE_OPS[1], y, conv[4].weight, conv[4].bias, True, True, True)
     y = ConvReLU.apply(CONV3D_WIDE_OPS[0], y, conv[6].weight, conv[6].bias, True, True, True)
     return ConvReLU.apply(CONV3D_HEAD_D2_OPS, y, conv[8].weight, conv[8].bias, False, True, False)
+
+
+class HorizonConvTransposeReLU(torch.autograd.Function):
+    """First decoder layer of notebook 08: nn.ConvTranspose2d(33, 32, 3, stride=2) (+ ReLU) on x [N, 32, H, W] f32 plus the
+    forecast horizon [N] as a 33rd input channel, constant over the image, built inside the kernels (forward and weight
+    gradient), never stored.  The horizon has no gradient; the 32 real channels' data gradient is the plain stride-2
+    ConvTranspose2d's on the first 32 rows of the weight (contiguous, so a view)."""
+
+    @staticmethod
+    def forward(ctx, x, horizon, weight, bias, x_is_relu_output, dy_pregated):
+        x, horizon = x.contiguous(), horizon.contiguous()
+        y = K.convt2d_s2_horizon_fwd_f32(x, horizon, weight.contiguous(), bias.contiguous(), True)
+        ctx.save_for_backward(x, horizon, weight, None if dy_pregated else y)
+        ctx.x_is_relu_output = x_is_relu_output
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, horizon, weight, y = ctx.saved_tensors
+        dy, weight = dy.contiguous(), weight.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.convt2d_s2_bwd_data_f32(dy, y, weight[:K.CONVT_HORIZON_C], x if ctx.x_is_relu_output else None,
+                                           tuple(x.shape))
+        dw, db = K.convt2d_s2_horizon_bwd_weight_f32(x, horizon, dy, y, tuple(weight.shape))
+        return dx, None, dw, db, None, None
+
+
+def conv3d_s2_relu(x, weight, bias, relu=True, x_is_relu_output=False):
+    """nn.Conv3d(C_in, C_out, (2, 3, 3), stride=(1, 2, 2))(x) (+ ReLU) for (C_in, C_out) = (1, 8), (8, 32), (32, 32), planes up
+    to 128 wide.  x_is_relu_output: dx leaves gated by x > 0."""
+    return ConvReLU.apply(CONV3D_S2_OPS, x, weight, bias, bool(relu), bool(x_is_relu_output), False)
+
+
+def horizon_conv_transpose_relu(x, horizon, weight, bias, x_is_relu_output=False):
+    """relu(decoder_conv.0(cat(x, horizon plane))) of 08_...ipynb:1375-1376, 1388-1391; no gradient to the horizon."""
+    return HorizonConvTransposeReLU.apply(x, horizon, weight, bias, bool(x_is_relu_output), False)
+
+
+def nb08_hist_depth_f32(history, horizon, encoder_conv, decoder_conv):
+    """self.decoder_conv(cat(self.encoder_conv(hist_images.unsqueeze(1)) without its depth axis, horizon plane)) of
+    08_...ipynb:1382-1392; encoder_conv / decoder_conv = the notebook's two nn.Sequential (modules 0, 2, 4 nn.Conv3d /
+    nn.ConvTranspose2d; the nn.ReLU modules are fused into the layers' kernels).  history [N, 4, H, W], horizon [N] f32 -> [N,
+    1, 4 e + 5, 4 f + 5] for an encoder output of e x f.  Depth 4 -> 3 -> 2 -> 1; dropping the depth axis of size 1 and adding
+    the one of the input are views.  Every inner ReLU output has one consumer, the next layer, whose data gradient leaves gated
+    by it (x_is_relu_output), so its producer skips gating the arriving gradient (dy_pregated): no ReLU or mask kernel runs
+    on its own.  The pairing only holds inside this chain."""
+    from .conv2d_functional import CONVT2D_HEAD_OPS, CONVT2D_S2_OPS
+    enc, dec = encoder_conv, decoder_conv
+    y = ConvReLU.apply(CONV3D_S2_OPS, history.unsqueeze(1), enc[0].weight, enc[0].bias, True, False, True)
+    for i in (2, 4):
+        y = ConvReLU.apply(CONV3D_S2_OPS, y, enc[i].weight, enc[i].bias, True, True, True)
+    y = HorizonConvTransposeReLU.apply(y.squeeze(2), horizon, dec[0].weight, dec[0].bias, True, True)
+    y = ConvReLU.apply(CONVT2D_S2_OPS, y, dec[2].weight, dec[2].bias, True, True, True)
+    return ConvReLU.apply(CONVT2D_HEAD_OPS, y, dec[4].weight, dec[4].bias, False, True, False)

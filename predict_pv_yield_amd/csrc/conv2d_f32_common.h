@@ -21,8 +21,10 @@ typedef __attribute__((ext_vector_type(4))) float acc4;
 // slab groups; group g adds slabs g, g + 8, ... into four interleaved partial sums (independent loads in flight), then
 // the four and the 8 groups' results are added in index order.  dw or db may be null (that part is not written).
 // TRANSPOSED: j = ci * 9 + tap' is stored as dw[ci][co][8 - tap'] (a ConvTranspose2d's [c_in][c_out][3][3] layout).
+// DEPTH2: one depth tap of a [c_out][c_in][2][3][3] weight (dw points at the tap's first element): j = ci * 9 + tap is
+// stored as dw[co * 2 k9 + ci * 18 + tap] (instantiated by conv3d_s2_f32.hip alone).
 constexpr int kSumElems = 32, kSumGroups = kBlock / kSumElems;
-template <bool TRANSPOSED>
+template <bool TRANSPOSED, bool DEPTH2 = false>
 __global__ __launch_bounds__(kBlock) void conv2d_slab_sum_f32(const float* __restrict__ slabs, float* __restrict__ dw,
                                                               float* __restrict__ db, int c_out, int k9, int n_slabs) {
   __shared__ float part[kSumGroups][kSumElems];
@@ -47,6 +49,7 @@ __global__ __launch_bounds__(kBlock) void conv2d_slab_sum_f32(const float* __res
   if (j < k9) {
     if (!dw) return;
     if (TRANSPOSED) dw[((j / 9) * c_out + co) * 9 + 8 - j % 9] = t;
+    else if (DEPTH2) dw[co * 2 * k9 + (j / 9) * 18 + j % 9] = t;
     else dw[co * k9 + j] = t;
   } else if (db) {
     db[co] = t;
@@ -107,7 +110,7 @@ __device__ __forceinline__ float pool3_expand(const float* dyp, const uint8_t* c
 
 // What a pass reads, by source kind.  Each file's first layer synthesises its input while staging (its own load_in /
 // stage_in arm); the other two kinds are the same everywhere.
-enum Src { SRC_PLAIN, SRC_POOLED, SRC_SAT, SRC_COUNTS };
+enum Src { SRC_PLAIN, SRC_POOLED, SRC_SAT, SRC_COUNTS, SRC_DEPTH, SRC_HORIZON };
 
 struct In {
   // SRC_PLAIN: x[n][c_in][h][w], zeroed where gate <= 0 (gate may be null)
@@ -115,6 +118,9 @@ struct In {
   // SRC_SAT: satellite frames behind x plus centre marker, geo x, geo y, pixel x, pixel y: experiments/001 reads sat[b]
   //          [t_total][h][w] frames 0..n_frames-1, experiments/002 sat[n][h][w][12] with n / t_per_ex the coords' example
   // SRC_COUNTS: x = history [n][4][h][w], flow [n][h][w] (int16 where *_i16, else f32 counts), horizon [n]: 6 channels
+  // SRC_DEPTH: x[b][c_in][t_total][h][w] read one depth slice at a time: the pass's image index is (b, z) = (i / n_frames,
+  //            i % n_frames) and channel ch is the plane (ch, z + t_per_ex); zeroed where gate <= 0 (gate may be null)
+  // SRC_HORIZON: x[n][c_in - 1][h][w], then horizon[n] as a constant last channel
   const float* x;
   const float* gate;
   const uint8_t* codes;    // SRC_POOLED: [n][c_in][ph][pw]

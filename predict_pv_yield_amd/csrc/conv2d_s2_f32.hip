@@ -25,13 +25,12 @@
 //      conv2d_slab_sum_f32: no atomics, identical bits run to run.
 // First layer: load_in<SRC_COUNTS> of conv2d_counts_f32.h, as in conv2d_ae_f32.hip.
 #include "conv2d_counts_f32.h"
+#include "conv2d_s2_plan_f32.h"
 
 namespace pv {
 namespace {
 
 constexpr int kMaxWidth = 128, kMinCountsSide = 31;   // 31 -> 15 -> 7 -> 3 -> 1: the smallest image four layers accept
-
-inline int conv_out(int s) { return (s - 3) / 2 + 1; }
 
 // B.  Block = (image, row band, column band) of tr x tc class-grid positions = up to 2 tr x 2 tc outputs.  The source rows
 // [a0 - 1, a0 + tr) and columns [b0 - 1, b0 + tc) are staged as lds[ch][tr + 1][tc + 1] (zero outside the source).  The
@@ -104,32 +103,6 @@ __global__ __launch_bounds__(kBlock) void conv2d_s2_scatter(Fwd a) {
   scatter_class<CINP, MT, 1, 1>(a, lds, wa, n, a0, b0, cs, sw, first_tile);
 }
 
-// The ConvTranspose2d bias gradient's slabs: block s adds dy (zeroed where the gate <= 0) over the planes of its images,
-// channel by channel: strided partial sums per thread, then a tree sum in LDS (fixed order).  slabs [n_slabs][c][1].
-__global__ __launch_bounds__(kBlock) void plane_sum_slabs_f32(const float* __restrict__ dy, const float* __restrict__ gate,
-                                                             float* __restrict__ slabs, int n, int per, int c, int plane) {
-  __shared__ float part[kBlock];
-  const int n0 = blockIdx.x * per, n1 = min(n0 + per, n);
-  for (int ch = 0; ch < c; ++ch) {
-    float s = 0.0f;
-    for (int img = n0; img < n1; ++img) {
-      const size_t base = ((size_t)img * c + ch) * plane;
-      for (int i = threadIdx.x; i < plane; i += kBlock) {
-        const float v = dy[base + i];
-        s += (gate && !(gate[base + i] > 0.0f)) ? 0.0f : v;
-      }
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int k = kBlock / 2; k > 0; k >>= 1) {
-      if ((int)threadIdx.x < k) part[threadIdx.x] += part[threadIdx.x + k];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) slabs[(size_t)blockIdx.x * c + ch] = part[0];
-    __syncthreads();
-  }
-}
-
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
 // A: at most 64 output columns per band (input tile up to 129 wide), bands of equal width; rows: the staged (2 tr + 1) x (2
@@ -184,28 +157,6 @@ Fwd gather_args(const float* w, const float* bias, float* y, int c, int m_out, i
   return a;
 }
 
-// C: (h_out, w_out) = the positions the sum runs over, rows = the D rows, c = the sliding operand's channels.  Among column
-// splits, the largest tile that fits 64 KB and 384 positions with the smallest staged area per position.
-WgPlan wg_plan_s2(int n, int c, int rows, int h_out, int w_out) {
-  WgPlan p = {};
-  p.h_out = h_out, p.w_out = w_out, p.cinp = (c + 3) & ~3, p.mt = (rows + 15) / 16;
-  double best = 1e30;
-  const int cb0 = (w_out + 63) / 64;
-  for (int n_cb = cb0; n_cb <= cb0 + 3 && n_cb <= w_out; ++n_cb) {
-    const int tc = (w_out + n_cb - 1) / n_cb;
-    int tr = 0;
-    while (tr < h_out && (tr + 1) * tc <= 384 && wg_lds_floats(p.cinp, p.mt, tr + 1, tc, 2) <= (size_t)kLdsFloats) ++tr;
-    if (tr == 0) continue;
-    const int n_rb = (h_out + tr - 1) / tr;
-    tr = (h_out + n_rb - 1) / n_rb;
-    const double cost = (double)(2 * tr + 1) * (2 * tc + 1) / ((double)tr * tc);
-    if (cost < best) best = cost, p.tr = tr, p.tc = tc, p.n_rb = n_rb, p.n_cb = (w_out + tc - 1) / tc;
-  }
-  if (p.tr == 0) p.tr = 1, p.tc = std::min(w_out, 8), p.n_rb = h_out, p.n_cb = (w_out + p.tc - 1) / p.tc;
-  slab_split(p, n, c, rows, 2);
-  return p;
-}
-
 template <int XSRC>
 int run_wgrad_s2(const char* who, const In& in, const In& g, const WgPlan& p, float* dw, float* db, void* ws, size_t ws_bytes,
                  hipStream_t st) {
@@ -248,15 +199,6 @@ int check_s2(const char* who, int n, int c_in, int c_out, int h_in, int w_in, Ki
                "%s: unsupported channel counts c_in=%d c_out=%d (16 -> 32 or 32 -> 32)", who, c_in, c_out);
   }
   return PV_OK;
-}
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// the bias slabs of a ConvTranspose2d weight gradient: one per group of `per` images, at most kMaxSlabs
-void bias_slabs(int n, int& n_slabs, int& per) {
-  const int want = std::min(n, kMaxSlabs);
-  per = (n + want - 1) / want;
-  n_slabs = (n + per - 1) / per;
 }
 
 }  // namespace

@@ -5,7 +5,8 @@
 // conv2d_f32.hip (experiments/002: full-width bands of rows, tc = w_out), conv2d_ae_f32.hip (notebooks/16_maxpool: tiles of
 // at most 64 columns) and conv2d_s2_f32.hip (notebooks 14 / 15: the same two GEMMs at stride 2, STRIDE = 2, the tile staged
 // split by column parity) instantiate them; each keeps its tile planner, its argument checks and its first layer's source
-// kind.  A forward-like output element's sum depends only on the (tap, channel group) order, not on the tile it
+// kind.  conv3d_s2_f32.hip (notebook 08) instantiates the stride-2 weight gradient over depth slices of NCDHW tensors
+// (SRC_DEPTH) and keeps forward-like kernels of its own, which run one K pass per depth tap.  A forward-like output element's sum depends only on the (tap, channel group) order, not on the tile it
 // falls in; the weight gradient's bits depend on the row-major position order inside an item, the items per slab and the
 // slab order (fixed slabs, each block writing its own, added in slab order: no atomics, identical bits run to run).
 #pragma once

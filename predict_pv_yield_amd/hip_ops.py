@@ -2084,6 +2084,121 @@ def conv3d_head_d2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
     return dw.view(tuple(weight_shape)), db
 
 
+# ---- notebooks/08_multiple_historical_images_as_separate_channels.ipynb: Conv3d 1 -> 8 -> 32 -> 32, kernel (2, 3, 3), stride
+# (1, 2, 2), no padding, then ConvTranspose2d 33 -> 32 whose last input channel is the forecast horizon
+# (csrc/conv3d_s2_f32.hip); planes up to 128 wide.  As for notebook 12, the depth axis does not fit a _ConvFamily record: the
+# family's one shape rule is _check_conv3d_s2. ----
+CONV3D_S2_PAIRS = ((1, 8), (8, 32), (32, 32))     # (c_in, c_out) of pv_conv3d_s2_*
+CONVT_HORIZON_C = 32                              # real input channels = output channels of pv_convt2d_s2_horizon_*
+
+
+def _check_conv3d_s2(who, x_shape, weight_shape):
+    """The shape rule of pv_conv3d_s2_*: x [N, C_in, D, H, W], weight [C_out, C_in, 2, 3, 3].  Returns the entry points' (n,
+    c_in, c_out, d, h, w) and the output's shape."""
+    if not (len(x_shape) == 5 and len(weight_shape) == 5 and tuple(weight_shape[1:]) == (x_shape[1], 2, 3, 3)):
+        raise ValueError(f"{who}: x [N, C_in, D, H, W] and weight [C_out, C_in, 2, 3, 3] expected, got {tuple(x_shape)} / "
+                         f"{tuple(weight_shape)}")
+    n, ci, d, h, w = (int(v) for v in x_shape)
+    co = int(weight_shape[0])
+    if (ci, co) not in CONV3D_S2_PAIRS:
+        raise ValueError(f"{who}: (C_in, C_out) = (1, 8), (8, 32) or (32, 32) expected, got ({ci}, {co})")
+    if d < 2 or min(h, w) < 3 or w > WIDE_MAX_W:
+        raise ValueError(f"{who}: at least two slices and planes of 3 to {WIDE_MAX_W} columns expected, got {tuple(x_shape)}")
+    return (n, ci, co, d, h, w), (n, co, d - 1, s2_out(h), s2_out(w))
+
+
+def conv3d_s2_fwd_f32(x, weight, bias, relu=True):
+    """conv3d(x, weight, stride (1, 2, 2)) + bias (+ ReLU): [N, C_in, D, H, W] f32 -> [N, C_out, D - 1, (H - 3) // 2 + 1, (W - 3)
+    // 2 + 1]; weight [C_out, C_in, 2, 3, 3]."""
+    who = "conv3d_s2_fwd_f32"
+    dims, y_shape = _check_conv3d_s2(who, x.shape, weight.shape)
+    _check_bias(who, bias, dims[2])
+    require_cuda(x, weight, bias)
+    _f32_contig(x, weight, bias)
+    y = torch.empty(y_shape, dtype=torch.float32, device=x.device)
+    check(get_lib().pv_conv3d_s2_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), *dims, int(relu), current_stream_ptr()),
+          "pv_" + who)
+    return y
+
+
+def conv3d_s2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of conv3d_s2_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None).  The rows and
+    columns of x the forward never reads are written as 0.  The 1 -> 8 layer has no data gradient."""
+    who = "conv3d_s2_bwd_data_f32"
+    dims, y_shape = _check_conv3d_s2(who, x_shape, weight.shape)
+    if dims[1] == 1:
+        raise ValueError(f"{who}: the (1, 8) layer is the first one and has no data gradient")
+    if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
+        raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    if x_gate is not None and tuple(x_gate.shape) != tuple(x_shape):
+        raise ValueError(f"{who}: x_gate {tuple(x_shape)} expected")
+    require_cuda(dy, dy_gate, weight, x_gate)
+    _f32_contig(dy, dy_gate, weight, x_gate)
+    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
+    check(get_lib().pv_conv3d_s2_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), *dims,
+                                              current_stream_ptr()), "pv_" + who)
+    return dx
+
+
+def conv3d_s2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw, dbias) of conv3d_s2_fwd_f32; deterministic (fixed slabs summed in order)."""
+    who = "conv3d_s2_bwd_weight_f32"
+    dims, y_shape = _check_conv3d_s2(who, x.shape, weight_shape)
+    if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
+        raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    require_cuda(x, dy, dy_gate)
+    _f32_contig(x, dy, dy_gate)
+    ws, nbytes = _wgrad_ws("conv3d_s2", x.device, *dims)
+    dw, db = _grads_out(weight_shape, dims[2], x.device)
+    check(get_lib().pv_conv3d_s2_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), *dims, ptr(ws), nbytes,
+                                                current_stream_ptr()), "pv_" + who)
+    return dw, db
+
+
+def _check_convt_horizon(who, x, horizon, weight_shape):
+    c = CONVT_HORIZON_C
+    if x.dim() != 4 or x.shape[1] != c or tuple(weight_shape) != (c + 1, c, 3, 3):
+        raise ValueError(f"{who}: x [N, {c}, H, W] and weight [{c + 1}, {c}, 3, 3] expected, got {tuple(x.shape)} / "
+                         f"{tuple(weight_shape)}")
+    n, _, h, w = (int(v) for v in x.shape)
+    if tuple(horizon.shape) != (n,):
+        raise ValueError(f"{who}: horizon [{n}] expected, got {tuple(horizon.shape)}")
+    if min(h, w) < 1 or 2 * w + 1 > WIDE_MAX_W:
+        raise ValueError(f"{who}: a non-empty plane whose output is at most {WIDE_MAX_W} columns wide expected, got {h} x {w}")
+    return n, h, w
+
+
+def convt2d_s2_horizon_fwd_f32(x, horizon, weight, bias, relu=True):
+    """conv_transpose2d(cat(x, horizon plane), weight, stride 2) + bias (+ ReLU): x [N, 32, H, W] f32, input channel 32 of
+    example i is horizon[i] everywhere -> [N, 32, 2 H + 1, 2 W + 1]; weight [33, 32, 3, 3]."""
+    who = "convt2d_s2_horizon_fwd_f32"
+    n, h, w = _check_convt_horizon(who, x, horizon, weight.shape)
+    _check_bias(who, bias, CONVT_HORIZON_C)
+    require_cuda(x, horizon, weight, bias)
+    _f32_contig(x, horizon, weight, bias)
+    y = torch.empty((n, CONVT_HORIZON_C, 2 * h + 1, 2 * w + 1), dtype=torch.float32, device=x.device)
+    check(get_lib().pv_convt2d_s2_horizon_fwd_f32(ptr(x), ptr(horizon), ptr(weight), ptr(bias), ptr(y), n, h, w, int(relu),
+                                                  current_stream_ptr()), "pv_" + who)
+    return y
+
+
+def convt2d_s2_horizon_bwd_weight_f32(x, horizon, dy, dy_gate, weight_shape):
+    """(dw [33, 32, 3, 3], dbias [32]) of convt2d_s2_horizon_fwd_f32; dy zeroed where dy_gate <= 0 (may be None);
+    deterministic.  The data gradient of the 32 real channels is convt2d_s2_bwd_data_f32 on weight[:32]."""
+    who = "convt2d_s2_horizon_bwd_weight_f32"
+    n, h, w = _check_convt_horizon(who, x, horizon, weight_shape)
+    y_shape = (n, CONVT_HORIZON_C, 2 * h + 1, 2 * w + 1)
+    if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
+        raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
+    require_cuda(x, horizon, dy, dy_gate)
+    _f32_contig(x, horizon, dy, dy_gate)
+    ws, nbytes = _wgrad_ws("convt2d_s2_horizon", x.device, n, h, w)
+    dw, db = _grads_out(weight_shape, CONVT_HORIZON_C, x.device)
+    check(get_lib().pv_convt2d_s2_horizon_bwd_weight_f32(ptr(x), ptr(horizon), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, h, w,
+                                                         ptr(ws), nbytes, current_stream_ptr()), "pv_" + who)
+    return dw, db
+
+
 def maxpool3d_fwd_f32(x, kernel=3, stride=None, padding=0):
     require_cuda(x)
     b, c, t, h, w = x.shape

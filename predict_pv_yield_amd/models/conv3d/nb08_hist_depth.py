@@ -1,0 +1,125 @@
+"""LitAutoEncoder of the strided depth-2 Conv3d encoder / ConvTranspose2d decoder -- host-side mirror of
+notebooks/08_multiple_historical_images_as_separate_channels.ipynb (the cell that defines LitAutoEncoder with STRIDE = (1, 2,
+2), KERNEL_SIZE = (2, 3, 3), CHANNELS = 32, N_HIST_IMAGES = 4, raw lines 1356-1411 of the .ipynb file; the three nn.Conv3d at
+1366-1370, the three nn.ConvTranspose2d at 1375-1379).
+
+  input  x[HISTORICAL_SAT_IMAGES]  [B, 4, H, W]   float32, normalised by the loader (H = W = 128 in the notebook)
+         x[FORECAST_HORIZON]       [B]            float32, normalised by the loader
+         x[TARGET_SAT_IMAGE]       [B, h_t, w_t]  float32, normalised; (h_t, w_t) == the output's sides - 1 (H = 128: 64)
+  graph  the four history frames are the depth axis of one input channel: [B, 1, 4, H, W];
+         encoder_conv = Sequential(Conv3d 1 -> 8, ReLU, Conv3d 8 -> 32, ReLU, Conv3d 32 -> 32, ReLU), all kernel (2, 3, 3),
+         stride (1, 2, 2), no padding: depth 4 -> 3 -> 2 -> 1, a side s becomes (s - 3) // 2 + 1 three times (128 -> 63 -> 31
+         -> 15); the depth axis of size 1 is dropped and the horizon joins as a 33rd, constant channel;
+         decoder_conv = Sequential(ConvTranspose2d 33 -> 32 stride 2, ReLU, ConvTranspose2d 32 -> 32 stride 2, ReLU,
+         ConvTranspose2d 32 -> 1 stride 1): e -> 2 e + 1 -> 4 e + 3 -> 4 e + 5 (15 -> 31 -> 63 -> 65)
+  loss   F.mse_loss(y_hat[:, :, :-1, :-1], target.unsqueeze(1)): the prediction is cropped, not the target; Adam(lr=1e-3)
+
+Same attribute / state_dict names as the notebook (encoder_conv.{0,2,4}.{weight,bias}, decoder_conv.{0,2,4}.{weight,bias};
+42 329 parameters).  The two nn.Sequential are parameter holders: every layer, the loss and the optimiser run on the gfx950
+kernels behind include/pv_yield_hip.h (pv_conv3d_s2_*, pv_convt2d_s2_horizon_*, pv_convt2d_s2_*, pv_convt2d_head_*,
+pv_mse_pred_window_f32, pv_adam_step_f32).  The 33-channel decoder input is never stored: the first decoder layer's kernels
+read the horizon of each example from device memory, so a step can be captured as a graph.  Deliberate differences from the
+notebook: it runs on the MI355X only (CPU tensors raise a RuntimeError); a target whose sides are not the output's minus one
+raises a ValueError where torch would broadcast or fail inside mse_loss; and the batch axis survives B = 1 (the notebook's
+encoder_out.squeeze_() drops it together with the depth axis, after which torch.cat fails).
+"""
+import torch
+from torch import nn
+
+from ... import lightning as pl
+from .flow_autoencoder import FORECAST_HORIZON, HISTORICAL_SAT_IMAGES, TARGET_SAT_IMAGE  # noqa: F401
+
+STRIDE = (1, 2, 2)  # depth, height, width
+KERNEL_SIZE = (2, 3, 3)  # depth, height, width
+CHANNELS = 32
+N_HIST_IMAGES = 4
+MIN_IMAGE_SIDE = 15           # 15 -> 7 -> 3 -> 1: the smallest side three 3x3 stride-2 convolutions accept
+MAX_IMAGE_SIDE = 128          # the kernels' widest plane
+
+
+def output_side(image_side: int) -> int:
+    """Side of y_hat for an input side (128 -> 65, 31 -> 17, 15 -> 9)."""
+    if not MIN_IMAGE_SIDE <= image_side <= MAX_IMAGE_SIDE:
+        raise ValueError(f"nb08 LitAutoEncoder needs images of {MIN_IMAGE_SIDE} to {MAX_IMAGE_SIDE} pixels a side (three 3x3 "
+                         f"stride-2 convolutions; planes up to {MAX_IMAGE_SIDE} wide), got {image_side}")
+    side = image_side
+    for _ in range(3):
+        side = (side - 3) // 2 + 1
+    return 4 * side + 5       # two ConvTranspose2d at stride 2 (s -> 2 s + 1), one at stride 1 (s -> s + 2)
+
+
+def target_side(image_side: int) -> int:
+    """Side of the target the loss accepts: y_hat[:, :, :-1, :-1] drops the prediction's last row and column."""
+    return output_side(image_side) - 1
+
+
+def check_target_side(image_shape, target_shape) -> None:
+    """image_shape: (H, W) of the history images; the target must be [B, target_side(H), target_side(W)]."""
+    want = tuple(target_side(int(side)) for side in image_shape)
+    if len(target_shape) != 3 or tuple(target_shape[1:]) != want:
+        raise ValueError(f"nb08 LitAutoEncoder: TARGET_SAT_IMAGE must be [B, {want[0]}, {want[1]}] for {image_shape[0]} x "
+                         f"{image_shape[1]}-pixel inputs, got {tuple(target_shape)}")
+
+
+class LitAutoEncoder(pl.LightningModule):
+    name = "nb08_hist_depth"
+
+    def __init__(self, lr: float = 0.001):
+        super().__init__()
+        self.lr = float(lr)
+
+        self.encoder_conv = nn.Sequential(
+            nn.Conv3d(in_channels=1, out_channels=CHANNELS // 4, kernel_size=KERNEL_SIZE, stride=STRIDE),
+            nn.ReLU(),
+            nn.Conv3d(in_channels=CHANNELS // 4, out_channels=CHANNELS, kernel_size=KERNEL_SIZE, stride=STRIDE),
+            nn.ReLU(),
+            nn.Conv3d(in_channels=CHANNELS, out_channels=CHANNELS, kernel_size=KERNEL_SIZE, stride=STRIDE),
+            nn.ReLU(),
+        )
+
+        self.decoder_conv = nn.Sequential(
+            nn.ConvTranspose2d(in_channels=CHANNELS + 1, out_channels=CHANNELS, kernel_size=3, stride=2),
+            nn.ReLU(),
+            nn.ConvTranspose2d(in_channels=CHANNELS, out_channels=CHANNELS, kernel_size=3, stride=2),
+            nn.ReLU(),
+            nn.ConvTranspose2d(in_channels=CHANNELS, out_channels=1, kernel_size=3, stride=1),
+        )
+
+    def forward(self, x):
+        from ...conv3d_wide_functional import nb08_hist_depth_f32
+        hist_images, horizon = x[HISTORICAL_SAT_IMAGES], x[FORECAST_HORIZON]
+        if hist_images.dim() != 4 or hist_images.shape[1] != N_HIST_IMAGES:
+            raise ValueError(f"nb08 LitAutoEncoder takes HISTORICAL_SAT_IMAGES [B, {N_HIST_IMAGES}, H, W], got "
+                             f"{tuple(hist_images.shape)}")
+        if not hist_images.is_cuda:
+            raise RuntimeError("predict_pv_yield_amd LitAutoEncoder runs on the MI355X only: move the module and the "
+                               "batch to cuda (there is no CPU fallback)")
+        for side in hist_images.shape[2:]:
+            output_side(int(side))
+        horizon = horizon.to(device=hist_images.device, dtype=torch.float32).reshape(-1)
+        if horizon.shape[0] != hist_images.shape[0]:
+            raise ValueError(f"nb08 LitAutoEncoder takes FORECAST_HORIZON [B], got {tuple(x[FORECAST_HORIZON].shape)} for "
+                             f"{hist_images.shape[0]} examples")
+        # the horizon channel is synthesised by the first decoder layer's kernels from one value per example
+        return nb08_hist_depth_f32(hist_images.float(), horizon, self.encoder_conv, self.decoder_conv)
+
+    def _training_or_validation_step(self, batch, is_train_step):
+        from ...conv2d_functional import mse_pred_window
+        y = batch[TARGET_SAT_IMAGE]
+        check_target_side(tuple(batch[HISTORICAL_SAT_IMAGES].shape[-2:]), y.shape)
+        y_hat = self(batch)
+        # y_hat[:, :, :-1, :-1] against the target: the window of the prediction that starts at (0, 0)
+        loss = mse_pred_window(y_hat.squeeze(1), y.to(device=y_hat.device, dtype=torch.float32), 0, 0)
+        tag = "Loss/Train" if is_train_step else "Loss/Validation"
+        self.log_dict({tag: loss}, on_step=is_train_step, on_epoch=True)
+        return loss
+
+    def training_step(self, batch, batch_idx):
+        return self._training_or_validation_step(batch, is_train_step=True)
+
+    def validation_step(self, batch, batch_idx):
+        return self._training_or_validation_step(batch, is_train_step=False)
+
+    def configure_optimizers(self):
+        from ...optim import HipAdam
+        return HipAdam(self.parameters(), lr=self.lr)

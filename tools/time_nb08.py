@@ -1,0 +1,199 @@
+"""Train-step time of notebooks/08_multiple_historical_images_as_separate_channels.ipynb's LitAutoEncoder (B x 4 x 128 x 128
+normalised frames as the depth axis of Conv3d 1 -> 8 -> 32 -> 32, kernel (2, 3, 3), stride (1, 2, 2); the horizon as the 33rd
+channel of ConvTranspose2d 33 -> 32 -> 32 -> 1), eager and replayed as a HIP graph, and the device time of every conv launch of
+the step.  The yardstick, in the same process and on the same device, is the general Conv3d f32 route
+(pv_conv3d_general_{fwd,bwd_data,bwd_weight}_f32) on the same launch: the Conv3d layers as they stand; a ConvTranspose2d
+layer as the Conv2d it transposes, as a (1, 3, 3) Conv3d at depth 1 (its forward is that conv's data gradient, its data
+gradient that conv's forward, its weight gradient that conv's with the operands swapped; the bias gradient is not part of
+the general route's launch there, and the horizon layer's 33-channel input is materialised outside the timing).  torch's own
+kernels are timed alongside for information only: the package never calls them.
+Warm-up first, device-side event timing of INNER back-to-back calls per sample, the median of REPS alternating samples (ours,
+general, torch, ours, ...), inputs resident before the timed region; the samples' min and max are kept as the spread.  Prints
+a table and one JSON line.
+   python tools/time_nb08.py [batch=64] [reps=7]"""
+import json, os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+import torch.nn.functional as F
+from predict_pv_yield_amd import hip_ops as K
+from predict_pv_yield_amd.graphs import GraphedTrainStep
+from predict_pv_yield_amd.models.conv3d.nb08_hist_depth import LitAutoEncoder, target_side
+from predict_pv_yield_amd.optim import HipAdam
+
+dev = torch.device("cuda:0")
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 7
+S = 128
+T = target_side(S)
+INNER = 2                # back-to-back calls per event pair
+ST = (1, 2, 2)
+
+g = torch.Generator().manual_seed(1)
+batch = {"HISTORICAL_SAT_IMAGES": torch.randn(B, 4, S, S, generator=g).to(dev),
+         "FORECAST_HORIZON": ((torch.randint(1, 25, (B,), generator=g).float() - 12.5) / 6.9222).to(dev),
+         "TARGET_SAT_IMAGE": torch.randn(B, T, T, generator=g).to(dev)}
+
+# ---- the train step ------------------------------------------------------------------------------------------------
+torch.manual_seed(0)
+model = LitAutoEncoder().to(dev)
+opt = model.configure_optimizers()
+
+
+def step():
+    opt.zero_grad(set_to_none=True)
+    model.training_step(batch, 0).backward()
+    opt.step()
+
+
+def wall(fn):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(REPS):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / REPS
+
+
+eager = wall(step)
+torch.manual_seed(0)
+gmodel = LitAutoEncoder().to(dev)
+gopt = HipAdam(gmodel.parameters(), lr=0.001, capturable=True)
+graphed = GraphedTrainStep(gmodel, gopt, batch, warmup=2)
+replay = wall(lambda: graphed(batch))
+graphed.close()
+del gmodel, gopt, graphed
+print(f"nb08 LitAutoEncoder B={B} {S}x{S}: eager {eager * 1e3:.3f} ms/step ({B / eager:.1f} samples/s), HIP graph "
+      f"{replay * 1e3:.3f} ms/step ({B / replay:.1f} samples/s)", flush=True)
+
+# ---- every conv launch of the step -------------------------------------------------------------------------------------
+hist, horizon = batch["HISTORICAL_SAT_IMAGES"].unsqueeze(1).contiguous(), batch["FORECAST_HORIZON"]
+P = lambda seq, i: (seq[i].weight.detach().contiguous(), seq[i].bias.detach().contiguous())      # noqa: E731
+(we0, be0), (we2, be2), (we4, be4) = (P(model.encoder_conv, i) for i in (0, 2, 4))
+(wd0, bd0), (wd2, bd2), (wd4, bd4) = (P(model.decoder_conv, i) for i in (0, 2, 4))
+e0 = K.conv3d_s2_fwd_f32(hist, we0, be0)
+e2 = K.conv3d_s2_fwd_f32(e0, we2, be2)
+e4 = K.conv3d_s2_fwd_f32(e2, we4, be4)
+enc = e4.squeeze(2).contiguous()
+d0 = K.convt2d_s2_horizon_fwd_f32(enc, horizon, wd0, bd0)
+d2 = K.convt2d_s2_fwd_f32(d0, wd2, bd2)
+d4 = K.convt2d_head_fwd_f32(d2, wd4, bd4)
+rnd = lambda t: torch.randn(t.shape, generator=g).to(dev)      # noqa: E731
+dy_e0, dy_e2, dy_e4, dy_d0, dy_d2, dy_d4 = (rnd(t) for t in (e0, e2, e4, d0, d2, d4))
+enc33 = torch.cat((enc, horizon.view(-1, 1, 1, 1).expand(B, 1, *enc.shape[2:])), 1).contiguous()
+zeros = lambda n: torch.zeros(n, device=dev)      # noqa: E731
+u = lambda t: t.unsqueeze(2)      # noqa: E731  NCHW as NCDHW of depth 1 (a view)
+
+
+def conv3d_rows(name, x, w, b, dy, first=False):
+    """(name, GFLOP, ours, general, torch) of one strided Conv3d layer's launches."""
+    gf = 2 * dy.numel() * w[0].numel() / 1e9
+    rows = [(f"{name} fwd", gf, lambda: K.conv3d_s2_fwd_f32(x, w, b),
+             lambda: K.conv3d_general_fwd_f32(x, w, b, stride=ST, relu=True), lambda: F.conv3d(x, w, b, stride=ST))]
+    if not first:
+        rows.append((f"{name} dgrad", gf, lambda: K.conv3d_s2_bwd_data_f32(dy, None, w, x, tuple(x.shape)),
+                     lambda: K.conv3d_general_bwd_data_f32(dy, None, w, tuple(x.shape), stride=ST, x_mask=x),
+                     lambda: torch.nn.grad.conv3d_input(tuple(x.shape), w, dy, stride=ST)))
+    rows.append((f"{name} wgrad + db", gf, lambda: K.conv3d_s2_bwd_weight_f32(x, dy, None, tuple(w.shape)),
+                 lambda: K.conv3d_general_bwd_weight_f32(x, dy, None, tuple(w.shape), stride=ST),
+                 lambda: torch.nn.grad.conv3d_weight(x, tuple(w.shape), dy, stride=ST)))
+    return rows
+
+
+def convt_rows(name, x, x_full, w, b, dy, stride, ours_fwd, ours_dgrad, ours_wgrad):
+    """... of one ConvTranspose2d layer: the general route runs the Conv2d it transposes (x_full: the input with every channel
+    materialised; w [c_in][c_out][3][3] is that conv's [c_out'][c_in'][3][3] as it stands)."""
+    gf = 2 * x_full.numel() * w[0].numel() / 1e9
+    w5, st3 = w.unsqueeze(2), (1, stride, stride)
+    rows = [(f"{name} fwd", gf, ours_fwd,
+             lambda: K.conv3d_general_bwd_data_f32(u(x_full), None, w5, tuple(u(dy).shape), stride=st3),
+             lambda: F.conv_transpose2d(x_full, w, b, stride=stride))]
+    if ours_dgrad is not None:
+        rows.append((f"{name} dgrad", gf, ours_dgrad,
+                     lambda: K.conv3d_general_fwd_f32(u(dy), w5, None, stride=st3),
+                     lambda: F.conv2d(dy, w, stride=stride)))
+    rows.append((f"{name} wgrad + db", gf, ours_wgrad,
+                 lambda: K.conv3d_general_bwd_weight_f32(u(dy), u(x_full), None, tuple(w5.shape), stride=st3, need_bias=False),
+                 lambda: torch.nn.grad.conv2d_weight(dy, tuple(w.shape), x_full, stride=stride)))
+    return rows
+
+
+cases = []
+cases += conv3d_rows("encoder_conv.0 1->8", hist, we0, be0, dy_e0, first=True)
+cases += conv3d_rows("encoder_conv.2 8->32", e0, we2, be2, dy_e2)
+cases += conv3d_rows("encoder_conv.4 32->32", e2, we4, be4, dy_e4)
+cases += convt_rows("decoder_conv.0 33->32 s2 (horizon synthesised)", enc, enc33, wd0, bd0, dy_d0, 2,
+                    lambda: K.convt2d_s2_horizon_fwd_f32(enc, horizon, wd0, bd0),
+                    lambda: K.convt2d_s2_bwd_data_f32(dy_d0, None, wd0[:32], enc, tuple(enc.shape)),
+                    lambda: K.convt2d_s2_horizon_bwd_weight_f32(enc, horizon, dy_d0, None, tuple(wd0.shape)))
+NEW = len(cases)      # the launches above run this pull request's kernels; the two layers below are the existing families
+cases += convt_rows("decoder_conv.2 32->32 s2", d0, d0, wd2, bd2, dy_d2, 2,
+                    lambda: K.convt2d_s2_fwd_f32(d0, wd2, bd2),
+                    lambda: K.convt2d_s2_bwd_data_f32(dy_d2, None, wd2, d0, tuple(d0.shape)),
+                    lambda: K.convt2d_s2_bwd_weight_f32(d0, dy_d2, None, tuple(wd2.shape)))
+cases += convt_rows("decoder_conv.4 32->1 s1 (head)", d2, d2, wd4, bd4, dy_d4, 1,
+                    lambda: K.convt2d_head_fwd_f32(d2, wd4, bd4),
+                    lambda: K.convt2d_head_bwd_data_f32(dy_d4, None, wd4, d2, tuple(d2.shape)),
+                    lambda: K.convt2d_head_bwd_weight_f32(d2, dy_d4, None, tuple(wd4.shape)))
+
+
+def device_ms(fn):
+    e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0_.record()
+    for _ in range(INNER):
+        fn()
+    e1_.record()
+    e1_.synchronize()
+    return e0_.elapsed_time(e1_) / INNER
+
+
+def usable(fn, what):
+    try:
+        fn()
+        torch.cuda.synchronize()
+        return True
+    except Exception as e:            # a route that does not take a shape is reported, not timed
+        print(f"{what}: {type(e).__name__}: {str(e)[:200]}")
+        return False
+
+
+med = lambda v: sorted(v)[len(v) // 2] if v else float("nan")      # noqa: E731
+r4 = lambda v: round(v, 4) if v == v else None      # noqa: E731
+rows_out, ratios = [], {}
+tot = {"ours": 0.0, "general": 0.0, "torch": 0.0, "gflop": 0.0}
+print(f"{'launch':58s} {'GFLOP':>7s} {'ours ms':>8s} {'spread':>15s} {'general ms':>10s} {'spread':>15s} {'ours/gen':>8s} "
+      f"{'torch ms':>9s}")
+for i, (name, gflop, ours, general, torch_fn) in enumerate(cases):
+    for _ in range(2):
+        ours()
+    ok_g, ok_t = usable(general, f"{name}: general route"), usable(torch_fn, f"{name}: torch")
+    ta, tg, tt = [], [], []
+    for _ in range(REPS):     # alternate the three
+        ta.append(device_ms(ours))
+        if ok_g:
+            tg.append(device_ms(general))
+        if ok_t:
+            tt.append(device_ms(torch_fn))
+    ma, mg, mt = med(ta), med(tg), med(tt)
+    tot["ours"] += ma
+    tot["general"] += mg if ok_g else 0.0
+    tot["torch"] += mt if ok_t else 0.0
+    tot["gflop"] += gflop
+    if ok_g:
+        ratios[name] = round(ma / mg, 4)
+    rows_out.append({"launch": name, "new_kernel": i < NEW, "gflop": round(gflop, 4), "ours_ms": r4(ma), "ours_ms_min": r4(min(ta)),
+                     "ours_ms_max": r4(max(ta)), "general_ms": r4(mg), "general_ms_min": r4(min(tg)) if tg else None,
+                     "general_ms_max": r4(max(tg)) if tg else None, "ours_over_general": ratios.get(name),
+                     "torch_ms": r4(mt)})
+    gs = f"{min(tg):7.3f}-{max(tg):7.3f}" if tg else f"{'':15s}"
+    print(f"{name:58s} {gflop:7.3f} {ma:8.3f} {min(ta):7.3f}-{max(ta):7.3f} {mg:10.3f} {gs} {ma / mg if ok_g else float('nan'):8.3f} "
+          f"{mt:9.3f}", flush=True)
+
+print(f"{'conv launches of a step (median each, summed)':58s} {tot['gflop']:7.3f} {tot['ours']:8.3f} {'':15s} "
+      f"{tot['general']:10.3f} {'':15s} {tot['ours'] / tot['general']:8.3f} {tot['torch']:9.3f}")
+print(json.dumps({"tool": "time_nb08", "batch": B, "image": S, "reps": REPS, "calls_per_sample": INNER,
+                  "eager_ms": round(eager * 1e3, 4), "graph_ms": round(replay * 1e3, 4),
+                  "samples_per_s_graph": round(B / replay, 2), "step_gflop": round(tot["gflop"], 3),
+                  "launches_ours_ms": round(tot["ours"], 4), "launches_general_ms": round(tot["general"], 4),
+                  "launches_torch_ms": round(tot["torch"], 4), "time_over_general_route": ratios, "launches": rows_out}))
