@@ -35,14 +35,16 @@ Reference operators replaced:
 
 Gating.  As in functional.Conv3dGeneralF32, the ReLU gating of an activation gradient is moved into the kernel that
 produces it.  x_is_relu_output -> this layer's dx leaves already zeroed where x <= 0 (the lower layer's pre-activation
-gradient).  In the unpooled chain, dy_pregated -> the incoming dy was gated that way by the next layer, so backward reads it
-without touching y again; it is set only inside sat_encoder_f32, where that pairing holds by construction.  The pooled
-layers return relu(max_pool2d(z, 3)) (equal to max_pool2d(relu(z), 3)) and keep one byte per pooled output: the winning
-window position, or "dead" where the maximum is <= 0.  Their backward expands the pooled gradient through those codes,
-which carry the ReLU gate as well, so no gradient arriving at a pooled layer needs gating; above a pooled layer the
-x_is_relu_output gate equals the codes' (the pooled output is 0 exactly where its window is dead), so sat_encoder001_f32
-leaves it off.  Its one ReLU output without a pool, conv3's, goes to fc1, whose data gradient is not gated, so conv3 gates
-its own dy by its output.
+gradient).  dy_pregated -> the incoming dy was gated that way by the next layer, so backward reads it without touching y
+again.  The two only pair up inside a chain, so the single-layer wrappers do not offer dy_pregated and no chain builder
+passes either flag: conv_chain derives both from a layer's position, and states the rule.  The pooled layers return
+relu(max_pool2d(z, 3)) (equal to max_pool2d(relu(z), 3)) and keep one byte per pooled output: the winning window position,
+or "dead" where the maximum is <= 0.  Their backward expands the pooled gradient through those codes, which carry the ReLU
+gate as well, so no gradient arriving at a pooled layer needs gating, and the layer above one leaves its dx ungated (the
+pooled output is 0 exactly where its window is dead).
+
+A new family: its record and one-line entry points in hip_ops.py, its *_OPS tuple and single-layer wrapper here, and a chain
+builder that lists its model's layers for conv_chain.
 """
 import torch
 
@@ -64,37 +66,46 @@ CONV2D_HEAD_S2_OPS = (K.conv2d_head_s2_fwd_f32, K.conv2d_head_s2_bwd_data_f32, K
 CONV2D_WIDE_S2_OPS = (K.conv2d_wide_s2_fwd_f32, K.conv2d_wide_s2_bwd_data_f32, K.conv2d_wide_s2_bwd_weight_f32)
 CONVT2D_WIDE_S2_OPS = (K.convt2d_wide_s2_fwd_f32, K.convt2d_wide_s2_bwd_data_f32, K.convt2d_wide_s2_bwd_weight_f32)
 CONVT2D_HEAD_OPS = (K.convt2d_head_fwd_f32, K.convt2d_head_bwd_data_f32, K.convt2d_head_bwd_weight_f32)
-# ... of the stripe first layer: (forward, weight gradient), stride 1 (notebook 10) and stride 2 (notebook 09)
+# ... of the synthesised-input first layers, (forward, weight gradient): experiments/002's coordinate channels,
+COORDS_OPS = (K.conv2d_coords_fwd_f32, K.conv2d_coords_bwd_weight_f32)
+# the stripe plane at stride 1 (notebook 10) and stride 2 (notebook 09),
 STRIPE_WIDE_OPS = (K.conv2d_wide_stripe_fwd_f32, K.conv2d_wide_stripe_bwd_weight_f32)
 STRIPE_WIDE_S2_OPS = (K.conv2d_wide_s2_stripe_fwd_f32, K.conv2d_wide_s2_stripe_bwd_weight_f32)
-# ... of the raw-counts first layer: (forward, weight gradient)
+# the raw counts of notebooks 14-16
 COUNTS_AE_OPS = (K.conv2d_ae_counts_fwd_f32, K.conv2d_ae_counts_bwd_weight_f32)
 COUNTS_S2_OPS = (K.conv2d_s2_counts_fwd_f32, K.conv2d_s2_counts_bwd_weight_f32)
 # ... and of the conv with fused MaxPool2d(3): the forward returns (pooled, codes), the gradients take the codes
 CONV2D144_POOL_OPS = (K.conv2d144_pool_fwd_f32, K.conv2d144_pool_bwd_data_f32, K.conv2d144_pool_bwd_weight_f32)
 CONV2D_AE_POOL_OPS = (K.conv2d_ae_pool_fwd_f32, K.conv2d_ae_pool_bwd_data_f32, K.conv2d_ae_pool_bwd_weight_f32)
+POOL_OPS = (CONV2D144_POOL_OPS, CONV2D_AE_POOL_OPS)
 
 
-class CoordsConv2dReLU(torch.autograd.Function):
-    """First layer: sat [N, H, W, 12] channels-last, x_coords [N / t, W], y_coords [N / t, H]; the 17-channel input is
-    synthesised inside the kernels (forward and weight gradient), never stored.  No gradient flows to the inputs."""
+class SynthConvReLU(torch.autograd.Function):
+    """A first layer whose input is synthesised inside its kernels (forward and weight gradient) from `inputs`, never stored:
+    relu(conv(input built from inputs)).  ops = (forward, weight gradient): forward(*inputs, weight, bias, **scalars) and
+    weight_gradient(*inputs, dy, weight_shape=..., **scalars).  No gradient flows to the inputs.
+      COORDS_OPS                            sat [N, H, W, 12] channels-last, x_coords [N / t, W], y_coords [N / t, H]; t_per_example
+      COUNTS_AE_OPS, COUNTS_S2_OPS          history [N, 4, H, W], flow prediction [N, H, W] (counts, int16 or f32), horizon [N] f32
+      STRIPE_WIDE_OPS, STRIPE_WIDE_S2_OPS   history [N, n_hist, H, W] f32, stripe_start [N] int32 (the stripe plane is 1 on columns
+                                            stripe_start[i] <= c < stripe_start[i] + stripe_width); stripe_width
+      conv3d_wide_functional.HORIZON_WIDE_OPS   history [N, D, H, W] f32, horizon [N] f32 as a second, constant channel"""
 
     @staticmethod
-    def forward(ctx, sat, x_coords, y_coords, weight, bias, t_per_example, dy_pregated):
-        sat, x_coords, y_coords = sat.contiguous(), x_coords.contiguous(), y_coords.contiguous()
-        y = K.conv2d_coords_fwd_f32(sat, x_coords, y_coords, weight.contiguous(), bias.contiguous(), t_per_example)
-        ctx.save_for_backward(sat, x_coords, y_coords, None if dy_pregated else y)
-        ctx.t_per_example, ctx.weight_shape = t_per_example, tuple(weight.shape)
+    def forward(ctx, ops, inputs, weight, bias, scalars, dy_pregated):
+        inputs = tuple(t.contiguous() for t in inputs)
+        y = ops[0](*inputs, weight.contiguous(), bias.contiguous(), **scalars)
+        ctx.save_for_backward(*inputs, None if dy_pregated else y)
+        ctx.ops, ctx.scalars, ctx.weight_shape = ops, scalars, tuple(weight.shape)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        sat, x_coords, y_coords, y = ctx.saved_tensors
+        *inputs, y = ctx.saved_tensors
         dy = dy.contiguous()
         if y is not None:
             dy = K.relu_gate_f32(dy, y)
-        dw, db = K.conv2d_coords_bwd_weight_f32(sat, x_coords, y_coords, dy, ctx.t_per_example, ctx.weight_shape)
-        return None, None, None, dw, db, None, None
+        dw, db = ctx.ops[1](*inputs, dy, weight_shape=ctx.weight_shape, **ctx.scalars)
+        return None, None, dw, db, None, None
 
 
 class ConvReLU(torch.autograd.Function):
@@ -167,9 +178,47 @@ class ConvPool(torch.autograd.Function):
         return None, dx, dw, db, None
 
 
+def conv_chain(x, layers, last_relu):
+    """A chain of fused conv (+ ReLU) layers in which every activation has exactly one consumer, the next layer.
+    x: the first layer's input -- data or a pooled output, not a bare ReLU output -- or None where layers[0] synthesises its
+    own.  layers, in order, each one of
+      (ops, module)                     ConvReLU, or ConvPool where ops is one of POOL_OPS
+      (ops, module, inputs[, scalars])  with x None: SynthConvReLU on the (forward, weight gradient) pair ops
+      (Function, module, inputs)        a Function of one family that ends in a ReLU, applied as (y, *inputs, weight, bias,
+                                        x_is_relu_output, dy_pregated)
+      a callable                        a view of the activation (squeeze, unsqueeze): the values, so the flags, stand
+    Every layer but the last ends in a ReLU (the nn.ReLU modules of the notebooks' nn.Sequential are fused into the layers'
+    kernels); the last one does where last_relu.
+
+    The gating rule, which no caller spells out: layer i + 1's x_is_relu_output holds exactly when its input is a ReLU
+    output and not a pooled one (the pool's codes carry that gate); layer i's dy_pregated holds exactly when it ends in such
+    a ReLU and has a consumer in the chain, since that consumer then gates its data gradient by its input.  So no ReLU or
+    mask kernel runs on its own, and the chain's own output, whose consumer is unknown, is gated by the layer itself."""
+    y, gated = x, False                                 # gated: y is a ReLU output and not a pooled one
+    for i, layer in enumerate(layers):
+        if callable(layer):
+            y = layer(y)
+            continue
+        ops, m, *extra = layer
+        last = i == len(layers) - 1
+        relu = last_relu or not last
+        pooled = ops in POOL_OPS
+        pregated = relu and not pooled and not last
+        if y is None:
+            y = SynthConvReLU.apply(ops, extra[0], m.weight, m.bias, extra[1] if len(extra) > 1 else {}, pregated)
+        elif not isinstance(ops, tuple):
+            y = ops.apply(y, *extra[0], m.weight, m.bias, gated, pregated)
+        elif pooled:
+            y = ConvPool.apply(ops, y, m.weight, m.bias, gated)
+        else:
+            y = ConvReLU.apply(ops, y, m.weight, m.bias, relu, gated, pregated)
+        gated = relu and not pooled
+    return y
+
+
 def coords_conv2d_relu(sat, x_coords, y_coords, weight, bias, t_per_example):
     """relu(sat_conv1(17-channel input of experiments/002...py:180-208)); gradients to weight and bias only."""
-    return CoordsConv2dReLU.apply(sat, x_coords, y_coords, weight, bias, int(t_per_example), False)
+    return SynthConvReLU.apply(COORDS_OPS, (sat, x_coords, y_coords), weight, bias, {"t_per_example": int(t_per_example)}, False)
 
 
 def conv2d_relu(x, weight, bias, relu=True, x_is_relu_output=False):
@@ -179,13 +228,9 @@ def conv2d_relu(x, weight, bias, relu=True, x_is_relu_output=False):
 
 
 def sat_encoder_f32(sat, x_coords, y_coords, conv1, conv2, conv3, t_per_example):
-    """relu(conv3(relu(conv2(relu(conv1(17-channel input)))))) of experiments/002...py:180-211; conv1..3 are nn.Conv2d.
-    The two inner activations have exactly one consumer each, the next layer's conv, whose data gradient leaves gated by
-    them (x_is_relu_output): so their producers skip gating the arriving gradient again (dy_pregated).  That pairing is
-    only valid inside this chain, which is why the flag is not offered by coords_conv2d_relu / conv2d_relu."""
-    y1 = CoordsConv2dReLU.apply(sat, x_coords, y_coords, conv1.weight, conv1.bias, int(t_per_example), True)
-    y2 = ConvReLU.apply(CONV2D_OPS, y1, conv2.weight, conv2.bias, True, True, True)
-    return ConvReLU.apply(CONV2D_OPS, y2, conv3.weight, conv3.bias, True, True, False)
+    """relu(conv3(relu(conv2(relu(conv1(17-channel input)))))) of experiments/002...py:180-211; conv1..3 are nn.Conv2d."""
+    first = (COORDS_OPS, conv1, (sat, x_coords, y_coords), {"t_per_example": int(t_per_example)})
+    return conv_chain(None, [first, (CONV2D_OPS, conv2), (CONV2D_OPS, conv3)], last_relu=True)
 
 
 def sat_conv_pool_f32(sat, x_coords, y_coords, weight, bias, n_frames):
@@ -206,38 +251,12 @@ def conv144_relu(x, weight, bias, relu=True, x_is_relu_output=False):
 
 def sat_encoder001_f32(sat, x_coords, y_coords, conv1, conv2, conv3, n_frames):
     """relu(conv3(pool(relu(conv2(pool(relu(conv1(stacked input)))))))) of experiments/001...py:264-310; conv1..3 are
-    nn.Conv2d.  [B, 144, 11, 11] at 128 x 128.  conv2 and conv3 read pooled outputs, whose layers route the gradient through
-    their codes, so their dx is not gated again."""
+    nn.Conv2d.  [B, 144, 11, 11] at 128 x 128.  conv3's output goes to fc1, whose data gradient is not gated."""
     y1 = SatConvPool.apply(sat, x_coords, y_coords, conv1.weight, conv1.bias, int(n_frames))
-    y2 = ConvPool.apply(CONV2D144_POOL_OPS, y1, conv2.weight, conv2.bias, False)
-    return ConvReLU.apply(CONV2D144_OPS, y2, conv3.weight, conv3.bias, True, False, False)
+    return conv_chain(y1, [(CONV2D144_POOL_OPS, conv2), (CONV2D144_OPS, conv3)], last_relu=True)
 
 
 # ---- notebooks/16_maxpool.ipynb ----------------------------------------------------------------------------------------
-class CountsConvReLU(torch.autograd.Function):
-    """First layer of notebooks 14-16: history [N, 4, H, W] and flow prediction [N, H, W] as raw counts (int16 or f32),
-    horizon [N]; the normalised 6-channel input is built inside the kernels (forward and weight gradient), never stored.
-    ops = COUNTS_AE_OPS (stride 1, notebook 16) or COUNTS_S2_OPS (stride 2).  No gradient flows to the inputs."""
-
-    @staticmethod
-    def forward(ctx, ops, history, flow_pred, horizon, weight, bias, dy_pregated):
-        history, flow_pred = history.contiguous(), flow_pred.contiguous()
-        horizon = horizon.to(torch.float32).contiguous()
-        y = ops[0](history, flow_pred, horizon, weight.contiguous(), bias.contiguous())
-        ctx.save_for_backward(history, flow_pred, horizon, None if dy_pregated else y)
-        ctx.ops, ctx.weight_shape = ops, tuple(weight.shape)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        history, flow_pred, horizon, y = ctx.saved_tensors
-        dy = dy.contiguous()
-        if y is not None:
-            dy = K.relu_gate_f32(dy, y)
-        dw, db = ctx.ops[1](history, flow_pred, horizon, dy, ctx.weight_shape)
-        return None, None, None, None, dw, db, None
-
-
 class MseNorm(torch.autograd.Function):
     """F.mse_loss(y_hat, normalise(target)[window]): y_hat [N, P, Q] f32, target raw counts; the gradient 2 (y_hat - y) / count
     is produced in the same pass.  window None: target [N, P + 16, Q + 16] and the crop [..., 8:-8, 8:-8], whose entry point
@@ -259,9 +278,13 @@ class MseNorm(torch.autograd.Function):
         return grad * g, None, None
 
 
+def _counts_inputs(history, flow_pred, horizon):
+    return history, flow_pred, horizon.to(torch.float32)
+
+
 def counts_conv_relu(history, flow_pred, horizon, weight, bias):
     """relu(encoder_conv1(normalised 6-channel input of 16_maxpool.ipynb:13760-13779)); gradients to weight and bias only."""
-    return CountsConvReLU.apply(COUNTS_AE_OPS, history, flow_pred, horizon, weight, bias, False)
+    return SynthConvReLU.apply(COUNTS_AE_OPS, _counts_inputs(history, flow_pred, horizon), weight, bias, {}, False)
 
 
 def conv2d_ae_relu(x, weight, bias, relu=True, x_is_relu_output=False):
@@ -286,24 +309,16 @@ def mse_crop_norm(y_hat, target):
 
 def nb16_autoencoder_f32(history, flow_pred, horizon, enc, dec):
     """decoder_conv4(relu(decoder_conv3(... maxpool(relu(encoder_conv4(... relu(encoder_conv1(input))))))) of
-    16_maxpool.ipynb:13760-13801; enc = the four nn.Conv2d, dec = the four nn.ConvTranspose2d.  Every inner ReLU output has
-    one consumer, the next layer, whose data gradient leaves gated by it (x_is_relu_output), so its producer skips gating
-    the arriving gradient (dy_pregated).  The pooled output is 0 exactly where its window is dead, which the codes carry,
-    so decoder_conv1 leaves its dx ungated.  The pairing only holds inside this chain."""
-    y = CountsConvReLU.apply(COUNTS_AE_OPS, history, flow_pred, horizon, enc[0].weight, enc[0].bias, True)
-    y = ConvReLU.apply(CONV2D_AE_OPS, y, enc[1].weight, enc[1].bias, True, True, True)
-    y = ConvReLU.apply(CONV2D_AE_OPS, y, enc[2].weight, enc[2].bias, True, True, True)
-    y = ConvPool.apply(CONV2D_AE_POOL_OPS, y, enc[3].weight, enc[3].bias, True)
-    y = ConvReLU.apply(CONVT2D_AE_OPS, y, dec[0].weight, dec[0].bias, True, False, True)
-    y = ConvReLU.apply(CONVT2D_AE_OPS, y, dec[1].weight, dec[1].bias, True, True, True)
-    y = ConvReLU.apply(CONVT2D_AE_OPS, y, dec[2].weight, dec[2].bias, True, True, True)
-    return ConvReLU.apply(CONVT2D_AE_OPS, y, dec[3].weight, dec[3].bias, False, True, False)
+    16_maxpool.ipynb:13760-13801; enc = the four nn.Conv2d, dec = the four nn.ConvTranspose2d."""
+    return conv_chain(None, [(COUNTS_AE_OPS, enc[0], _counts_inputs(history, flow_pred, horizon)),
+                             (CONV2D_AE_OPS, enc[1]), (CONV2D_AE_OPS, enc[2]), (CONV2D_AE_POOL_OPS, enc[3]),
+                             *((CONVT2D_AE_OPS, m) for m in dec)], last_relu=False)
 
 
 # ---- notebooks/14_back_to_2d_conv_AE.ipynb, 15_int16.ipynb -------------------------------------------------------------
 def counts_conv_s2_relu(history, flow_pred, horizon, weight, bias):
     """relu(conv.0(normalised 6-channel input of 15_int16.ipynb:13766-13779)), stride 2; gradients to weight and bias only."""
-    return CountsConvReLU.apply(COUNTS_S2_OPS, history, flow_pred, horizon, weight, bias, False)
+    return SynthConvReLU.apply(COUNTS_S2_OPS, _counts_inputs(history, flow_pred, horizon), weight, bias, {}, False)
 
 
 def conv2d_s2_relu(x, weight, bias, relu=True, x_is_relu_output=False):
@@ -324,44 +339,14 @@ def mse_window_norm(y_hat, target, row0=0, col0=0):
 
 def nb15_autoencoder_f32(history, flow_pred, horizon, conv):
     """self.conv(images) of 15_int16.ipynb:13746-13780; conv = the notebook's nn.Sequential (modules 0, 2, 4, 6 nn.Conv2d and
-    8, 10, 12 nn.ConvTranspose2d, all stride 2; the nn.ReLU modules between them are fused into the layers' kernels).  Every
-    inner ReLU output has one consumer, the next layer, whose data gradient leaves gated by it (x_is_relu_output), so its
-    producer skips gating the arriving gradient (dy_pregated): no ReLU or mask kernel runs on its own.  The pairing only
-    holds inside this chain."""
-    y = CountsConvReLU.apply(COUNTS_S2_OPS, history, flow_pred, horizon, conv[0].weight, conv[0].bias, True)
-    for i in (2, 4, 6):
-        y = ConvReLU.apply(CONV2D_S2_OPS, y, conv[i].weight, conv[i].bias, True, True, True)
-    for i in (8, 10):
-        y = ConvReLU.apply(CONVT2D_S2_OPS, y, conv[i].weight, conv[i].bias, True, True, True)
-    return ConvReLU.apply(CONVT2D_S2_OPS, y, conv[12].weight, conv[12].bias, False, True, False)
+    8, 10, 12 nn.ConvTranspose2d, all stride 2)."""
+    return conv_chain(None, [(COUNTS_S2_OPS, conv[0], _counts_inputs(history, flow_pred, horizon)),
+                             *((CONV2D_S2_OPS, conv[i]) for i in (2, 4, 6)),
+                             *((CONVT2D_S2_OPS, conv[i]) for i in (8, 10, 12))], last_relu=False)
 
 
 # ---- notebooks/10_just_conv.ipynb ---------------------------------------------------------------------------------------
 STRIPE_WIDTH = 128 // 24          # 10_just_conv.ipynb:1379: a constant, not derived from the image width
-
-
-class StripeConvReLU(torch.autograd.Function):
-    """First layer of notebooks 09 and 10: history [N, n_hist, H, W] f32 plus the forecast-horizon stripe plane (1 on columns
-    stripe_start[i] <= c < stripe_start[i] + stripe_width), built inside the kernels (forward and weight gradient), never
-    stored.  ops = STRIPE_WIDE_OPS (stride 1, notebook 10) or STRIPE_WIDE_S2_OPS (stride 2, notebook 09).  No gradient flows
-    to the inputs."""
-
-    @staticmethod
-    def forward(ctx, ops, history, stripe_start, weight, bias, stripe_width, dy_pregated):
-        history, stripe_start = history.contiguous(), stripe_start.contiguous()
-        y = ops[0](history, stripe_start, weight.contiguous(), bias.contiguous(), stripe_width)
-        ctx.save_for_backward(history, stripe_start, None if dy_pregated else y)
-        ctx.ops, ctx.stripe_width, ctx.weight_shape = ops, stripe_width, tuple(weight.shape)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        history, stripe_start, y = ctx.saved_tensors
-        dy = dy.contiguous()
-        if y is not None:
-            dy = K.relu_gate_f32(dy, y)
-        dw, db = ctx.ops[1](history, stripe_start, dy, ctx.weight_shape, ctx.stripe_width)
-        return None, None, None, dw, db, None, None
 
 
 def stripe_start_from_horizon(horizon, stripe_width=STRIPE_WIDTH):
@@ -373,7 +358,7 @@ def stripe_start_from_horizon(horizon, stripe_width=STRIPE_WIDTH):
 
 def stripe_conv_relu(history, stripe_start, weight, bias, stripe_width=STRIPE_WIDTH):
     """relu(conv.0(cat(history, stripe plane))) of 10_just_conv.ipynb:1386-1387, 1398-1409; gradients to weight and bias only."""
-    return StripeConvReLU.apply(STRIPE_WIDE_OPS, history, stripe_start, weight, bias, int(stripe_width), False)
+    return SynthConvReLU.apply(STRIPE_WIDE_OPS, (history, stripe_start), weight, bias, {"stripe_width": int(stripe_width)}, False)
 
 
 def conv2d_wide_relu(x, weight, bias, relu=True, x_is_relu_output=False, padding=0):
@@ -390,13 +375,10 @@ def conv2d_head_s2(x, weight, bias, x_is_relu_output=False):
 
 def nb10_just_conv_f32(history, stripe_start, conv):
     """self.conv(cat(hist_images, stripe plane)) of 10_just_conv.ipynb:1386-1410; conv = the notebook's nn.Sequential (modules 0,
-    2, 4, 6 nn.Conv2d; the nn.ReLU modules between them are fused into the layers' kernels).  Every inner ReLU output has one
-    consumer, the next layer, whose data gradient leaves gated by it (x_is_relu_output), so its producer skips gating the
-    arriving gradient (dy_pregated): no ReLU or mask kernel runs on its own.  The pairing only holds inside this chain."""
-    y = StripeConvReLU.apply(STRIPE_WIDE_OPS, history, stripe_start, conv[0].weight, conv[0].bias, STRIPE_WIDTH, True)
-    y = ConvReLU.apply(CONV2D_WIDE_OPS, y, conv[2].weight, conv[2].bias, True, True, True)
-    y = ConvReLU.apply(CONV2D_WIDE_P2_OPS, y, conv[4].weight, conv[4].bias, True, True, True)
-    return ConvReLU.apply(CONV2D_HEAD_S2_OPS, y, conv[6].weight, conv[6].bias, False, True, False)
+    2, 4, 6 nn.Conv2d)."""
+    return conv_chain(None, [(STRIPE_WIDE_OPS, conv[0], (history, stripe_start), {"stripe_width": STRIPE_WIDTH}),
+                             (CONV2D_WIDE_OPS, conv[2]), (CONV2D_WIDE_P2_OPS, conv[4]), (CONV2D_HEAD_S2_OPS, conv[6])],
+                      last_relu=False)
 
 
 # ---- notebooks/09_horizon_represented_as_a_stripe.ipynb ------------------------------------------------------------------
@@ -419,7 +401,8 @@ class MsePredWindow(torch.autograd.Function):
 def stripe_conv_s2_relu(history, stripe_start, weight, bias, stripe_width=STRIPE_WIDTH):
     """relu(encoder_conv.0(cat(history, stripe plane))) of 09_horizon_represented_as_a_stripe.ipynb:1366-1367, 1382-1397,
     stride 2; gradients to weight and bias only."""
-    return StripeConvReLU.apply(STRIPE_WIDE_S2_OPS, history, stripe_start, weight, bias, int(stripe_width), False)
+    return SynthConvReLU.apply(STRIPE_WIDE_S2_OPS, (history, stripe_start), weight, bias, {"stripe_width": int(stripe_width)},
+                               False)
 
 
 def conv2d_wide_s2_relu(x, weight, bias, relu=True, x_is_relu_output=False):
@@ -445,14 +428,9 @@ def mse_pred_window(y_hat, target, row0=0, col0=0):
 
 def nb09_stripe_ae_f32(history, stripe_start, encoder_conv, decoder_conv):
     """self.decoder_conv(self.encoder_conv(cat(hist_images, stripe plane))) of 09_horizon_represented_as_a_stripe.ipynb
-    :1366-1398; encoder_conv / decoder_conv = the notebook's two nn.Sequential (modules 0, 2, 4 nn.Conv2d / nn.ConvTranspose2d;
-    the nn.ReLU modules between them are fused into the layers' kernels).  Every inner ReLU output has one consumer, the next
-    layer, whose data gradient leaves gated by it (x_is_relu_output), so its producer skips gating the arriving gradient
-    (dy_pregated): no ReLU or mask kernel runs on its own.  The pairing only holds inside this chain."""
+    :1366-1398; encoder_conv / decoder_conv = the notebook's two nn.Sequential (modules 0, 2, 4 nn.Conv2d / nn.ConvTranspose2d)."""
     enc, dec = encoder_conv, decoder_conv
-    y = StripeConvReLU.apply(STRIPE_WIDE_S2_OPS, history, stripe_start, enc[0].weight, enc[0].bias, STRIPE_WIDTH, True)
-    for i in (2, 4):
-        y = ConvReLU.apply(CONV2D_WIDE_S2_OPS, y, enc[i].weight, enc[i].bias, True, True, True)
-    for i in (0, 2):
-        y = ConvReLU.apply(CONVT2D_WIDE_S2_OPS, y, dec[i].weight, dec[i].bias, True, True, True)
-    return ConvReLU.apply(CONVT2D_HEAD_OPS, y, dec[4].weight, dec[4].bias, False, True, False)
+    return conv_chain(None, [(STRIPE_WIDE_S2_OPS, enc[0], (history, stripe_start), {"stripe_width": STRIPE_WIDTH}),
+                             (CONV2D_WIDE_S2_OPS, enc[2]), (CONV2D_WIDE_S2_OPS, enc[4]),
+                             (CONVT2D_WIDE_S2_OPS, dec[0]), (CONVT2D_WIDE_S2_OPS, dec[2]), (CONVT2D_HEAD_OPS, dec[4])],
+                      last_relu=False)

@@ -10,17 +10,17 @@ notebooks/08_multiple_historical_images_as_separate_channels.ipynb (raw lines of
     self.decoder_conv(cat(encoder_out, forecast horizon plane)): ConvTranspose2d 33 -> 32 -> 32 stride 2 with ReLU,
     ConvTranspose2d 32 -> 1                                                                                    :1374-1380, 1388-1392
 
-Gating follows conv2d_functional: ConvReLU (which only hands tensors to its family's three entry points, so it serves
-NCDHW tensors unchanged) lets each data gradient leave gated by the layer's input (x_is_relu_output), and the layer below then
-reads the arriving gradient without touching its own output (dy_pregated).  Both are flags fixed when the chain is built: no
-tensor is handed from one backward node to another here, so there is nothing to keep in a _backward_pass.PassTable.
+Gating follows conv2d_functional, whose ConvReLU only hands tensors to its family's three entry points and so serves NCDHW
+tensors unchanged; the chain builders list their layers for conv_chain, which derives both flags from position.  They are
+fixed when the chain is built: no tensor is handed from one backward node to another here, so there is nothing to keep in a
+_backward_pass.PassTable.
 """
 from functools import partial
 
 import torch
 
 from . import hip_ops as K
-from .conv2d_functional import ConvReLU
+from .conv2d_functional import CONVT2D_HEAD_OPS, CONVT2D_S2_OPS, ConvReLU, SynthConvReLU, conv_chain
 
 # (forward, data gradient, weight gradient) of the wide family, one tuple per depth padding, and of the depth-2 head
 CONV3D_WIDE_OPS = {pd: (partial(K.conv3d_wide_fwd_f32, padding=(pd, 1, 1)),
@@ -29,35 +29,14 @@ CONV3D_WIDE_OPS = {pd: (partial(K.conv3d_wide_fwd_f32, padding=(pd, 1, 1)),
 CONV3D_HEAD_D2_OPS = (K.conv3d_head_d2_fwd_f32, K.conv3d_head_d2_bwd_data_f32, K.conv3d_head_d2_bwd_weight_f32)
 # notebook 08: the strided depth-2 Conv3d layers
 CONV3D_S2_OPS = (K.conv3d_s2_fwd_f32, K.conv3d_s2_bwd_data_f32, K.conv3d_s2_bwd_weight_f32)
-
-
-class HorizonConvReLU(torch.autograd.Function):
-    """First layer of notebook 12: history [N, D, H, W] f32 plus the forecast horizon [N] as a second input channel, constant
-    over depth and the image, built inside the kernels (forward and weight gradient), never stored.  No gradient flows to the
-    inputs."""
-
-    @staticmethod
-    def forward(ctx, history, horizon, weight, bias, dy_pregated):
-        history, horizon = history.contiguous(), horizon.contiguous()
-        y = K.conv3d_wide_horizon_fwd_f32(history, horizon, weight.contiguous(), bias.contiguous())
-        ctx.save_for_backward(history, horizon, None if dy_pregated else y)
-        ctx.weight_shape = tuple(weight.shape)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        history, horizon, y = ctx.saved_tensors
-        dy = dy.contiguous()
-        if y is not None:
-            dy = K.relu_gate_f32(dy, y)
-        dw, db = K.conv3d_wide_horizon_bwd_weight_f32(history, horizon, dy, ctx.weight_shape)
-        return None, None, dw, db, None
+# (forward, weight gradient) of notebook 12's first layer, whose second input channel is the forecast horizon
+HORIZON_WIDE_OPS = (K.conv3d_wide_horizon_fwd_f32, K.conv3d_wide_horizon_bwd_weight_f32)
 
 
 def horizon_conv_relu(history, horizon, weight, bias):
     """relu(conv.0(cat(history.unsqueeze(1), horizon channel))) of 12_just_3d_conv.ipynb:1398-1399, 1413-1418; gradients to
     weight and bias only."""
-    return HorizonConvReLU.apply(history, horizon, weight, bias, False)
+    return SynthConvReLU.apply(HORIZON_WIDE_OPS, (history, horizon), weight, bias, {}, False)
 
 
 def conv3d_wide_relu(x, weight, bias, relu=True, x_is_relu_output=False, padding=(0, 1, 1)):
@@ -77,15 +56,11 @@ def conv3d_head_d2(x, weight, bias, x_is_relu_output=False):
 
 def nb12_just_3d_conv_f32(history, horizon, conv):
     """self.conv(cat(hist_images.unsqueeze(1), horizon channel)) of 12_just_3d_conv.ipynb:1397-1420; conv = the notebook's
-    nn.Sequential (modules 0, 2, 4, 6, 8 nn.Conv3d; the nn.ReLU modules between them are fused into the layers' kernels).
-    history [N, 4, H, W], horizon [N] f32 -> [N, 1, 1, (H - 1) // 2 + 1, (W - 1) // 2 + 1].  Every inner ReLU output has one
-    consumer, the next layer, whose data gradient leaves gated by it (x_is_relu_output), so its producer skips gating the
-    arriving gradient (dy_pregated): no ReLU or mask kernel runs on its own.  The pairing only holds inside this chain."""
-    y = HorizonConvReLU.apply(history, horizon, conv[0].weight, conv[0].bias, True)
-    y = ConvReLU.apply(CONV3D_WIDE_OPS[0], y, conv[2].weight, conv[2].bias, True, True, True)
-    y = ConvReLU.apply(CONV3D_WIDE_OPS[1], y, conv[4].weight, conv[4].bias, True, True, True)
-    y = ConvReLU.apply(CONV3D_WIDE_OPS[0], y, conv[6].weight, conv[6].bias, True, True, True)
-    return ConvReLU.apply(CONV3D_HEAD_D2_OPS, y, conv[8].weight, conv[8].bias, False, True, False)
+    nn.Sequential (modules 0, 2, 4, 6, 8 nn.Conv3d).  history [N, 4, H, W], horizon [N] f32 -> [N, 1, 1, (H - 1) // 2 + 1,
+    (W - 1) // 2 + 1]."""
+    return conv_chain(None, [(HORIZON_WIDE_OPS, conv[0], (history, horizon)), (CONV3D_WIDE_OPS[0], conv[2]),
+                             (CONV3D_WIDE_OPS[1], conv[4]), (CONV3D_WIDE_OPS[0], conv[6]), (CONV3D_HEAD_D2_OPS, conv[8])],
+                      last_relu=False)
 
 
 class HorizonConvTransposeReLU(torch.autograd.Function):
@@ -128,16 +103,9 @@ def horizon_conv_transpose_relu(x, horizon, weight, bias, x_is_relu_output=False
 def nb08_hist_depth_f32(history, horizon, encoder_conv, decoder_conv):
     """self.decoder_conv(cat(self.encoder_conv(hist_images.unsqueeze(1)) without its depth axis, horizon plane)) of
     08_...ipynb:1382-1392; encoder_conv / decoder_conv = the notebook's two nn.Sequential (modules 0, 2, 4 nn.Conv3d /
-    nn.ConvTranspose2d; the nn.ReLU modules are fused into the layers' kernels).  history [N, 4, H, W], horizon [N] f32 -> [N,
-    1, 4 e + 5, 4 f + 5] for an encoder output of e x f.  Depth 4 -> 3 -> 2 -> 1; dropping the depth axis of size 1 and adding
-    the one of the input are views.  Every inner ReLU output has one consumer, the next layer, whose data gradient leaves gated
-    by it (x_is_relu_output), so its producer skips gating the arriving gradient (dy_pregated): no ReLU or mask kernel runs
-    on its own.  The pairing only holds inside this chain."""
-    from .conv2d_functional import CONVT2D_HEAD_OPS, CONVT2D_S2_OPS
+    nn.ConvTranspose2d).  history [N, 4, H, W], horizon [N] f32 -> [N, 1, 4 e + 5, 4 f + 5] for an encoder output of e x f.
+    Depth 4 -> 3 -> 2 -> 1; dropping the depth axis of size 1 and adding the one of the input are views."""
     enc, dec = encoder_conv, decoder_conv
-    y = ConvReLU.apply(CONV3D_S2_OPS, history.unsqueeze(1), enc[0].weight, enc[0].bias, True, False, True)
-    for i in (2, 4):
-        y = ConvReLU.apply(CONV3D_S2_OPS, y, enc[i].weight, enc[i].bias, True, True, True)
-    y = HorizonConvTransposeReLU.apply(y.squeeze(2), horizon, dec[0].weight, dec[0].bias, True, True)
-    y = ConvReLU.apply(CONVT2D_S2_OPS, y, dec[2].weight, dec[2].bias, True, True, True)
-    return ConvReLU.apply(CONVT2D_HEAD_OPS, y, dec[4].weight, dec[4].bias, False, True, False)
+    return conv_chain(history.unsqueeze(1), [(CONV3D_S2_OPS, enc[0]), (CONV3D_S2_OPS, enc[2]), (CONV3D_S2_OPS, enc[4]),
+                                             lambda y: y.squeeze(2), (HorizonConvTransposeReLU, dec[0], (horizon,)),
+                                             (CONVT2D_S2_OPS, dec[2]), (CONVT2D_HEAD_OPS, dec[4])], last_relu=False)

@@ -39,29 +39,41 @@ def draw_example(n_frames: int, height: int, width: int, rng: np.random.Generato
     return hist_start, horizon, top, left
 
 
-def super_batch_to_example(frames: np.ndarray, rng: np.random.Generator, side_large: int = 128, side_small: int = 64):
+def super_batch_to_example(frames: np.ndarray, rng: np.random.Generator, side_large: int = 128, side_small: int = 64,
+                           horizon_form=int):
+    """One example: the history crop, its centred target crop and horizon_form(timesteps ahead)."""
     n_frames, height, width = frames.shape
     hist_start, horizon, top, left = draw_example(n_frames, height, width, rng, side_large)
     hist_end = hist_start + N_HIST_IMAGES
     border = (side_large - side_small) // 2
     target = frames[hist_end - 1 + horizon, top + border:top + side_large - border, left + border:left + side_large - border]
-    return {TARGET_SAT_IMAGE: target, FORECAST_HORIZON: horizon,
+    return {TARGET_SAT_IMAGE: target, FORECAST_HORIZON: horizon_form(horizon),
             HISTORICAL_SAT_IMAGES: frames[hist_start:hist_end, top:top + side_large, left:left + side_large]}
 
 
-def make_fake_nb10_batch(frames: np.ndarray, batch_size: int, image_size_pixels: int, rng: np.random.Generator, device):
-    small = output_side(image_size_pixels)
+def make_fake_batch(frames: np.ndarray, batch_size: int, image_size_pixels: int, rng: np.random.Generator, device,
+                    side_rule=output_side, horizon_form=int):
+    """batch_size examples whose centred target crop has side_rule(image_size_pixels) pixels a side; the horizon is int64 where
+    horizon_form leaves it an int, else float32."""
+    small = side_rule(image_size_pixels)
     if (image_size_pixels - small) % 2:
         raise ValueError(f"image_size_pixels={image_size_pixels}: the centred target crop of {small} pixels needs an even "
                          f"border")
-    examples = [super_batch_to_example(frames, rng, image_size_pixels, small) for _ in range(batch_size)]
+    examples = [super_batch_to_example(frames, rng, image_size_pixels, small, horizon_form) for _ in range(batch_size)]
+    horizon = np.array([e[FORECAST_HORIZON] for e in examples])
     return {HISTORICAL_SAT_IMAGES: torch.from_numpy(np.stack([e[HISTORICAL_SAT_IMAGES] for e in examples])).to(device),
-            FORECAST_HORIZON: torch.tensor([e[FORECAST_HORIZON] for e in examples], dtype=torch.int64, device=device),
+            FORECAST_HORIZON: torch.from_numpy(horizon).to(device),
             TARGET_SAT_IMAGE: torch.from_numpy(np.stack([e[TARGET_SAT_IMAGE] for e in examples])).to(device)}
 
 
+make_fake_nb10_batch = make_fake_batch
+
+
 class Nb10DataModule(LightningDataModule):
-    """n_train_data / n_val_data seeded batches drawn from n_super_batches synthetic super-batches, built once at setup()."""
+    """n_train_data / n_val_data seeded batches drawn from n_super_batches synthetic super-batches, built once at setup().
+    make_batch: the model's batch builder (a subclass sets its own target side and horizon form)."""
+
+    make_batch = staticmethod(make_fake_nb10_batch)
 
     def __init__(self, batch_size: int = 64, image_size_pixels: int = 128, n_train_data: int = 8, n_val_data: int = 2,
                  n_super_batches: int = 2, n_timesteps: int = 49, frame_size_pixels: int = 176, seed: int = 1234,
@@ -80,8 +92,8 @@ class Nb10DataModule(LightningDataModule):
         rng = np.random.default_rng(self.seed)
 
         def batches(n):
-            return [make_fake_nb10_batch(supers[int(rng.integers(len(supers)))], self.batch_size, self.image_size_pixels, rng,
-                                         self.device) for _ in range(n)]
+            return [self.make_batch(supers[int(rng.integers(len(supers)))], self.batch_size, self.image_size_pixels, rng,
+                                    self.device) for _ in range(n)]
 
         self._train, self._val = batches(self.n_train_data), batches(self.n_val_data)
 

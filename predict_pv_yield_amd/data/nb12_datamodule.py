@@ -4,11 +4,12 @@ sample_squares cells are the same in both notebooks); what differs is FORECAST_H
 loader (normalise_forecast_horizon, 12_just_3d_conv.ipynb:757-768): float32 (h - mean) / std of arange(1, 25).  The batch
 keeps the notebook's three keys: HISTORICAL_SAT_IMAGES [B, 4, S, S] f32, FORECAST_HORIZON [B] f32, TARGET_SAT_IMAGE [B, s, s]
 f32 with s = (S - 1) // 2 + 1."""
-import numpy as np
-import torch
+from functools import partial
 
-from ..models.conv3d.nb12_just_3d_conv import (FORECAST_HORIZON, HISTORICAL_SAT_IMAGES, N_HIST_IMAGES, TARGET_SAT_IMAGE,
-                                               output_side)
+import numpy as np
+
+from ..models.conv3d.nb12_just_3d_conv import output_side
+from . import nb10_datamodule as nb10
 from .nb10_datamodule import Nb10DataModule, draw_example, make_fake_super_batch  # noqa: F401
 
 FCST_HORIZON_SEQ = np.arange(1, 25, dtype=np.float32)
@@ -24,39 +25,11 @@ def normalise_forecast_horizon(forecast_horizon: int) -> np.float32:
     return forecast_horizon
 
 
-def super_batch_to_example(frames: np.ndarray, rng: np.random.Generator, side_large: int = 128, side_small: int = 64):
-    n_frames, height, width = frames.shape
-    hist_start, horizon, top, left = draw_example(n_frames, height, width, rng, side_large, N_HIST_IMAGES)
-    hist_end = hist_start + N_HIST_IMAGES
-    border = (side_large - side_small) // 2
-    target = frames[hist_end - 1 + horizon, top + border:top + side_large - border, left + border:left + side_large - border]
-    return {TARGET_SAT_IMAGE: target, FORECAST_HORIZON: normalise_forecast_horizon(horizon),
-            HISTORICAL_SAT_IMAGES: frames[hist_start:hist_end, top:top + side_large, left:left + side_large]}
-
-
-def make_fake_nb12_batch(frames: np.ndarray, batch_size: int, image_size_pixels: int, rng: np.random.Generator, device):
-    small = output_side(image_size_pixels)
-    if (image_size_pixels - small) % 2:
-        raise ValueError(f"image_size_pixels={image_size_pixels}: the centred target crop of {small} pixels needs an even "
-                         f"border")
-    examples = [super_batch_to_example(frames, rng, image_size_pixels, small) for _ in range(batch_size)]
-    return {HISTORICAL_SAT_IMAGES: torch.from_numpy(np.stack([e[HISTORICAL_SAT_IMAGES] for e in examples])).to(device),
-            FORECAST_HORIZON: torch.from_numpy(np.array([e[FORECAST_HORIZON] for e in examples], dtype=np.float32)).to(device),
-            TARGET_SAT_IMAGE: torch.from_numpy(np.stack([e[TARGET_SAT_IMAGE] for e in examples])).to(device)}
+super_batch_to_example = partial(nb10.super_batch_to_example, horizon_form=normalise_forecast_horizon)
+make_fake_nb12_batch = partial(nb10.make_fake_batch, side_rule=output_side, horizon_form=normalise_forecast_horizon)
 
 
 class Nb12DataModule(Nb10DataModule):
     """Nb10DataModule's seeded batches (same super-batches, same draws) with the horizon normalised as notebook 12 does."""
 
-    def setup(self, stage=None):
-        if self._train is not None:
-            return
-        supers = [make_fake_super_batch(self.n_timesteps, self.frame_size_pixels, self.seed + i)
-                  for i in range(self.n_super_batches)]
-        rng = np.random.default_rng(self.seed)
-
-        def batches(n):
-            return [make_fake_nb12_batch(supers[int(rng.integers(len(supers)))], self.batch_size, self.image_size_pixels, rng,
-                                         self.device) for _ in range(n)]
-
-        self._train, self._val = batches(self.n_train_data), batches(self.n_val_data)
+    make_batch = staticmethod(make_fake_nb12_batch)

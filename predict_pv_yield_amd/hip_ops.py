@@ -1078,8 +1078,9 @@ def conv3d_general_bwd_weight_f32(x, dy, y_mask, weight_shape, stride=1, padding
 # A family of entry points is described once, by a _ConvFamily record (its plain forward / data gradient / weight gradient)
 # and, where it has them, a _PoolFamily record (the same three passes with MaxPool2d(3) fused).  _conv_fwd, _conv_bwd_data,
 # _conv_bwd_weight, _pool_*, _counts_* and _mse_norm are the only implementations; the public functions below them are
-# one-line calls.  A new family is a new record plus its one-line functions, and its argtypes from the shared lists of
-# _lib.py; a new pass is written once here.  tests/test_conv2d_glue_cpu.py pins what each wrapper hands to the C ABI.
+# one-line calls, for the Conv3d families of notebooks 12 and 08 further down as well.  A new family is a new record (its
+# shape rule) plus its one-line functions, and its argtypes from the shared lists of _lib.py; a new pass is written once here.
+# tests/test_conv2d_glue_cpu.py pins what each wrapper hands to the C ABI.
 # ------------------------------------------------------------------------------------------------
 C144 = 144
 
@@ -1247,20 +1248,32 @@ def s2_out(side):
 
 
 class _ConvFamily(NamedTuple):
-    """One family of plain entry points: pv_{stem}_{fwd,bwd_data,bwd_weight}_f32 and pv_{stem}_bwd_weight_workspace_bytes."""
+    """One family of plain entry points, 2-D or 3-D: pv_{stem}_{fwd,bwd_data,bwd_weight}_f32 and
+    pv_{stem}_bwd_weight_workspace_bytes."""
     stem: str                       # also names the weight gradient's workspace, "{stem}_wgrad" (a captured graph pins by key)
-    check_channels: Callable        # (who, x_shape, weight_shape): raises ValueError
-    out_hw: Callable                # (h, w) of the input -> (h, w) of the output
-    c_out_axis: int = 0             # of the weight: 0 in Conv2d's [C_out, C_in, 3, 3], 1 in ConvTranspose2d's [C_in, C_out, ..]
-    ws_args: tuple = ()             # the workspace query's arguments after (n, c_in, c_out, h, w): the "pooled" flag, 0 here
-    pad_args: tuple = ()            # every pass's arguments after (n, c_in, c_out, h, w): the padding of a padded family
+    shape: Callable                 # (who, x_shape, weight_shape) -> (every pass's integers (n, c_in, c_out, sides.., padding..),
+    #                                 the output's shape); raises ValueError
+    ws_args: tuple = ()             # the workspace query's arguments after those integers: the "pooled" flag, 0 here
+    out_hw: Callable = None         # 2-D: (h, w) of the input -> (h, w) of the output, for the synthesised first layers
+    pad_args: tuple = ()            # 2-D: the padding of a padded family, which follows (n, c_in, c_out, h, w)
+
+
+def _conv2d_family(stem, check_channels, out_hw, c_out_axis=0, ws_args=(), pad_args=()):
+    """A 2-D family from its channel rule (who, x_shape, weight_shape), which raises ValueError, and its output rule;
+    c_out_axis of the weight: 0 in Conv2d's [C_out, C_in, 3, 3], 1 in ConvTranspose2d's [C_in, C_out, 3, 3]."""
+    def shape(who, x_shape, weight_shape):
+        check_channels(who, x_shape, weight_shape)
+        n, ci, h, w = x_shape
+        co = weight_shape[c_out_axis]
+        return (n, ci, co, h, w, *pad_args), (n, co, *out_hw(h, w))
+    return _ConvFamily(stem, shape, ws_args, out_hw, pad_args)
 
 
 class _PoolFamily(NamedTuple):
     """The conv + MaxPool2d(3) passes of a family, pv_{stem}_pool_{fwd,bwd_data,bwd_weight}_f32; the weight gradient takes
     the plain family's workspace, queried with the "pooled" flag 1."""
     stem: str
-    check_channels: Callable        # as _ConvFamily's; the pooled passes need a bias
+    check_channels: Callable        # (who, x_shape, weight_shape): raises ValueError; the pooled passes need a bias
     pooled_shape: Callable          # (n, c_out, h, w) -> shape of the pooled output
     fwd_workspace: bool             # the forward has pv_{stem}_pool_fwd_workspace_bytes and takes (workspace, bytes)
 
@@ -1273,22 +1286,21 @@ def _s2_hw(h, w):
     return max(s2_out(h), 0), max(s2_out(w), 0)
 
 
-_CONV2D = _ConvFamily("conv2d", _check_c32, _valid_hw)
-_CONV2D144 = _ConvFamily("conv2d144", _check_c144, _valid_hw, ws_args=(0,))
-_CONV2D_AE = _ConvFamily("conv2d_ae", _check_ae, _valid_hw, ws_args=(0,))
-_CONVT2D_AE = _ConvFamily("convt2d_ae", _check_aet, lambda h, w: (h + 2, w + 2), c_out_axis=1)
-_CONV2D_S2 = _ConvFamily("conv2d_s2", _check_ae, _s2_hw)
-_CONVT2D_S2 = _ConvFamily("convt2d_s2", _check_aet, lambda h, w: (2 * h + 1, 2 * w + 1), c_out_axis=1)
+_CONV2D = _conv2d_family("conv2d", _check_c32, _valid_hw)
+_CONV2D144 = _conv2d_family("conv2d144", _check_c144, _valid_hw, ws_args=(0,))
+_CONV2D_AE = _conv2d_family("conv2d_ae", _check_ae, _valid_hw, ws_args=(0,))
+_CONVT2D_AE = _conv2d_family("convt2d_ae", _check_aet, lambda h, w: (h + 2, w + 2), c_out_axis=1)
+_CONV2D_S2 = _conv2d_family("conv2d_s2", _check_ae, _s2_hw)
+_CONVT2D_S2 = _conv2d_family("convt2d_s2", _check_aet, lambda h, w: (2 * h + 1, 2 * w + 1), c_out_axis=1)
 # notebook 10: the padded wide family is one stem with a record per padding (the padding goes to every pass and to the
 # workspace query); the stride-2 head maps a side s to (s + 1) // 2 + 1
-_CONV2D_WIDE_P0 = _ConvFamily("conv2d_wide", lambda *a: _check_wide(*a, pad=0), _valid_hw, ws_args=(0,), pad_args=(0,))
-_CONV2D_WIDE_P2 = _ConvFamily("conv2d_wide", lambda *a: _check_wide(*a, pad=2), lambda h, w: (h + 2, w + 2), ws_args=(2,),
-                              pad_args=(2,))
-_CONV2D_HEAD_S2 = _ConvFamily("conv2d_head_s2", lambda *a: _check_head(*a), lambda h, w: (head_s2_out(h), head_s2_out(w)))
+_CONV2D_WIDE_P0 = _conv2d_family("conv2d_wide", lambda *a: _check_wide(*a, pad=0), _valid_hw, pad_args=(0,))
+_CONV2D_WIDE_P2 = _conv2d_family("conv2d_wide", lambda *a: _check_wide(*a, pad=2), lambda h, w: (h + 2, w + 2), pad_args=(2,))
+_CONV2D_HEAD_S2 = _conv2d_family("conv2d_head_s2", lambda *a: _check_head(*a), lambda h, w: (head_s2_out(h), head_s2_out(w)))
 # notebook 09: the stride-2 64 / 128-channel layers and the one-output-channel ConvTranspose2d head (stride 1)
-_CONV2D_WIDE_S2 = _ConvFamily("conv2d_wide_s2", _check_wide_s2, _s2_hw)
-_CONVT2D_WIDE_S2 = _ConvFamily("convt2d_wide_s2", _check_widet_s2, lambda h, w: (2 * h + 1, 2 * w + 1), c_out_axis=1)
-_CONVT2D_HEAD = _ConvFamily("convt2d_head", _check_headt, lambda h, w: (h + 2, w + 2), c_out_axis=1)
+_CONV2D_WIDE_S2 = _conv2d_family("conv2d_wide_s2", _check_wide_s2, _s2_hw)
+_CONVT2D_WIDE_S2 = _conv2d_family("convt2d_wide_s2", _check_widet_s2, lambda h, w: (2 * h + 1, 2 * w + 1), c_out_axis=1)
+_CONVT2D_HEAD = _conv2d_family("convt2d_head", _check_headt, lambda h, w: (h + 2, w + 2), c_out_axis=1)
 _CONV2D144_POOL = _PoolFamily("conv2d144", _check_c144_pooled, _pooled_shape, False)
 _CONV2D_AE_POOL = _PoolFamily("conv2d_ae", _check_ae, _pooled_shape_c, True)
 
@@ -1307,8 +1319,7 @@ def _grads_out(weight_shape, c_out, device):
             torch.empty((c_out,), dtype=torch.float32, device=device))
 
 
-def _check_dy(who, fam, dy, dy_gate, n, co, h, w):
-    y_shape = (n, co, *fam.out_hw(h, w))
+def _check_dy(who, dy, dy_gate, y_shape):
     if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
         raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
 
@@ -1316,46 +1327,40 @@ def _check_dy(who, fam, dy, dy_gate, n, co, h, w):
 # ---- the plain passes ----
 def _conv_fwd(fam, x, weight, bias, relu):
     who = f"{fam.stem}_fwd_f32"
-    fam.check_channels(who, x.shape, weight.shape)
-    n, ci, h, w = x.shape
-    co = weight.shape[fam.c_out_axis]
-    _check_bias(who, bias, co)
+    dims, y_shape = fam.shape(who, x.shape, weight.shape)
+    _check_bias(who, bias, dims[2])
     require_cuda(x, weight, bias)
     _f32_contig(x, weight, bias)
-    y = torch.empty((n, co, *fam.out_hw(h, w)), dtype=torch.float32, device=x.device)
-    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(weight), ptr(bias), ptr(y), n, ci, co, h, w, *fam.pad_args,
-                                          int(relu), current_stream_ptr()), "pv_" + who)
+    y = torch.empty(y_shape, dtype=torch.float32, device=x.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(weight), ptr(bias), ptr(y), *dims, int(relu), current_stream_ptr()),
+          "pv_" + who)
     return y
 
 
 def _conv_bwd_data(fam, dy, dy_gate, weight, x_gate, x_shape):
     who = f"{fam.stem}_bwd_data_f32"
-    fam.check_channels(who, x_shape, weight.shape)
-    n, ci, h, w = x_shape
-    co = weight.shape[fam.c_out_axis]
-    _check_dy(who, fam, dy, dy_gate, n, co, h, w)
+    dims, y_shape = fam.shape(who, x_shape, weight.shape)
+    _check_dy(who, dy, dy_gate, y_shape)
     if x_gate is not None and tuple(x_gate.shape) != tuple(x_shape):
         raise ValueError(f"{who}: x_gate {tuple(x_shape)} expected")
     require_cuda(dy, dy_gate, weight, x_gate)
     _f32_contig(dy, dy_gate, weight, x_gate)
     dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
-    check(getattr(get_lib(), "pv_" + who)(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), n, ci, co, h, w,
-                                          *fam.pad_args, current_stream_ptr()), "pv_" + who)
+    check(getattr(get_lib(), "pv_" + who)(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), *dims,
+                                          current_stream_ptr()), "pv_" + who)
     return dx
 
 
 def _conv_bwd_weight(fam, x, dy, dy_gate, weight_shape):
     who = f"{fam.stem}_bwd_weight_f32"
-    fam.check_channels(who, x.shape, weight_shape)
-    n, ci, h, w = x.shape
-    co = weight_shape[fam.c_out_axis]
-    _check_dy(who, fam, dy, dy_gate, n, co, h, w)
+    dims, y_shape = fam.shape(who, x.shape, weight_shape)
+    _check_dy(who, dy, dy_gate, y_shape)
     require_cuda(x, dy, dy_gate)
     _f32_contig(x, dy, dy_gate)
-    ws, nbytes = _wgrad_ws(fam.stem, x.device, n, ci, co, h, w, *fam.ws_args)
-    dw, db = _grads_out(weight_shape, co, x.device)
-    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, ci, co, h, w, *fam.pad_args,
-                                          ptr(ws), nbytes, current_stream_ptr()), "pv_" + who)
+    ws, nbytes = _wgrad_ws(fam.stem, x.device, *dims, *fam.ws_args)
+    dw, db = _grads_out(weight_shape, dims[2], x.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), *dims, ptr(ws), nbytes,
+                                          current_stream_ptr()), "pv_" + who)
     return dw, db
 
 
@@ -1453,7 +1458,7 @@ def _counts_bwd_weight(fam, history, flow_pred, horizon, dy, weight_shape):
                          f"{tuple(dy.shape)}")
     require_cuda(dy)
     _f32_contig(dy)
-    ws, nbytes = _wgrad_ws(fam.stem, history.device, n, 6, co, h, w, *fam.ws_args)
+    ws, nbytes = _wgrad_ws(fam.stem, history.device, n, 6, co, h, w, *fam.pad_args, *fam.ws_args)
     dw, db = _grads_out(weight_shape, co, history.device)
     check(getattr(get_lib(), "pv_" + who)(ptr(history), int(history.dtype == torch.int16), ptr(flow_pred),
                                           int(flow_pred.dtype == torch.int16), ptr(horizon), ptr(dy), ptr(dw), ptr(db), n, h,
@@ -1750,7 +1755,8 @@ def _stripe_bwd_weight(fam, history, stripe_start, dy, weight_shape, stripe_widt
                          f"{tuple(weight_shape)} / {tuple(dy.shape)}")
     require_cuda(dy)
     _f32_contig(dy)
-    ws, nbytes = _wgrad_ws(fam.stem, history.device, n, n_hist + 1, STRIPE_C_OUT, h, w, *fam.ws_args)
+    ws, nbytes = _wgrad_ws(fam.stem, history.device, n, n_hist + 1, STRIPE_C_OUT, h, w, *fam.pad_args,
+                            *fam.ws_args)
     dw, db = _grads_out(weight_shape, STRIPE_C_OUT, history.device)
     check(getattr(get_lib(), "pv_" + who)(ptr(history), ptr(stripe_start), ptr(dy), ptr(dw), ptr(db), n, n_hist, h, w,
                                           STRIPE_C_OUT, int(stripe_width), ptr(ws), nbytes, current_stream_ptr()),
@@ -1904,8 +1910,8 @@ def mse_pred_window_f32(y_hat, target, row0=0, col0=0, need_grad=True):
 
 
 # ---- notebooks/12_just_3d_conv.ipynb: Conv3d 2 -> 64 -> 128 -> 128 -> 128 -> 1, kernel (2, 3, 3), spatial padding 1, the
-# second input channel the forecast horizon (csrc/conv3d_wide_f32.hip); planes up to 128 wide.  The depth axis does not fit a
-# _ConvFamily record, so the family's one shape rule is _check_conv3d_wide and its three passes are written once below. ----
+# second input channel the forecast horizon (csrc/conv3d_wide_f32.hip); planes up to 128 wide.  A 3-D family is a _ConvFamily
+# record whose shape rule is written out (_check_conv3d_wide); its passes are _conv_fwd, _conv_bwd_data, _conv_bwd_weight. ----
 HORIZON_C_OUT = 64
 
 
@@ -1914,8 +1920,8 @@ def head_s2p1_out(side):
     return (side - 1) // 2 + 1
 
 
-_CONV2D_HEAD_S2P1 = _ConvFamily("conv2d_head_s2p1", lambda *a: _check_head(*a),
-                                lambda h, w: (head_s2p1_out(h), head_s2p1_out(w)))
+_CONV2D_HEAD_S2P1 = _conv2d_family("conv2d_head_s2p1", lambda *a: _check_head(*a),
+                                   lambda h, w: (head_s2p1_out(h), head_s2p1_out(w)))
 
 
 def _check_conv3d_wide(who, x_shape, weight_shape, padding):
@@ -1938,49 +1944,24 @@ def _check_conv3d_wide(who, x_shape, weight_shape, padding):
     return (n, ci, co, d, h, w, padding[0], 1), (n, co, d_out, h, w)
 
 
+def _conv3d_wide(padding):
+    return _ConvFamily("conv3d_wide", lambda who, x_shape, w_shape: _check_conv3d_wide(who, x_shape, w_shape, padding))
+
+
 def conv3d_wide_fwd_f32(x, weight, bias, relu=True, padding=(0, 1, 1)):
     """conv3d(x, weight, stride 1, padding (0 | 1, 1, 1)) + bias (+ ReLU): [N, 64 | 128, D, H, W] f32 -> [N, 128, D + 2 pd - 1,
     H, W]; weight [128, C_in, 2, 3, 3]."""
-    who = "conv3d_wide_fwd_f32"
-    dims, y_shape = _check_conv3d_wide(who, x.shape, weight.shape, padding)
-    _check_bias(who, bias, dims[2])
-    require_cuda(x, weight, bias)
-    _f32_contig(x, weight, bias)
-    y = torch.empty(y_shape, dtype=torch.float32, device=x.device)
-    check(get_lib().pv_conv3d_wide_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), *dims, int(relu), current_stream_ptr()),
-          "pv_" + who)
-    return y
+    return _conv_fwd(_conv3d_wide(padding), x, weight, bias, relu)
 
 
 def conv3d_wide_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape, padding=(0, 1, 1)):
     """dx of conv3d_wide_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
-    who = "conv3d_wide_bwd_data_f32"
-    dims, y_shape = _check_conv3d_wide(who, x_shape, weight.shape, padding)
-    if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
-        raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    if x_gate is not None and tuple(x_gate.shape) != tuple(x_shape):
-        raise ValueError(f"{who}: x_gate {tuple(x_shape)} expected")
-    require_cuda(dy, dy_gate, weight, x_gate)
-    _f32_contig(dy, dy_gate, weight, x_gate)
-    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
-    check(get_lib().pv_conv3d_wide_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), *dims,
-                                                current_stream_ptr()), "pv_" + who)
-    return dx
+    return _conv_bwd_data(_conv3d_wide(padding), dy, dy_gate, weight, x_gate, x_shape)
 
 
 def conv3d_wide_bwd_weight_f32(x, dy, dy_gate, weight_shape, padding=(0, 1, 1)):
     """(dw, dbias) of conv3d_wide_fwd_f32; deterministic (fixed slabs summed in order)."""
-    who = "conv3d_wide_bwd_weight_f32"
-    dims, y_shape = _check_conv3d_wide(who, x.shape, weight_shape, padding)
-    if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
-        raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    require_cuda(x, dy, dy_gate)
-    _f32_contig(x, dy, dy_gate)
-    ws, nbytes = _wgrad_ws("conv3d_wide", x.device, *dims)
-    dw, db = _grads_out(weight_shape, dims[2], x.device)
-    check(get_lib().pv_conv3d_wide_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), *dims, ptr(ws), nbytes,
-                                                  current_stream_ptr()), "pv_" + who)
-    return dw, db
+    return _conv_bwd_weight(_conv3d_wide(padding), x, dy, dy_gate, weight_shape)
 
 
 def _check_horizon(who, history, horizon, weight_shape):
@@ -2086,8 +2067,7 @@ def conv3d_head_d2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
 
 # ---- notebooks/08_multiple_historical_images_as_separate_channels.ipynb: Conv3d 1 -> 8 -> 32 -> 32, kernel (2, 3, 3), stride
 # (1, 2, 2), no padding, then ConvTranspose2d 33 -> 32 whose last input channel is the forecast horizon
-# (csrc/conv3d_s2_f32.hip); planes up to 128 wide.  As for notebook 12, the depth axis does not fit a _ConvFamily record: the
-# family's one shape rule is _check_conv3d_s2. ----
+# (csrc/conv3d_s2_f32.hip); planes up to 128 wide.  The family's shape rule is _check_conv3d_s2. ----
 CONV3D_S2_PAIRS = ((1, 8), (8, 32), (32, 32))     # (c_in, c_out) of pv_conv3d_s2_*
 CONVT_HORIZON_C = 32                              # real input channels = output channels of pv_convt2d_s2_horizon_*
 
@@ -2107,52 +2087,31 @@ def _check_conv3d_s2(who, x_shape, weight_shape):
     return (n, ci, co, d, h, w), (n, co, d - 1, s2_out(h), s2_out(w))
 
 
+def _check_conv3d_s2_dgrad(who, x_shape, weight_shape):
+    dims, y_shape = _check_conv3d_s2(who, x_shape, weight_shape)
+    if dims[1] == 1:
+        raise ValueError(f"{who}: the (1, 8) layer is the first one and has no data gradient")
+    return dims, y_shape
+
+
+_CONV3D_S2 = _ConvFamily("conv3d_s2", _check_conv3d_s2)
+
+
 def conv3d_s2_fwd_f32(x, weight, bias, relu=True):
     """conv3d(x, weight, stride (1, 2, 2)) + bias (+ ReLU): [N, C_in, D, H, W] f32 -> [N, C_out, D - 1, (H - 3) // 2 + 1, (W - 3)
     // 2 + 1]; weight [C_out, C_in, 2, 3, 3]."""
-    who = "conv3d_s2_fwd_f32"
-    dims, y_shape = _check_conv3d_s2(who, x.shape, weight.shape)
-    _check_bias(who, bias, dims[2])
-    require_cuda(x, weight, bias)
-    _f32_contig(x, weight, bias)
-    y = torch.empty(y_shape, dtype=torch.float32, device=x.device)
-    check(get_lib().pv_conv3d_s2_fwd_f32(ptr(x), ptr(weight), ptr(bias), ptr(y), *dims, int(relu), current_stream_ptr()),
-          "pv_" + who)
-    return y
+    return _conv_fwd(_CONV3D_S2, x, weight, bias, relu)
 
 
 def conv3d_s2_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
     """dx of conv3d_s2_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None).  The rows and
     columns of x the forward never reads are written as 0.  The 1 -> 8 layer has no data gradient."""
-    who = "conv3d_s2_bwd_data_f32"
-    dims, y_shape = _check_conv3d_s2(who, x_shape, weight.shape)
-    if dims[1] == 1:
-        raise ValueError(f"{who}: the (1, 8) layer is the first one and has no data gradient")
-    if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
-        raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    if x_gate is not None and tuple(x_gate.shape) != tuple(x_shape):
-        raise ValueError(f"{who}: x_gate {tuple(x_shape)} expected")
-    require_cuda(dy, dy_gate, weight, x_gate)
-    _f32_contig(dy, dy_gate, weight, x_gate)
-    dx = torch.empty(tuple(x_shape), dtype=torch.float32, device=dy.device)
-    check(get_lib().pv_conv3d_s2_bwd_data_f32(ptr(dy), ptr(dy_gate), ptr(weight), ptr(dx), ptr(x_gate), *dims,
-                                              current_stream_ptr()), "pv_" + who)
-    return dx
+    return _conv_bwd_data(_CONV3D_S2._replace(shape=_check_conv3d_s2_dgrad), dy, dy_gate, weight, x_gate, x_shape)
 
 
 def conv3d_s2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
     """(dw, dbias) of conv3d_s2_fwd_f32; deterministic (fixed slabs summed in order)."""
-    who = "conv3d_s2_bwd_weight_f32"
-    dims, y_shape = _check_conv3d_s2(who, x.shape, weight_shape)
-    if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
-        raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    require_cuda(x, dy, dy_gate)
-    _f32_contig(x, dy, dy_gate)
-    ws, nbytes = _wgrad_ws("conv3d_s2", x.device, *dims)
-    dw, db = _grads_out(weight_shape, dims[2], x.device)
-    check(get_lib().pv_conv3d_s2_bwd_weight_f32(ptr(x), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), *dims, ptr(ws), nbytes,
-                                                current_stream_ptr()), "pv_" + who)
-    return dw, db
+    return _conv_bwd_weight(_CONV3D_S2, x, dy, dy_gate, weight_shape)
 
 
 def _check_convt_horizon(who, x, horizon, weight_shape):

@@ -25,7 +25,8 @@ W, where Python's negative slice indices would count from the right edge.
 import torch
 from torch import nn
 
-from ... import lightning as pl
+from .._notebook_ae import NotebookAutoEncoder
+from .._notebook_ae import check_target_side as _check_target_side
 from ..conv3d.flow_autoencoder import FORECAST_HORIZON, HISTORICAL_SAT_IMAGES, TARGET_SAT_IMAGE  # noqa: F401
 
 STRIDE = 1
@@ -46,14 +47,13 @@ def output_side(image_side: int) -> int:
 
 def check_target_side(image_shape, target_shape) -> None:
     """image_shape: (H, W) of the history images; the target must be [B, output_side(H), output_side(W)]."""
-    want = tuple(output_side(int(side)) for side in image_shape)
-    if len(target_shape) != 3 or tuple(target_shape[1:]) != want:
-        raise ValueError(f"nb10 LitAutoEncoder: TARGET_SAT_IMAGE must be [B, {want[0]}, {want[1]}] for {image_shape[0]} x "
-                         f"{image_shape[1]}-pixel inputs, got {tuple(target_shape)}")
+    _check_target_side("nb10", output_side, image_shape, target_shape)
 
 
-class LitAutoEncoder(pl.LightningModule):
+class LitAutoEncoder(NotebookAutoEncoder):
     name = "nb10_just_conv"
+    nb = "nb10"
+    output_side, check_target_side = staticmethod(output_side), staticmethod(check_target_side)
 
     def __init__(self, lr: float = 0.001):
         super().__init__()
@@ -71,39 +71,11 @@ class LitAutoEncoder(pl.LightningModule):
 
     def forward(self, x):
         from ...conv2d_functional import nb10_just_conv_f32, stripe_start_from_horizon
-        hist_images, horizon = x[HISTORICAL_SAT_IMAGES], x[FORECAST_HORIZON]
-        if not hist_images.is_cuda:
-            raise RuntimeError("predict_pv_yield_amd LitAutoEncoder runs on the MI355X only: move the module and the "
-                               "batch to cuda (there is no CPU fallback)")
-        if hist_images.dim() != 4 or hist_images.shape[1] != N_HIST_IMAGES:
-            raise ValueError(f"nb10 LitAutoEncoder takes HISTORICAL_SAT_IMAGES [B, {N_HIST_IMAGES}, H, W], got "
-                             f"{tuple(hist_images.shape)}")
-        for side in hist_images.shape[2:]:
-            output_side(int(side))
-        horizon = horizon.to(device=hist_images.device).reshape(-1)
-        if horizon.shape[0] != hist_images.shape[0]:
-            raise ValueError(f"nb10 LitAutoEncoder takes FORECAST_HORIZON [B], got {tuple(x[FORECAST_HORIZON].shape)} for "
-                             f"{hist_images.shape[0]} examples")
+        hist_images, horizon = self.history_and_horizon(x)
         # the stripe plane is synthesised by the first layer's kernels from one start column per example
         stripe_start = stripe_start_from_horizon(horizon, STRIPE_WIDTH)
-        return nb10_just_conv_f32(hist_images.float(), stripe_start, self.conv)
+        return nb10_just_conv_f32(hist_images, stripe_start, self.conv)
 
-    def _training_or_validation_step(self, batch, is_train_step):
+    def loss(self, y_hat, y):
         from ...functional import mse_loss
-        y = batch[TARGET_SAT_IMAGE]
-        check_target_side(tuple(batch[HISTORICAL_SAT_IMAGES].shape[-2:]), y.shape)
-        y_hat = self(batch)
-        loss = mse_loss(y_hat, y.to(device=y_hat.device, dtype=torch.float32).unsqueeze(1))
-        tag = "Loss/Train" if is_train_step else "Loss/Validation"
-        self.log_dict({tag: loss}, on_step=is_train_step, on_epoch=True)
-        return loss
-
-    def training_step(self, batch, batch_idx):
-        return self._training_or_validation_step(batch, is_train_step=True)
-
-    def validation_step(self, batch, batch_idx):
-        return self._training_or_validation_step(batch, is_train_step=False)
-
-    def configure_optimizers(self):
-        from ...optim import HipAdam
-        return HipAdam(self.parameters(), lr=self.lr)
+        return mse_loss(y_hat, y.to(device=y_hat.device, dtype=torch.float32).unsqueeze(1))

@@ -18,10 +18,10 @@ root gradient, as functional.MSELossF32 does.  Deliberate differences from the n
 raise a RuntimeError), and a target whose side does not line up with the output raises a ValueError where torch would
 broadcast a 1 x 1 crop silently.
 """
-import torch
 from torch import nn
 
-from ... import lightning as pl
+from .._notebook_ae import NotebookAutoEncoder
+from .._notebook_ae import check_target_side as _check_target_side
 from ..conv3d.flow_autoencoder import (FORECAST_HORIZON, HISTORICAL_SAT_IMAGES, OPTICAL_FLOW_PREDICTIONS,  # noqa: F401
                                        TARGET_SAT_IMAGE, normalise_forecast_horizon)
 
@@ -48,15 +48,14 @@ def target_side(image_side: int) -> int:
 
 def check_target_side(image_shape, target_shape) -> None:
     """image_shape: (H, W) of the history images; the target must be [B, target_side(H), target_side(W)]."""
-    want = tuple(target_side(int(side)) for side in image_shape)
-    if len(target_shape) != 3 or tuple(target_shape[1:]) != want:
-        raise ValueError(f"nb16 LitAutoEncoder: TARGET_SAT_IMAGE must be [B, {want[0]}, {want[1]}] for {image_shape[0]} x "
-                         f"{image_shape[1]}-pixel inputs (the {CROP}-pixel crop leaves the {want[0] - 2 * CROP} x "
-                         f"{want[1] - 2 * CROP} output), got {tuple(target_shape)}")
+    _check_target_side("nb16", target_side, image_shape, target_shape,
+                       lambda want: f" (the {CROP}-pixel crop leaves the {want[0] - 2 * CROP} x {want[1] - 2 * CROP} output)")
 
 
-class LitAutoEncoder(pl.LightningModule):
+class LitAutoEncoder(NotebookAutoEncoder):
     name = "nb16_maxpool_ae"
+    nb = "nb16"
+    output_side, check_target_side = staticmethod(output_side), staticmethod(check_target_side)
 
     def __init__(self):
         super().__init__()
@@ -76,41 +75,11 @@ class LitAutoEncoder(pl.LightningModule):
 
     def forward(self, x):
         from ...conv2d_functional import nb16_autoencoder_f32
-        history, flow_pred, horizon = x[HISTORICAL_SAT_IMAGES], x[OPTICAL_FLOW_PREDICTIONS], x[FORECAST_HORIZON]
-        if not (history.is_cuda and flow_pred.is_cuda):
-            raise RuntimeError("predict_pv_yield_amd LitAutoEncoder runs on the MI355X only: move the module and the "
-                               "batch to cuda (there is no CPU fallback)")
-        if history.dim() != 4 or history.shape[1] != 4 or tuple(flow_pred.shape) != (history.shape[0],) + tuple(history.shape[2:]):
-            raise ValueError(f"nb16 LitAutoEncoder takes HISTORICAL_SAT_IMAGES [B, 4, S, S] and OPTICAL_FLOW_PREDICTIONS "
-                             f"[B, S, S], got {tuple(history.shape)} / {tuple(flow_pred.shape)}")
-        for side in history.shape[2:]:
-            output_side(int(side))
-        # raw counts stay int16 / float32: the first layer normalises them while it stages its input
-        history, flow_pred = (t if t.dtype in (torch.int16, torch.float32) else t.float() for t in (history, flow_pred))
-        horizon = horizon.to(device=history.device, dtype=torch.float32).reshape(-1)
         enc = (self.encoder_conv1, self.encoder_conv2, self.encoder_conv3, self.encoder_conv4)
         dec = (self.decoder_conv1, self.decoder_conv2, self.decoder_conv3, self.decoder_conv4)
-        return nb16_autoencoder_f32(history, flow_pred, horizon, enc, dec)
+        return nb16_autoencoder_f32(*self.counts_and_horizon(x), enc, dec)
 
-    def _training_or_validation_step(self, batch, is_train_step):
+    def loss(self, y_hat, y):
         from ...conv2d_functional import mse_crop_norm
-        y = batch[TARGET_SAT_IMAGE]
-        check_target_side(tuple(batch[HISTORICAL_SAT_IMAGES].shape[-2:]), y.shape)
-        y_hat = self(batch)
-        if y.dtype not in (torch.int16, torch.float32):
-            y = y.float()
         # normalisation and the 8-pixel crop of the target happen inside the loss kernel
-        loss = mse_crop_norm(y_hat.squeeze(1), y)
-        tag = "Loss/Train" if is_train_step else "Loss/Validation"
-        self.log_dict({tag: loss}, on_step=is_train_step, on_epoch=True)
-        return loss
-
-    def training_step(self, batch, batch_idx):
-        return self._training_or_validation_step(batch, is_train_step=True)
-
-    def validation_step(self, batch, batch_idx):
-        return self._training_or_validation_step(batch, is_train_step=False)
-
-    def configure_optimizers(self):
-        from ...optim import HipAdam
-        return HipAdam(self.parameters(), lr=0.001)
+        return mse_crop_norm(y_hat.squeeze(1), self.counts(y))

@@ -26,7 +26,8 @@ encoder_out.squeeze_() drops it together with the depth axis, after which torch.
 import torch
 from torch import nn
 
-from ... import lightning as pl
+from .._notebook_ae import NotebookAutoEncoder
+from .._notebook_ae import check_target_side as _check_target_side
 from .flow_autoencoder import FORECAST_HORIZON, HISTORICAL_SAT_IMAGES, TARGET_SAT_IMAGE  # noqa: F401
 
 STRIDE = (1, 2, 2)  # depth, height, width
@@ -55,14 +56,13 @@ def target_side(image_side: int) -> int:
 
 def check_target_side(image_shape, target_shape) -> None:
     """image_shape: (H, W) of the history images; the target must be [B, target_side(H), target_side(W)]."""
-    want = tuple(target_side(int(side)) for side in image_shape)
-    if len(target_shape) != 3 or tuple(target_shape[1:]) != want:
-        raise ValueError(f"nb08 LitAutoEncoder: TARGET_SAT_IMAGE must be [B, {want[0]}, {want[1]}] for {image_shape[0]} x "
-                         f"{image_shape[1]}-pixel inputs, got {tuple(target_shape)}")
+    _check_target_side("nb08", target_side, image_shape, target_shape)
 
 
-class LitAutoEncoder(pl.LightningModule):
+class LitAutoEncoder(NotebookAutoEncoder):
     name = "nb08_hist_depth"
+    nb = "nb08"
+    output_side, check_target_side = staticmethod(output_side), staticmethod(check_target_side)
 
     def __init__(self, lr: float = 0.001):
         super().__init__()
@@ -87,39 +87,10 @@ class LitAutoEncoder(pl.LightningModule):
 
     def forward(self, x):
         from ...conv3d_wide_functional import nb08_hist_depth_f32
-        hist_images, horizon = x[HISTORICAL_SAT_IMAGES], x[FORECAST_HORIZON]
-        if hist_images.dim() != 4 or hist_images.shape[1] != N_HIST_IMAGES:
-            raise ValueError(f"nb08 LitAutoEncoder takes HISTORICAL_SAT_IMAGES [B, {N_HIST_IMAGES}, H, W], got "
-                             f"{tuple(hist_images.shape)}")
-        if not hist_images.is_cuda:
-            raise RuntimeError("predict_pv_yield_amd LitAutoEncoder runs on the MI355X only: move the module and the "
-                               "batch to cuda (there is no CPU fallback)")
-        for side in hist_images.shape[2:]:
-            output_side(int(side))
-        horizon = horizon.to(device=hist_images.device, dtype=torch.float32).reshape(-1)
-        if horizon.shape[0] != hist_images.shape[0]:
-            raise ValueError(f"nb08 LitAutoEncoder takes FORECAST_HORIZON [B], got {tuple(x[FORECAST_HORIZON].shape)} for "
-                             f"{hist_images.shape[0]} examples")
         # the horizon channel is synthesised by the first decoder layer's kernels from one value per example
-        return nb08_hist_depth_f32(hist_images.float(), horizon, self.encoder_conv, self.decoder_conv)
+        return nb08_hist_depth_f32(*self.history_and_horizon(x, torch.float32), self.encoder_conv, self.decoder_conv)
 
-    def _training_or_validation_step(self, batch, is_train_step):
+    def loss(self, y_hat, y):
         from ...conv2d_functional import mse_pred_window
-        y = batch[TARGET_SAT_IMAGE]
-        check_target_side(tuple(batch[HISTORICAL_SAT_IMAGES].shape[-2:]), y.shape)
-        y_hat = self(batch)
         # y_hat[:, :, :-1, :-1] against the target: the window of the prediction that starts at (0, 0)
-        loss = mse_pred_window(y_hat.squeeze(1), y.to(device=y_hat.device, dtype=torch.float32), 0, 0)
-        tag = "Loss/Train" if is_train_step else "Loss/Validation"
-        self.log_dict({tag: loss}, on_step=is_train_step, on_epoch=True)
-        return loss
-
-    def training_step(self, batch, batch_idx):
-        return self._training_or_validation_step(batch, is_train_step=True)
-
-    def validation_step(self, batch, batch_idx):
-        return self._training_or_validation_step(batch, is_train_step=False)
-
-    def configure_optimizers(self):
-        from ...optim import HipAdam
-        return HipAdam(self.parameters(), lr=self.lr)
+        return mse_pred_window(y_hat.squeeze(1), y.to(device=y_hat.device, dtype=torch.float32), 0, 0)

@@ -68,6 +68,11 @@ def test_output_side_and_refusals():
         model(batch)
     with pytest.raises(ValueError, match="TARGET_SAT_IMAGE"):
         model.training_step({**batch, "TARGET_SAT_IMAGE": torch.zeros(2, 16, 16)}, 0)
+    # three or five history frames, a depth axis already there, no batch axis: refused before the device is looked at
+    z = torch.zeros
+    for hist in (z(2, 3, 16, 16), z(2, 5, 16, 16), z(2, 1, 4, 16, 16), z(4, 16, 16)):
+        with pytest.raises(ValueError, match="HISTORICAL_SAT_IMAGES"):
+            model({"HISTORICAL_SAT_IMAGES": hist, "FORECAST_HORIZON": z(2)})
     opt = model.configure_optimizers()
     assert type(opt).__name__ == "HipAdam" and opt.param_groups[0]["lr"] == 1e-3
     assert M.LitAutoEncoder(lr=1e-4).configure_optimizers().param_groups[0]["lr"] == 1e-4

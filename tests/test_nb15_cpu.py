@@ -73,6 +73,11 @@ def test_output_size_rule_and_refusals():
         model.training_step(batch, 0)
     with pytest.raises(RuntimeError, match="MI355X only"):
         model(batch)
+    # three or five history frames, a depth axis already there, no batch axis: refused before the device is looked at
+    z = torch.zeros
+    for hist in (z(2, 3, 47, 47), z(2, 5, 47, 47), z(2, 1, 4, 47, 47), z(4, 47, 47)):
+        with pytest.raises(ValueError, match="HISTORICAL_SAT_IMAGES"):
+            model({**batch, M.HISTORICAL_SAT_IMAGES: hist})
 
 
 def test_fake_datamodule_refuses_an_odd_border():
