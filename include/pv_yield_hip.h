@@ -687,6 +687,50 @@ int pv_convt2d_s2_horizon_bwd_weight_f32(const float* x, const float* horizon, c
                                          float* dbias, int32_t n, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
                                          void* stream);
 
+/* ---- notebooks/07_multiple_historical_images.ipynb: one encoder for every history frame, ConvTranspose2d 128 -> 32 ---- */
+/* (line numbers: the raw 07_...ipynb file; the LitAutoEncoder cell starts at 1356, encoder_conv is at 1364-1371, decoder_conv
+ * at 1373-1379, forward at 1381-1396.)  NCHW f32, exact f32; gates (NULL = none) and weight-gradient slabs follow the
+ * conventions of the pv_conv2d_s2_* entry points above.  The N_HIST_IMAGES = 4 calls of encoder_conv with the same weights are
+ * folded into the batch, image index frames * b + f: encoder_conv.2 / .4 are pv_conv2d_s2_* at n = frames * B (their weight
+ * gradient over all images is the sum of the per-frame gradients), and torch.cat(encoder_outs, dim=1) (07_...ipynb:1394) is
+ * the view [frames * B][32][e][f] -> [B][frames * 32][e][f].  Unsupported shapes return PV_ESIZE, null pointers and
+ * non-positive sizes PV_EINVAL, before any launch. */
+/* replaces: x[FORECAST_HORIZON].view(-1, 1, 1, 1).expand(...); hist_image = x[HISTORICAL_SAT_IMAGES][:, i:i+1]; torch.cat(
+ * (hist_image, forecast_horizon), dim=1); nn.Conv2d(2, 32, kernel_size=3, stride=STRIDE) (+ nn.ReLU() if relu) for every i,
+ * 07_...ipynb:1365, 1383-1392.  history [n][frames][h][w_img] read in place, horizon [n] (device f32): input channel 1 of image
+ * (b, f) is horizon[b] inside the plane, synthesised in the kernel (no [frames * n][2][h][w] tensor exists); w [32][2][3][3];
+ * y [n * frames][32][(h - 3) / 2 + 1][(w_img - 3) / 2 + 1]; frames >= 1, h, w_img >= 3, w_img <= 128; bias may be NULL. */
+int pv_conv2d_s2_frame_horizon_fwd_f32(const float* history, const float* horizon, const float* w, const float* bias, float* y,
+                                       int32_t n, int32_t frames, int32_t h, int32_t w_img, int32_t relu, void* stream);
+/* bytes of the weight-gradient workspace: one partial [32][2 * 9 + 1] per slab of tiles */
+int pv_conv2d_s2_frame_horizon_bwd_weight_workspace_bytes(int32_t n, int32_t frames, int32_t h, int32_t w_img, size_t* bytes);
+/* replaces: the weight and bias gradients of encoder_conv.0 summed over its frames calls (autograd of 07_...ipynb:1365,
+ * 1389-1393), re-synthesising the horizon channel as the forward does: dw [32][2][3][3], dw[:, 1] = sum_i horizon[i / frames]
+ * sum_pos dy[i]; dbias [32]; dy [n * frames][32][h_out][w_out] zeroed where dy_gate <= 0; deterministic.  The layer's input is
+ * data: there is no data gradient. */
+int pv_conv2d_s2_frame_horizon_bwd_weight_f32(const float* history, const float* horizon, const float* dy, const float* dy_gate,
+                                              float* dw, float* dbias, int32_t n, int32_t frames, int32_t h, int32_t w_img,
+                                              void* ws, size_t ws_bytes, void* stream);
+/* replaces: nn.ConvTranspose2d(CHANNELS * N_HIST_IMAGES, CHANNELS, kernel_size=3, stride=2) (+ nn.ReLU() if relu),
+ * decoder_conv.0 of 07_...ipynb:1374.  (c_in, c_out) = (128, 32) only; x [n][128][h][w], w [128][32][3][3], y [n][32][2 h + 1]
+ * [2 w + 1]; 2 w_in + 1 <= 128; bias may be NULL.  Computed as y = bias + sum_f convT(x[:, 32 f : 32 f + 32], w[32 f : 32 f +
+ * 32]), one K pass per frame into the same accumulators. */
+int pv_convt2d_s2_frames_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                                 int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of decoder_conv.0 (autograd of 07_...ipynb:1374): dx[:, 32 f : 32 f + 32] = the stride-2 conv
+ * of dy with w[32 f : 32 f + 32]; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0. */
+int pv_convt2d_s2_frames_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                                      int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+/* bytes of the workspace of pv_convt2d_s2_frames_bwd_weight_f32: one partial [128][32 * 9 + 1] per slab of tiles (the four
+ * frames' 32 rows one after the other), then one partial [32] per slab of images for the bias gradient */
+int pv_convt2d_s2_frames_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                                    size_t* bytes);
+/* replaces: the weight and bias gradients of decoder_conv.0: dw [128][32][3][3] (rows 32 f .. 32 f + 31 from frame f's
+ * channels of x), dbias [32] = the sum of dy (both with dy zeroed where dy_gate <= 0); deterministic. */
+int pv_convt2d_s2_frames_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias,
+                                        int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
+                                        size_t ws_bytes, void* stream);
+
 /* MaxPool3d over x[B*C planes][Ti,Hi,Wi]; argmax (may be NULL) = flat winner offset inside the plane stack, first
  * maximum wins, NaN propagates (torch CPU semantics).  bwd overwrites dx by gathering dy through argmax. */
 int pv_maxpool3d_fwd_f32(const float* x, float* y, int32_t* argmax, const pv_conv3d_geom* d, void* stream);

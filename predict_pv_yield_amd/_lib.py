@@ -120,6 +120,10 @@ _C3D_S2_BWD_DATA = [c_vp] * 5 + _DIMS6 + [c_vp]                      # dy, dy_ga
 _C3D_S2_BWD_WEIGHT = [c_vp] * 5 + _DIMS6 + _WORKSPACE + [c_vp]       # x, dy, dy_gate, dw, dbias, dims
 _CONVT_HORIZON_FWD = [c_vp] * 5 + [c_i32] * 3 + [c_i32, c_vp]        # x, horizon, weight, bias, y, (n, h, w), relu
 _CONVT_HORIZON_BWD_WEIGHT = [c_vp] * 6 + [c_i32] * 3 + _WORKSPACE + [c_vp]   # x, horizon, dy, dy_gate, dw, dbias, (n, h, w)
+# ... the per-frame first layer (notebook 07) takes (n, frames, h, w) after its pointers; its 128 -> 32 ConvTranspose2d is a
+# _conv2d_family
+_FRAME_HORIZON_FWD = [c_vp] * 5 + [c_i32] * 4 + [c_i32, c_vp]        # history, horizon, weight, bias, y, dims, relu
+_FRAME_HORIZON_BWD_WEIGHT = [c_vp] * 6 + [c_i32] * 4 + _WORKSPACE + [c_vp]   # history, horizon, dy, dy_gate, dw, dbias, dims
 _MSE_NORM_TAIL = [c_vp, c_vp] + _WORKSPACE + [c_vp]                  # loss, grad, workspace, stream
 
 
@@ -253,6 +257,10 @@ SIGNATURES = {
     "pv_convt2d_s2_horizon_fwd_f32": _CONVT_HORIZON_FWD,
     "pv_convt2d_s2_horizon_bwd_weight_workspace_bytes": [c_i32] * 3 + [ctypes.POINTER(c_sz)],
     "pv_convt2d_s2_horizon_bwd_weight_f32": _CONVT_HORIZON_BWD_WEIGHT,
+    "pv_conv2d_s2_frame_horizon_fwd_f32": _FRAME_HORIZON_FWD,
+    "pv_conv2d_s2_frame_horizon_bwd_weight_workspace_bytes": [c_i32] * 4 + [ctypes.POINTER(c_sz)],
+    "pv_conv2d_s2_frame_horizon_bwd_weight_f32": _FRAME_HORIZON_BWD_WEIGHT,
+    **_conv2d_family("convt2d_s2_frames", _WS_QUERY5),
     "pv_maxpool3d_fwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_maxpool3d_bwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_mse_loss_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp],

@@ -4,7 +4,8 @@ kernels of csrc/conv2d_ae_f32.hip (notebooks/16_maxpool.ipynb: Conv2d up to 128 
 stride-2 Conv2d / ConvTranspose2d kernels of csrc/conv2d_s2_f32.hip (notebooks/14_back_to_2d_conv_AE.ipynb, 15_int16.ipynb) and
 the padded 64 / 128-channel kernels, stripe first layer and stride-2 head of csrc/conv2d_wide_f32.hip (notebooks/10_just_conv.ipynb)
 and the stride-2 64 / 128-channel Conv2d / ConvTranspose2d kernels, stride-2 stripe first layer, one-channel ConvTranspose2d
-head and prediction-window MSE of csrc/conv2d_wide_s2_f32.hip (notebooks/09_horizon_represented_as_a_stripe.ipynb).
+head and prediction-window MSE of csrc/conv2d_wide_s2_f32.hip (notebooks/09_horizon_represented_as_a_stripe.ipynb) and the
+per-frame first layer and 128 -> 32 ConvTranspose2d of csrc/conv2d_frames_f32.hip (notebooks/07_multiple_historical_images.ipynb).
 
 Reference operators replaced:
   experiments/002_cnn_processes_single_sat_image_then_rnn.py
@@ -32,6 +33,11 @@ Reference operators replaced:
     ReLU after each                                                                                            :1366-1370, 1382-1397
     self.decoder_conv(out): ConvTranspose2d 128 -> 128 -> 128 stride 2 with ReLU, ConvTranspose2d 128 -> 1     :1375-1379
     F.mse_loss(y_hat[:, :, :-1, :-1], y.unsqueeze(1))                                                          :1402-1403
+  notebooks/07_multiple_historical_images.ipynb (raw lines of the .ipynb file)
+    for each of the 4 history frames: self.encoder_conv(cat(hist_image, horizon plane)): Conv2d 2 -> 32 -> 32 -> 32, all
+    stride 2, a ReLU after each; torch.cat(encoder_outs, dim=1)                                                :1364-1371, 1383-1394
+    self.decoder_conv(encoder_outs): ConvTranspose2d 128 -> 32 -> 32 stride 2 with ReLU, ConvTranspose2d 32 -> 1 :1373-1379, 1396
+    F.mse_loss(y_hat[:, :, :-1, :-1], y.unsqueeze(1))                                                          :1399-1402
 
 Gating.  As in functional.Conv3dGeneralF32, the ReLU gating of an activation gradient is moved into the kernel that
 produces it.  x_is_relu_output -> this layer's dx leaves already zeroed where x <= 0 (the lower layer's pre-activation
@@ -74,6 +80,9 @@ STRIPE_WIDE_S2_OPS = (K.conv2d_wide_s2_stripe_fwd_f32, K.conv2d_wide_s2_stripe_b
 # the raw counts of notebooks 14-16
 COUNTS_AE_OPS = (K.conv2d_ae_counts_fwd_f32, K.conv2d_ae_counts_bwd_weight_f32)
 COUNTS_S2_OPS = (K.conv2d_s2_counts_fwd_f32, K.conv2d_s2_counts_bwd_weight_f32)
+# the per-frame history plane plus horizon plane of notebook 07 (and its 128 -> 32 ConvTranspose2d, a plain family)
+FRAME_HORIZON_S2_OPS = (K.conv2d_s2_frame_horizon_fwd_f32, K.conv2d_s2_frame_horizon_bwd_weight_f32)
+CONVT2D_S2_FRAMES_OPS = (K.convt2d_s2_frames_fwd_f32, K.convt2d_s2_frames_bwd_data_f32, K.convt2d_s2_frames_bwd_weight_f32)
 # ... and of the conv with fused MaxPool2d(3): the forward returns (pooled, codes), the gradients take the codes
 CONV2D144_POOL_OPS = (K.conv2d144_pool_fwd_f32, K.conv2d144_pool_bwd_data_f32, K.conv2d144_pool_bwd_weight_f32)
 CONV2D_AE_POOL_OPS = (K.conv2d_ae_pool_fwd_f32, K.conv2d_ae_pool_bwd_data_f32, K.conv2d_ae_pool_bwd_weight_f32)
@@ -88,6 +97,8 @@ class SynthConvReLU(torch.autograd.Function):
       COUNTS_AE_OPS, COUNTS_S2_OPS          history [N, 4, H, W], flow prediction [N, H, W] (counts, int16 or f32), horizon [N] f32
       STRIPE_WIDE_OPS, STRIPE_WIDE_S2_OPS   history [N, n_hist, H, W] f32, stripe_start [N] int32 (the stripe plane is 1 on columns
                                             stripe_start[i] <= c < stripe_start[i] + stripe_width); stripe_width
+      FRAME_HORIZON_S2_OPS                  history [N, F, H, W] f32, horizon [N] f32: every frame with the horizon as a second,
+                                            constant channel, the frames folded into the batch -> [N F, 32, ..]
       conv3d_wide_functional.HORIZON_WIDE_OPS   history [N, D, H, W] f32, horizon [N] f32 as a second, constant channel"""
 
     @staticmethod
@@ -433,4 +444,20 @@ def nb09_stripe_ae_f32(history, stripe_start, encoder_conv, decoder_conv):
     return conv_chain(None, [(STRIPE_WIDE_S2_OPS, enc[0], (history, stripe_start), {"stripe_width": STRIPE_WIDTH}),
                              (CONV2D_WIDE_S2_OPS, enc[2]), (CONV2D_WIDE_S2_OPS, enc[4]),
                              (CONVT2D_WIDE_S2_OPS, dec[0]), (CONVT2D_WIDE_S2_OPS, dec[2]), (CONVT2D_HEAD_OPS, dec[4])],
+                      last_relu=False)
+
+
+# ---- notebooks/07_multiple_historical_images.ipynb -------------------------------------------------------------------------
+def nb07_multi_hist_f32(history, horizon, encoder_conv, decoder_conv):
+    """self.decoder_conv(cat([self.encoder_conv(cat(history[:, f:f + 1], horizon plane)) for f in range(4)], dim=1)) of
+    07_multiple_historical_images.ipynb:1381-1396; encoder_conv / decoder_conv = the notebook's two nn.Sequential (modules 0,
+    2, 4 nn.Conv2d / nn.ConvTranspose2d).  history [N, F, H, W], horizon [N] f32 -> [N, 1, 4 e + 5, 4 f + 5] for an encoder
+    output of e x f.  The F calls of the encoder are one pass over F N images (image F i + f), so every encoder parameter's
+    gradient is the sum over the frames, and the concatenation along the channels is the view [F N, 32, e, f] -> [N, F 32, e,
+    f] of contiguous memory."""
+    enc, dec = encoder_conv, decoder_conv
+    n, frames = history.shape[:2]
+    return conv_chain(None, [(FRAME_HORIZON_S2_OPS, enc[0], (history, horizon)), (CONV2D_S2_OPS, enc[2]), (CONV2D_S2_OPS, enc[4]),
+                             lambda y: y.view(n, frames * y.shape[1], *y.shape[2:]),
+                             (CONVT2D_S2_FRAMES_OPS, dec[0]), (CONVT2D_S2_OPS, dec[2]), (CONVT2D_HEAD_OPS, dec[4])],
                       last_relu=False)

@@ -110,7 +110,7 @@ __device__ __forceinline__ float pool3_expand(const float* dyp, const uint8_t* c
 
 // What a pass reads, by source kind.  Each file's first layer synthesises its input while staging (its own load_in /
 // stage_in arm); the other two kinds are the same everywhere.
-enum Src { SRC_PLAIN, SRC_POOLED, SRC_SAT, SRC_COUNTS, SRC_DEPTH, SRC_HORIZON };
+enum Src { SRC_PLAIN, SRC_POOLED, SRC_SAT, SRC_COUNTS, SRC_DEPTH, SRC_HORIZON, SRC_FRAME_HORIZON, SRC_CH_GROUP, SRC_FRAME_SHARED };
 
 struct In {
   // SRC_PLAIN: x[n][c_in][h][w], zeroed where gate <= 0 (gate may be null)
@@ -121,6 +121,10 @@ struct In {
   // SRC_DEPTH: x[b][c_in][t_total][h][w] read one depth slice at a time: the pass's image index is (b, z) = (i / n_frames,
   //            i % n_frames) and channel ch is the plane (ch, z + t_per_ex); zeroed where gate <= 0 (gate may be null)
   // SRC_HORIZON: x[n][c_in - 1][h][w], then horizon[n] as a constant last channel
+  // SRC_FRAME_HORIZON: x = history [b][n_frames][h][w]: the pass's image i = n_frames b + f is plane i of x (channel 0), then
+  //                    horizon[i / n_frames] as a constant second channel (c_in = 2)
+  // SRC_CH_GROUP: the c_in channels [t_per_ex, t_per_ex + c_in) of x[n][t_total][h][w]; zeroed where gate <= 0 (may be null)
+  // SRC_FRAME_SHARED: x[b][c_in][h][w] read by the n_frames images i = n_frames b + f of an example alike; gate as SRC_PLAIN
   const float* x;
   const float* gate;
   const uint8_t* codes;    // SRC_POOLED: [n][c_in][ph][pw]

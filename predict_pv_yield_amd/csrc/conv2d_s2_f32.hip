@@ -103,24 +103,7 @@ __global__ __launch_bounds__(kBlock) void conv2d_s2_scatter(Fwd a) {
   scatter_class<CINP, MT, 1, 1>(a, lds, wa, n, a0, b0, cs, sw, first_tile);
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------------
-
-// A: at most 64 output columns per band (input tile up to 129 wide), bands of equal width; rows: the staged (2 tr + 1) x (2
-// tc + 1) tile within 64 KB, about 512 positions, bands of equal height.  w_out <= 63 leaves at least one row at 32 channels.
-void gather_tiles(Fwd& a, int cinp) {
-  a.n_cb = (a.w_out + 63) / 64;
-  a.tc = (a.w_out + a.n_cb - 1) / a.n_cb;
-  const int fit = (kLdsFloats / (cinp * (2 * a.tc + 1)) - 1) / 2;
-  a.tr = std::max(1, std::min(std::min(a.h_out, fit), (512 + a.tc - 1) / a.tc));
-  a.n_rb = (a.h_out + a.tr - 1) / a.tr;
-  a.tr = (a.h_out + a.n_rb - 1) / a.n_rb;
-}
-
-template <int CINP, int MT, int SRC>
-int run_gather(const char* who, Fwd a, int n, hipStream_t st) {
-  gather_tiles(a, CINP);
-  return launch_fwd<CINP, MT, SRC, false, 2>(who, a, n, st);
-}
+// ---- host side (the gather form's tiles and both forms' Fwd are in conv2d_s2_plan_f32.h) -------------------------------
 
 // B: at most 64 output columns = 32 class columns per band; rows: the staged (tr + 1) x (tc + 1) tile within 64 KB, about
 // 512 outputs (128 class positions).
@@ -140,21 +123,6 @@ int run_scatter(const char* who, Fwd a, int n, hipStream_t st) {
   PV_REQUIRE(blocks > 0 && blocks < (1LL << 31), PV_ESIZE, "%s: grid of %lld blocks", who, blocks);
   conv2d_s2_scatter<CINP, MT><<<dim3((unsigned)blocks), dim3(kBlock), lds, st>>>(a);
   return check_launch(who);
-}
-
-// the scatter form's Fwd: out [m_out][h_out][w_out] from src; weights stored [c][m_out][3][3], taps as they stand
-Fwd scatter_args(const float* w, const float* bias, float* y, int m_out, int h_out, int w_out, int relu) {
-  Fwd a = {};
-  a.w = w, a.bias = bias, a.y = y, a.m_out = m_out, a.h_out = h_out, a.w_out = w_out;
-  a.w_sm = 9, a.w_sc = m_out * 9, a.flip = 0, a.relu = relu ? 1 : 0;
-  return a;
-}
-
-// the gather form's Fwd: out [m_out] over the conv_out grid of a [c] x h_src x w_src source, weights stored [m_out][c][3][3]
-Fwd gather_args(const float* w, const float* bias, float* y, int c, int m_out, int h_src, int w_src, int relu) {
-  Fwd a = conv_fwd_args(w, bias, y, c, m_out, h_src, w_src, relu);
-  a.h_out = conv_out(h_src), a.w_out = conv_out(w_src);
-  return a;
 }
 
 template <int XSRC>

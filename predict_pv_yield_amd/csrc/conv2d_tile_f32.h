@@ -6,7 +6,9 @@
 // at most 64 columns) and conv2d_s2_f32.hip (notebooks 14 / 15: the same two GEMMs at stride 2, STRIDE = 2, the tile staged
 // split by column parity) instantiate them; each keeps its tile planner, its argument checks and its first layer's source
 // kind.  conv3d_s2_f32.hip (notebook 08) instantiates the stride-2 weight gradient over depth slices of NCDHW tensors
-// (SRC_DEPTH) and keeps forward-like kernels of its own, which run one K pass per depth tap.  A forward-like output element's sum depends only on the (tap, channel group) order, not on the tile it
+// (SRC_DEPTH) and keeps forward-like kernels of its own, which run one K pass per depth tap.  conv2d_frames_f32.hip (notebook
+// 07) instantiates both at stride 2 over its per-frame sources (SRC_FRAME_HORIZON, SRC_FRAME_SHARED, SRC_CH_GROUP).  A
+// forward-like output element's sum depends only on the (tap, channel group) order, not on the tile it
 // falls in; the weight gradient's bits depend on the row-major position order inside an item, the items per slab and the
 // slab order (fixed slabs, each block writing its own, added in slab order: no atomics, identical bits run to run).
 #pragma once
@@ -116,6 +118,8 @@ __global__ __launch_bounds__(kBlock) void conv2d_tile_fwd(Fwd a) {
   const int sw = STRIDE == 2 ? 2 * cols + 1 : cols + 2, sr = STRIDE == 2 ? 2 * rows + 1 : rows + 2;
   const int cs = sr * sw, npos = rows * cols;
 
+  // SRC_FRAME_SHARED: image n = n_frames b + f takes the f-th slice of m_out rows of the weight (a block-uniform offset)
+  if constexpr (SRC == SRC_FRAME_SHARED) a.w += (size_t)(n % a.in.n_frames) * a.m_out * a.w_sm;
   float wa[MT][9][KS];
   load_weights<MT, KS>(wa, a, lane);
 
@@ -190,6 +194,9 @@ template <int MT, int NTW, int XSRC, int GSRC, int STRIDE = 1>
 __global__ __launch_bounds__(kBlock) void conv2d_tile_wgrad(Wg q) {
   extern __shared__ float lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // GSRC == SRC_CH_GROUP: blockIdx.y names the group of g.c_in channels of g whose rows this block sums, and a slab holds
+  // every group's rows one after the other ([n_slabs][groups * g.c_in][ncols]: one slab sum over all of them)
+  if constexpr (GSRC == SRC_CH_GROUP) q.g.t_per_ex = blockIdx.y * q.g.c_in;
   const int k9 = q.in.c_in * 9, ncols = k9 + 1, nt = (ncols + 15) / 16;
   const int sw = STRIDE == 2 ? 2 * q.tc + 1 : q.tc + 2, sr = STRIDE == 2 ? 2 * q.tr + 1 : q.tr + 2, cs = sr * sw;
   const int dps = (q.tr * q.tc + 3) & ~3;
@@ -257,7 +264,9 @@ __global__ __launch_bounds__(kBlock) void conv2d_tile_wgrad(Wg q) {
     }
   }
   // this slab's partial sums: D row m = mt * 16 + (lane / 16) * 4 + i, column = tile * 16 + lane % 16
-  float* out = q.slabs + (size_t)blockIdx.x * q.g.c_in * ncols;
+  size_t slab = blockIdx.x;
+  if constexpr (GSRC == SRC_CH_GROUP) slab = slab * gridDim.y + blockIdx.y;
+  float* out = q.slabs + slab * q.g.c_in * ncols;
 #pragma unroll
   for (int j = 0; j < NTW; ++j) {
     const int col = (wave + 4 * j) * 16 + (lane & 15);

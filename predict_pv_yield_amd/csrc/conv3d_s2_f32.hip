@@ -43,17 +43,6 @@ __device__ __forceinline__ float load_in<SRC_HORIZON>(const In& s, int n, int ch
 }
 
 constexpr int kMaxWidth = 128;
-constexpr int kClassTiles = 2;   // B: 16-position tiles of one parity class per wave (128 class positions per block)
-
-// one output element of image i = (b, z) of y [n][m_out][dst_d][h_out][w_out]: bias, ReLU, output gate
-__device__ __forceinline__ void store_out_depth(const Fwd& a, int img, int dst_d, int m, int r, int c, float acc) {
-  const int b = img / dst_d, z = img - b * dst_d;
-  const size_t off = ((((size_t)b * a.m_out + m) * dst_d + z) * a.h_out + r) * a.w_out + c;
-  float v = acc + (a.bias ? a.bias[m] : 0.0f);
-  if (a.relu) v = v > 0.0f ? v : 0.0f;
-  if (a.out_gate && !(a.out_gate[off] > 0.0f)) v = 0.0f;
-  a.y[off] = v;
-}
 
 // A.  Block = (image (b, z), row band, column band) of tr x tc <= 64 TPW output positions; wave w owns the 16-position tiles
 // w, w + 4, ... (TPW at most) and keeps their accumulators over both depth-tap passes.  CP = the real input channels rounded
@@ -125,70 +114,7 @@ __global__ __launch_bounds__(kBlock) void conv3d_s2_gather(Fwd a, int dst_d) {
   }
 }
 
-// B.  One parity class (PR, PC) of the block: its 16-position tiles continue the numbering of the classes before it and are
-// dealt to the waves in turn, as in conv2d_s2_f32.hip; a wave's tiles of the class are its slots 0 .. kClassTiles - 1.  STORE
-// = false: one pass's products are added into the slots; STORE = true: the slots are written out.
-template <int CP, int MT, int PR, int PC, bool STORE>
-__device__ __forceinline__ void scatter_class3(const Fwd& a, const float* lds, const float (&wa)[MT][9][CP / 4], int img,
-                                               int dst_d, int a0, int b0, int cs, int sw, int& first_tile,
-                                               acc4 (&acc)[kClassTiles][MT]) {
-  constexpr int KS = CP / 4;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // class positions inside the block: 2 a + PR < h_out, 2 b + PC < w_out
-  const int rows = max(0, min(a.tr, (a.h_out - PR + 1) / 2 - a0)), cols = max(0, min(a.tc, (a.w_out - PC + 1) / 2 - b0));
-  const int npos = rows * cols, tiles = (npos + 15) / 16;
-  const int start = (wave - first_tile) & 3;
-  first_tile += tiles;
-#pragma unroll
-  for (int ti = 0; ti < kClassTiles; ++ti) {
-    const int t = start + 4 * ti;
-    if (t >= tiles) continue;
-    const int p = t * 16 + (lane & 15);
-    const bool valid = p < npos;
-    const int pp = valid ? p : 0;
-    const int la = pp / cols, lb = pp - la * cols;
-    if constexpr (STORE) {
-      if (!valid) continue;
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int m = mt * 16 + (lane >> 4) * 4 + i;
-          if (m < a.m_out) store_out_depth(a, img, dst_d, m, 2 * (a0 + la) + PR, 2 * (b0 + lb) + PC, acc[ti][mt][i]);
-        }
-    } else {
-      const float* src = lds + (lane >> 4) * cs + (la + 1) * sw + lb + 1;
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh) {
-        if ((kh & 1) != PR) continue;
-#pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-          if ((kw & 1) != PC) continue;
-          const float* st = src - (kh >> 1) * sw - (kw >> 1);   // source (a - kh / 2, b - kw / 2)
-#pragma unroll
-          for (int s = 0; s < KS; ++s) {
-            const float bv = st[s * 4 * cs];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-              acc[ti][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[mt][kh * 3 + kw][s], bv, acc[ti][mt], 0, 0, 0);
-          }
-        }
-      }
-    }
-  }
-}
-
-template <int CP, int MT, bool STORE>
-__device__ __forceinline__ void scatter_classes3(const Fwd& a, const float* lds, const float (&wa)[MT][9][CP / 4], int img,
-                                                 int dst_d, int a0, int b0, int cs, int sw,
-                                                 acc4 (&acc)[4][kClassTiles][MT]) {
-  int first_tile = 0;
-  scatter_class3<CP, MT, 0, 0, STORE>(a, lds, wa, img, dst_d, a0, b0, cs, sw, first_tile, acc[0]);
-  scatter_class3<CP, MT, 0, 1, STORE>(a, lds, wa, img, dst_d, a0, b0, cs, sw, first_tile, acc[1]);
-  scatter_class3<CP, MT, 1, 0, STORE>(a, lds, wa, img, dst_d, a0, b0, cs, sw, first_tile, acc[2]);
-  scatter_class3<CP, MT, 1, 1, STORE>(a, lds, wa, img, dst_d, a0, b0, cs, sw, first_tile, acc[3]);
-}
-
+// B.  scatter_classes3 of conv2d_s2_plan_f32.h, one pass per depth tap.
 // Block = (image, row band, column band) of tr x tc <= 128 class-grid positions.  SRC_DEPTH (NKD = 2): the image is (b, z),
 // z < dst_d = d_in, the source dy [n][c][d_out][..] read at depth z - kd (in.n_frames = d_in, in.t_total = d_out); a pass
 // whose depth is outside [0, d_out) is skipped.  SRC_HORIZON (NKD = 1, dst_d = 1): one pass over the 33 channels.
@@ -261,21 +187,12 @@ int run_gather3(const char* who, Fwd a, int images, int dst_d, hipStream_t st) {
   return check_launch(who);
 }
 
-// B: at most 64 output columns = 32 class columns per band; rows: the staged (tr + 1) x (tc + 1) tile within 64 KB and at
-// most 64 kClassTiles class positions
+// B: the tiles of scatter_slot_tiles
 template <int CP, int MT, int SRC, int NKD>
 int run_scatter3(const char* who, Fwd a, int images, int dst_d, hipStream_t st) {
-  const int ga = (a.h_out + 1) / 2, gb = (a.w_out + 1) / 2;   // class grid of the even rows / columns (the larger one)
-  a.n_cb = (a.w_out + 63) / 64;
-  a.tc = (gb + a.n_cb - 1) / a.n_cb;
-  a.n_cb = (gb + a.tc - 1) / a.tc;
-  const int fit = kLdsFloats / (CP * (a.tc + 1)) - 1;
-  a.tr = std::max(1, std::min(std::min(ga, fit), 64 * kClassTiles / a.tc));
-  a.n_rb = (ga + a.tr - 1) / a.tr;
-  a.tr = (ga + a.n_rb - 1) / a.n_rb;
-  const size_t lds = (size_t)CP * (a.tr + 1) * (a.tc + 1) * sizeof(float);
-  PV_REQUIRE(lds <= kLdsFloats * sizeof(float) && a.tr * a.tc <= 64 * kClassTiles, PV_ESIZE,
-             "%s: no tile of %d x %d within the LDS budget", who, a.tr, a.tc);
+  size_t lds;
+  int rc = scatter_slot_tiles(who, a, CP, lds);
+  if (rc) return rc;
   const long long blocks = (long long)images * a.n_rb * a.n_cb;
   PV_REQUIRE(blocks > 0 && blocks < (1LL << 31), PV_ESIZE, "%s: grid of %lld blocks", who, blocks);
   conv3d_s2_scatter<CP, MT, SRC, NKD><<<dim3((unsigned)blocks), dim3(kBlock), lds, st>>>(a, dst_d);

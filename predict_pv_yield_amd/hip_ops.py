@@ -1073,7 +1073,8 @@ def conv3d_general_bwd_weight_f32(x, dy, y_mask, weight_shape, stride=1, padding
 # experiments/001 (conv2d144_*, 144 -> 144, + MaxPool2d(3)), notebooks/16_maxpool.ipynb (conv2d_ae_* / convt2d_ae_*, + pool,
 # cropped normalised MSE), notebooks/14, 15 (conv2d_s2_* / convt2d_s2_*, stride 2, windowed normalised MSE), notebooks/10
 # (conv2d_wide_*, conv2d_head_s2_*: padded 64 / 128 channels, stripe first layer) and notebooks/09 (conv2d_wide_s2_*,
-# convt2d_wide_s2_*, convt2d_head_*: the same widths at stride 2, MSE over a window of the prediction).
+# convt2d_wide_s2_*, convt2d_head_*: the same widths at stride 2, MSE over a window of the prediction); further down,
+# notebooks/07 (conv2d_s2_frame_horizon_*, convt2d_s2_frames_*: the per-frame first layer and ConvTranspose2d 128 -> 32).
 #
 # A family of entry points is described once, by a _ConvFamily record (its plain forward / data gradient / weight gradient)
 # and, where it has them, a _PoolFamily record (the same three passes with MaxPool2d(3) fused).  _conv_fwd, _conv_bwd_data,
@@ -2156,6 +2157,91 @@ def convt2d_s2_horizon_bwd_weight_f32(x, horizon, dy, dy_gate, weight_shape):
     check(get_lib().pv_convt2d_s2_horizon_bwd_weight_f32(ptr(x), ptr(horizon), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, h, w,
                                                          ptr(ws), nbytes, current_stream_ptr()), "pv_" + who)
     return dw, db
+
+
+# ---- notebooks/07_multiple_historical_images.ipynb: one Conv2d 2 -> 32 -> 32 -> 32 stride-2 encoder applied to every history
+# frame with the same weights (the frames folded into the batch, image FRAMES b + f), then ConvTranspose2d 128 -> 32 over the
+# concatenated encoder outputs (csrc/conv2d_frames_f32.hip); planes up to 128 wide.  Layers 2 and 3 are conv2d_s2_* on
+# [FRAMES B, 32, ..].  The shape rules are _check_frame_horizon and _check_convt_frames. ----
+FRAME_C = 32                                      # CHANNELS: the encoder's width, per frame
+HIST_FRAMES = 4                                   # N_HIST_IMAGES
+CONVT_FRAMES_PAIR = (HIST_FRAMES * FRAME_C, FRAME_C)      # (c_in, c_out) of pv_convt2d_s2_frames_*
+
+
+def _check_frame_horizon(who, history, horizon, weight_shape):
+    """The shape rule of pv_conv2d_s2_frame_horizon_*: history [N, F, H, W], horizon [N], weight [32, 2, 3, 3].  Returns the
+    entry points' (n, frames, h, w) and the output's shape."""
+    if history.dim() != 4 or history.shape[1] < 1:
+        raise ValueError(f"{who}: history [N, F >= 1, H, W] expected, got {tuple(history.shape)}")
+    n, frames, h, w = (int(v) for v in history.shape)
+    if tuple(horizon.shape) != (n,):
+        raise ValueError(f"{who}: horizon [{n}] expected, got {tuple(horizon.shape)}")
+    if tuple(weight_shape) != (FRAME_C, 2, 3, 3):
+        raise ValueError(f"{who}: weight [{FRAME_C}, 2, 3, 3] expected, got {tuple(weight_shape)}")
+    if min(h, w) < 3 or w > WIDE_MAX_W:
+        raise ValueError(f"{who}: planes of 3 to {WIDE_MAX_W} columns expected, got {h} x {w}")
+    return (n, frames, h, w), (n * frames, FRAME_C, s2_out(h), s2_out(w))
+
+
+def conv2d_s2_frame_horizon_fwd_f32(history, horizon, weight, bias, relu=True):
+    """conv2d(cat(history[:, f:f + 1], horizon plane), weight, stride 2) + bias (+ ReLU) for every frame f at once: history [N,
+    F, H, W] f32 read in place, the second input channel of example i is horizon[i] everywhere -> [N F, 32, (H - 3) // 2 + 1,
+    (W - 3) // 2 + 1] with image index F i + f; weight [32, 2, 3, 3]."""
+    who = "conv2d_s2_frame_horizon_fwd_f32"
+    dims, y_shape = _check_frame_horizon(who, history, horizon, weight.shape)
+    _check_bias(who, bias, FRAME_C)
+    require_cuda(history, horizon, weight, bias)
+    _f32_contig(history, horizon, weight, bias)
+    y = torch.empty(y_shape, dtype=torch.float32, device=history.device)
+    check(get_lib().pv_conv2d_s2_frame_horizon_fwd_f32(ptr(history), ptr(horizon), ptr(weight), ptr(bias), ptr(y), *dims,
+                                                       int(relu), current_stream_ptr()), "pv_" + who)
+    return y
+
+
+def conv2d_s2_frame_horizon_bwd_weight_f32(history, horizon, dy, weight_shape, dy_gate=None):
+    """(dw [32, 2, 3, 3], dbias [32]) of conv2d_s2_frame_horizon_fwd_f32's conv, summed over its frames, from dy [N F, 32, ..]
+    zeroed where dy_gate <= 0 (may be None); deterministic."""
+    who = "conv2d_s2_frame_horizon_bwd_weight_f32"
+    dims, y_shape = _check_frame_horizon(who, history, horizon, weight_shape)
+    _check_dy(who, dy, dy_gate, y_shape)
+    require_cuda(history, horizon, dy, dy_gate)
+    _f32_contig(history, horizon, dy, dy_gate)
+    ws, nbytes = _wgrad_ws("conv2d_s2_frame_horizon", history.device, *dims)
+    dw, db = _grads_out(weight_shape, FRAME_C, history.device)
+    check(get_lib().pv_conv2d_s2_frame_horizon_bwd_weight_f32(ptr(history), ptr(horizon), ptr(dy), ptr(dy_gate), ptr(dw),
+                                                              ptr(db), *dims, ptr(ws), nbytes, current_stream_ptr()),
+          "pv_" + who)
+    return dw, db
+
+
+def _check_convt_frames(who, x_shape, weight_shape):
+    """The shape rule of pv_convt2d_s2_frames_*: x [N, 128, H, W], weight [128, 32, 3, 3]."""
+    ci, co = CONVT_FRAMES_PAIR
+    if not (len(x_shape) == 4 and x_shape[1] == ci and tuple(weight_shape) == (ci, co, 3, 3)):
+        raise ValueError(f"{who}: x [N, {ci}, H, W] and weight [{ci}, {co}, 3, 3] expected, got {tuple(x_shape)} / "
+                         f"{tuple(weight_shape)}")
+    if min(x_shape[2:]) < 1 or 2 * x_shape[3] + 1 > WIDE_MAX_W:
+        raise ValueError(f"{who}: a non-empty plane whose output is at most {WIDE_MAX_W} columns wide expected, got "
+                         f"{x_shape[2]} x {x_shape[3]}")
+
+
+_CONVT2D_S2_FRAMES = _conv2d_family("convt2d_s2_frames", _check_convt_frames, lambda h, w: (2 * h + 1, 2 * w + 1), c_out_axis=1)
+
+
+def convt2d_s2_frames_fwd_f32(x, weight, bias, relu=True):
+    """conv_transpose2d(x, weight, stride 2) + bias (+ ReLU): [N, 128, H, W] f32 -> [N, 32, 2 H + 1, 2 W + 1], 2 W + 1 <= 128;
+    weight [128, 32, 3, 3]."""
+    return _conv_fwd(_CONVT2D_S2_FRAMES, x, weight, bias, relu)
+
+
+def convt2d_s2_frames_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+    """dx of convt2d_s2_frames_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
+    return _conv_bwd_data(_CONVT2D_S2_FRAMES, dy, dy_gate, weight, x_gate, x_shape)
+
+
+def convt2d_s2_frames_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+    """(dw [128, 32, 3, 3], dbias [32]) of convt2d_s2_frames_fwd_f32; deterministic (fixed slabs summed in order)."""
+    return _conv_bwd_weight(_CONVT2D_S2_FRAMES, x, dy, dy_gate, weight_shape)
 
 
 def maxpool3d_fwd_f32(x, kernel=3, stride=None, padding=0):

@@ -40,14 +40,13 @@ class NotebookAutoEncoder(pl.LightningModule):
         if hist_images.dim() != 4 or hist_images.shape[1] != N_HIST_IMAGES:
             raise ValueError(f"{self.nb} LitAutoEncoder takes HISTORICAL_SAT_IMAGES [B, {N_HIST_IMAGES}, H, W], got "
                              f"{tuple(hist_images.shape)}")
+        if horizon.numel() != hist_images.shape[0]:       # a shape like the one above: refused before the device is looked at
+            raise ValueError(f"{self.nb} LitAutoEncoder takes FORECAST_HORIZON [B], got {tuple(horizon.shape)} for "
+                             f"{hist_images.shape[0]} examples")
         _require_device(hist_images)
         for side in hist_images.shape[2:]:
             self.output_side(int(side))
-        horizon = horizon.to(device=hist_images.device, dtype=horizon_dtype).reshape(-1)
-        if horizon.shape[0] != hist_images.shape[0]:
-            raise ValueError(f"{self.nb} LitAutoEncoder takes FORECAST_HORIZON [B], got {tuple(x[FORECAST_HORIZON].shape)} for "
-                             f"{hist_images.shape[0]} examples")
-        return hist_images.float(), horizon
+        return hist_images.float(), horizon.to(device=hist_images.device, dtype=horizon_dtype).reshape(-1)
 
     def counts_and_horizon(self, x):
         """(history [B, 4, S, S], flow prediction [B, S, S], horizon [B] f32) of a batch of raw counts, which stay int16 /

@@ -1,0 +1,387 @@
+"""GPU: the weight-shared per-frame encoder's first layer and the 128 -> 32 ConvTranspose2d of
+notebooks/07_multiple_historical_images.ipynb (csrc/conv2d_frames_f32.hip, conv2d_functional,
+models/conv2d/nb07_multi_hist.py) against float64 on the CPU.
+
+Tolerances are the project's own for exact-f32 conv kernels (conv2d_f32_helpers): ELEM_TOL per element relative to the
+element's float64 sum of |products|, NORM_TOL relative norm for reductions.  The references are float64 F.conv2d on the
+explicitly built [F B, 2, H, W] input, torch.nn.grad.conv2d_weight, F.conv_transpose2d and its float64 autograd (this torch
+has no torch.nn.grad function for the transposed form's weight gradient).
+
+Parameters after three Adam steps (golden), the bounds of tests/test_gpu_nb08.py: Adam's step is about lr = 1e-3 per step
+whatever the gradient's size, so 99 % of the elements of every tensor must agree to 1e-5; the remaining elements are those
+whose gradient is ~ 0 and may take either sign in two correct implementations: 3 * 2e-3 (+ 1e-6) in all.
+"""
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import nb07_reference as R
+from conv2d_f32_helpers import NORM_TOL, ROOT, _ops, _rel, _to, _within
+from predict_pv_yield_amd.models.conv2d.nb07_multi_hist import LitAutoEncoder, target_side      # absent: the file fails at import
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "nb07_small.npz")
+# (batch, height, width) of the history frames: one output; an unread row and column; odd and even sides; one block of nine
+# 16-position tiles over its four waves; the model's second size, the only one whose forward takes several row bands (31
+# rows of outputs as 16 + 15); full width, 7 x 63 outputs: one block in the forward, two row bands (the 384-position limit) in
+# the weight gradient
+FIRST_SHAPES = [(1, 3, 3), (2, 4, 4), (3, 7, 12), (2, 26, 26), (1, 63, 63), (2, 15, 128)]
+# (batch, height, width) of the 128 -> 32 ConvTranspose2d's input; (2, 5, 60) -> 11 x 121 takes two column bands
+FRAMES_SHAPES = [(1, 1, 1), (2, 2, 5), (3, 7, 7), (1, 15, 15), (2, 5, 60), (2, 40, 3)]
+GATES = ((True, True), (False, False))      # (dy_gate, x_gate): every gradient with and without its gates
+HORIZONS = [0.0, -1.3, 0.7]                 # per example distinct: zero and both signs
+
+
+def _g(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _randn(g, *shape, scale=1.0):
+    return torch.randn(*shape, generator=g) * scale
+
+
+def _out(s):
+    return (s - 3) // 2 + 1
+
+
+# ---- 1. the first layer: every frame with the horizon as a second channel, folded into the batch -------------------------
+def _first_layer(device, n, frames, h, w, horizon, seed):
+    K = _ops()
+    g = _g(seed)
+    history = _randn(g, n, frames, h, w)
+    wt, b = _randn(g, 32, 2, 3, 3, scale=18 ** -0.5), _randn(g, 32, scale=0.1)
+    x64 = R.folded_input64(history, horizon)
+    assert tuple(x64.shape) == (n * frames, 2, h, w)
+    for i in range(n * frames):       # image F b + f: frame f of example b, then that example's horizon
+        assert torch.equal(x64[i, 0], history[i // frames, i % frames].double()) and (x64[i, 1] == horizon[i // frames].double()).all()
+    w64, b64 = wt.double(), b.double()
+    pre = F.conv2d(x64, w64, b64, stride=2)
+    absref = F.conv2d(x64.abs(), w64.abs(), b64.abs(), stride=2)
+    assert tuple(pre.shape) == (n * frames, 32, _out(h), _out(w))
+    hd, zd, wd, bd = history.to(device), horizon.to(device), wt.to(device), b.to(device)
+    y = K.conv2d_s2_frame_horizon_fwd_f32(hd, zd, wd, bd, relu=True)
+    assert tuple(y.shape) == tuple(pre.shape)
+    _within(y, pre.relu(), absref, what="forward relu")
+    _within(K.conv2d_s2_frame_horizon_fwd_f32(hd, zd, wd, bd, relu=False), pre, absref, what="forward without relu")
+    _within(K.conv2d_s2_frame_horizon_fwd_f32(hd, zd, wd, None, relu=False), pre - b64.view(1, -1, 1, 1), absref,
+            what="forward without bias")
+    dy, dy_gate = _randn(g, *pre.shape), _randn(g, *pre.shape)
+    for use_dg in (True, False):
+        dyg = dy.double() * (dy_gate > 0) if use_dg else dy.double()
+        dw, db = K.conv2d_s2_frame_horizon_bwd_weight_f32(hd, zd, dy.to(device), (32, 2, 3, 3),
+                                                          dy_gate=dy_gate.to(device) if use_dg else None)
+        assert tuple(dw.shape) == (32, 2, 3, 3) and tuple(db.shape) == (32,)
+        dw64 = torch.nn.grad.conv2d_weight(x64, (32, 2, 3, 3), dyg, stride=2)
+        for ch, what in ((0, "history channel"), (1, "horizon channel")):      # each on its own: neither hides in the other's norm
+            if ch == 1 and not horizon.any():
+                assert (dw[:, 1] == 0).all(), "all horizons 0: the horizon channel's gradient is exactly 0"
+                continue
+            err = _rel(dw[:, ch], dw64[:, ch])
+            assert err <= NORM_TOL, (use_dg, what, err)
+        assert _rel(db, dyg.sum((0, 2, 3))) <= NORM_TOL
+
+
+@pytest.mark.parametrize("n, h, w", FIRST_SHAPES)
+def test_first_layer_against_float64(device, n, h, w):
+    _first_layer(device, n, 4, h, w, torch.tensor(HORIZONS[:n]) if n > 1 else torch.tensor([-0.4]), 700 + w + h)
+
+
+def test_first_layer_with_one_frame(device):
+    _first_layer(device, 3, 1, 7, 12, torch.tensor(HORIZONS), 731)
+
+
+def test_first_layer_with_all_horizons_zero(device):
+    """dw[:, 1] is exactly 0, and the history channel's gradient is unchanged by it."""
+    _first_layer(device, 3, 4, 7, 12, torch.zeros(3), 732)
+
+
+# ---- 2. ConvTranspose2d 128 -> 32 along the frame seam -------------------------------------------------------------------
+@pytest.mark.parametrize("n, h, w", FRAMES_SHAPES)
+def test_frames_conv_transpose_against_float64(device, n, h, w):
+    K = _ops()
+    g = _g(1100 + w + h)
+    x = _randn(g, n, 128, h, w)
+    wt, b = _randn(g, 128, 32, 3, 3, scale=(9 * 128) ** -0.5), _randn(g, 32, scale=0.1)
+    xd, wd, bd = x.to(device), wt.to(device), b.to(device)
+    x64, w64, b64 = x.double().requires_grad_(True), wt.double().requires_grad_(True), b.double().requires_grad_(True)
+    pre = F.conv_transpose2d(x64, w64, b64, stride=2)
+    absref = F.conv_transpose2d(x64.detach().abs(), w64.detach().abs(), b64.detach().abs(), stride=2)
+    for relu in (True, False):
+        y = K.convt2d_s2_frames_fwd_f32(xd, wd, bd, relu=relu)
+        assert tuple(y.shape) == (n, 32, 2 * h + 1, 2 * w + 1)
+        _within(y, pre.detach().relu() if relu else pre.detach(), absref, what=f"frames convT forward relu={relu}")
+    _within(K.convt2d_s2_frames_fwd_f32(xd, wd, None, relu=False), pre.detach() - b64.detach().view(1, -1, 1, 1), absref,
+            what="frames convT forward without bias")
+    dy, dy_gate, x_gate = _randn(g, *pre.shape), _randn(g, *pre.shape), _randn(g, *x.shape)
+    for use_dg, use_xg in GATES:
+        dyg = dy.double() * (dy_gate > 0) if use_dg else dy.double()
+        gate_d = dy_gate.to(device) if use_dg else None
+        for t in (x64, w64, b64):
+            t.grad = None
+        pre.backward(dyg, retain_graph=True)
+        dw, db = K.convt2d_s2_frames_bwd_weight_f32(xd, dy.to(device), gate_d, tuple(wt.shape))
+        assert tuple(dw.shape) == (128, 32, 3, 3) and tuple(db.shape) == (32,)
+        dx = K.convt2d_s2_frames_bwd_data_f32(dy.to(device), gate_d, wd, x_gate.to(device) if use_xg else None, tuple(x.shape))
+        assert tuple(dx.shape) == tuple(x.shape)
+        dx64 = x64.grad * (x_gate > 0) if use_xg else x64.grad
+        for f in range(4):      # per frame slice: a dropped, doubled or swapped frame shows
+            rows = slice(32 * f, 32 * f + 32)
+            err = _rel(dw[rows], w64.grad[rows])
+            assert err <= NORM_TOL, (use_dg, f, err)
+            absdx = F.conv2d(dyg.abs(), w64.detach()[rows].abs(), stride=2)
+            _within(dx[:, rows], dx64[:, rows], absdx, what=f"frames convT dx frame {f} gates {use_dg} {use_xg}")
+        assert _rel(db, b64.grad) <= NORM_TOL, (use_dg, _rel(db, b64.grad))
+
+
+@pytest.mark.parametrize("f", range(4))
+def test_frames_conv_transpose_of_one_frame_is_the_32_channel_layer(device, f):
+    """x nonzero in frame f only: the forward is pv_convt2d_s2_fwd_f32 on that slice and weight slice (the other frames'
+    passes add exact zeros)."""
+    K = _ops()
+    g = _g(1200 + f)
+    n, h, w = 2, 7, 7
+    rows = slice(32 * f, 32 * f + 32)
+    x = torch.zeros(n, 128, h, w)
+    x[:, rows] = _randn(g, n, 32, h, w)
+    wt, b = _randn(g, 128, 32, 3, 3, scale=(9 * 128) ** -0.5), _randn(g, 32, scale=0.1)
+    xd, wd, bd = x.to(device), wt.to(device), b.to(device)
+    y = K.convt2d_s2_frames_fwd_f32(xd, wd, bd, relu=False)
+    one = K.convt2d_s2_fwd_f32(xd[:, rows].contiguous(), wd[rows].contiguous(), bd, relu=False)
+    x64, w64, b64 = x.double()[:, rows], wt.double()[rows], b.double()
+    absref = F.conv_transpose2d(x64.abs(), w64.abs(), b64.abs(), stride=2)
+    _within(y, one.double().cpu(), absref, what=f"frame {f} against the 32 -> 32 layer")
+    _within(y, F.conv_transpose2d(x64, w64, b64, stride=2), absref, what=f"frame {f} against float64")
+
+
+# ---- 3. the model against the golden fixture ---------------------------------------------------------------------------
+def _model_cls():
+    return LitAutoEncoder
+
+
+def _load_model(device, init):
+    model = _model_cls()()
+    model.load_state_dict(init)
+    return model.to(device)
+
+
+@pytest.mark.parametrize("tag", ["a", "b"])
+def test_model_against_golden(device, tag):
+    gold = np.load(GOLDEN)
+    batch, init = R.golden_case(gold, tag)
+    model = _load_model(device, init)
+    dbatch = _to(batch, device)
+    y_hat = model(dbatch)
+    assert tuple(y_hat.shape) == tuple(gold[f"{tag}/y_hat"].shape)
+    assert _rel(y_hat.detach(), gold[f"{tag}/y_hat"]) <= NORM_TOL
+    opt = model.configure_optimizers()
+    losses = []
+    for step in range(3):
+        opt.zero_grad(set_to_none=True)
+        loss = model.training_step(dbatch, 0)
+        loss.backward()
+        if step == 0:
+            for k, p in model.named_parameters():
+                err = _rel(p.grad, gold[f"{tag}/grad/{k}"])
+                print(f"{tag} grad {k}: rel {err:.3e} (bound {NORM_TOL})")
+                assert err <= NORM_TOL, (k, err)
+        opt.step()
+        losses.append(loss.item())
+    for got, want in zip(losses, gold[f"{tag}/losses"]):
+        assert abs(got - want) <= 1e-5 * want, (losses, gold[f"{tag}/losses"])
+    for k, p in model.named_parameters():
+        want = torch.from_numpy(gold[f"{tag}/step3/{k}"]).double()
+        err = (p.detach().cpu().double() - want).abs()
+        moved = (want - init[k].double()).abs()
+        q99 = err.flatten().sort().values[int(0.99 * (err.numel() - 1))].item()
+        print(f"{tag} step3 {k}: max {err.max().item():.3e} 99% {q99:.3e} moved median {moved.median().item():.3e}")
+        assert moved.median().item() >= 1e-4, k       # the fixture's parameters did move (three steps of lr = 1e-3)
+        assert q99 <= 1e-5, (k, q99)
+        assert err.max().item() <= 3 * 2e-3 + 1e-6, k
+
+
+# ---- 4. full size ------------------------------------------------------------------------------------------------------
+def _full_batch(seed, b=4, s=128):
+    g = _g(seed)
+    t = target_side(s)
+    return {"HISTORICAL_SAT_IMAGES": _randn(g, b, 4, s, s), "FORECAST_HORIZON": _randn(g, b),
+            "TARGET_SAT_IMAGE": _randn(g, b, t, t)}
+
+
+@pytest.mark.parametrize("b, s, out", [(4, 128, 65), (2, 15, 9)])
+def test_full_size_forward_and_loss(device, b, s, out):
+    """The notebook's size (S = 128 -> [B, 1, 65, 65]) and the smallest image the model takes (15 -> 1 x 1 inside)."""
+    torch.manual_seed(5)
+    model = _model_cls()().to(device)
+    batch = _full_batch(50, b, s)
+    y_hat = model(_to(batch, device))
+    assert tuple(y_hat.shape) == (b, 1, out, out)
+    loss = model.training_step(_to(batch, device), 0)
+    p = R.params64(model.state_dict(), requires_grad=False)
+    y64 = R.forward64(p, batch)
+    assert _rel(y_hat.detach(), y64) <= NORM_TOL
+    ref = R.loss64(y64, batch["TARGET_SAT_IMAGE"]).item()
+    assert abs(loss.item() - ref) <= 1e-5 * ref, (loss.item(), ref)
+
+
+def test_a_batch_of_one(device):
+    torch.manual_seed(6)
+    model = _model_cls()().to(device)
+    batch = _to(_full_batch(51, 1, 31), device)
+    assert tuple(model(batch).shape) == (1, 1, 17, 17)
+    assert torch.isfinite(model.training_step(batch, 0))
+
+
+# ---- 5. determinism and HIP-graph replay -------------------------------------------------------------------------------
+def _train(device, steps, seed=3, b=4):
+    torch.manual_seed(seed)
+    model = _model_cls()().to(device)
+    opt = model.configure_optimizers()
+    losses = []
+    for i in range(steps):
+        batch = _to(_full_batch(60 + i, b=b), device)
+        opt.zero_grad(set_to_none=True)
+        loss = model.training_step(batch, i)
+        loss.backward()
+        opt.step()
+        losses.append(loss.item())
+    return model, losses
+
+
+def test_train_steps_are_deterministic(device):
+    m1, l1 = _train(device, 3)
+    m2, l2 = _train(device, 3)
+    assert l1 == l2
+    for (k, p), q in zip(m1.named_parameters(), m2.parameters()):
+        assert torch.equal(p, q), k
+
+
+def test_train_step_replays_as_a_hip_graph(device):
+    from predict_pv_yield_amd.graphs import GraphedTrainStep
+    from predict_pv_yield_amd.optim import HipAdam
+    batches = [_to(_full_batch(70 + s), device) for s in range(3)]
+
+    def make(capturable):
+        torch.manual_seed(11)
+        model = _model_cls()().to(device)
+        return model, HipAdam(model.parameters(), lr=0.001, capturable=capturable)
+
+    model_e, opt_e = make(False)
+    model_g, opt_g = make(True)
+    step = GraphedTrainStep(model_g, opt_g, batches[0], warmup=2)
+    try:
+        for _ in range(2):
+            opt_e.zero_grad(set_to_none=True)
+            model_e.training_step(batches[0], 0).backward()
+            opt_e.step()
+        for i in range(5):
+            opt_e.zero_grad(set_to_none=True)
+            loss = model_e.training_step(batches[i % 3], 0)
+            loss.backward()
+            opt_e.step()
+            assert float(step(batches[i % 3])) == float(loss), f"step {i}"
+        for p, q in zip(model_g.parameters(), model_e.parameters()):
+            assert torch.equal(p, q)
+    finally:
+        step.close()
+
+
+# ---- 6. Trainer.fit on the fake datamodule -----------------------------------------------------------------------------
+def test_trainer_fit_on_the_fake_datamodule(device, tmp_path):
+    from predict_pv_yield_amd import lightning as pl
+    from predict_pv_yield_amd.data.nb08_datamodule import Nb08DataModule
+    class Recording(LitAutoEncoder):
+        seen = []
+
+        def log_dict(self, d, **kw):
+            type(self).seen.extend((k, v.detach()) for k, v in d.items())
+            return super().log_dict(d, **kw)
+
+    Recording.seen = []
+    torch.manual_seed(1)
+    model = Recording()
+    dm = Nb08DataModule(batch_size=4, n_train_data=3, n_val_data=1, n_super_batches=1)
+    ckpt = pl.ModelCheckpoint(save_last=True, dirpath=str(tmp_path / "ck"))
+    trainer = pl.Trainer(gpus=1, max_epochs=1, callbacks=[ckpt], log_every_n_steps=1)
+    trainer.fit(model, datamodule=dm)
+    batch = next(iter(dm.train_dataloader()))
+    assert tuple(batch["HISTORICAL_SAT_IMAGES"].shape) == (4, 4, 128, 128) and tuple(batch["TARGET_SAT_IMAGE"].shape) == (4, 64, 64)
+    assert batch["FORECAST_HORIZON"].dtype == torch.float32
+    train = [float(v) for k, v in Recording.seen if k == "Loss/Train"]
+    assert len(train) == 3 and all(np.isfinite(train)), train
+    assert any(k == "Loss/Validation" for k, _ in Recording.seen)
+    state = torch.load(ckpt.last_model_path)["state_dict"]
+    assert list(state) == [f"{part}_conv.{i}.{w}" for part in ("encoder", "decoder") for i in (0, 2, 4)
+                           for w in ("weight", "bias")]
+    fresh = LitAutoEncoder()
+    fresh.load_state_dict(state)
+    for (k, p), q in zip(model.state_dict().items(), fresh.state_dict().values()):
+        assert torch.equal(p.cpu(), q), k
+
+
+def test_trainer_fit_with_hip_graph_matches_the_eager_fit(device):
+    """`run.py ... +trainer.hip_graph=true`: Trainer(hip_graph=True) replays the step after its eager steps; more batches
+    than those, same parameters and logged losses as the eager fit."""
+    from predict_pv_yield_amd import lightning as pl
+    from predict_pv_yield_amd.data.nb08_datamodule import Nb08DataModule
+    dm = Nb08DataModule(batch_size=4, n_train_data=pl.Trainer.GRAPH_EAGER_STEPS + 3, n_val_data=1, n_super_batches=1)
+    results = []
+    for graph in (False, True):
+        torch.manual_seed(2)
+        model = _model_cls()()
+        trainer = pl.Trainer(gpus=1, max_epochs=1, hip_graph=graph, log_every_n_steps=1)
+        trainer.fit(model, datamodule=dm)
+        results.append(({k: v.detach().clone() for k, v in model.state_dict().items()}, dict(trainer.callback_metrics)))
+    (sd_e, log_e), (sd_g, log_g) = results
+    for k in sd_e:
+        assert torch.equal(sd_e[k], sd_g[k]), k
+    assert np.isfinite(float(log_g["Loss/Train_epoch"])) and float(log_g["Loss/Train_epoch"]) == float(log_e["Loss/Train_epoch"])
+
+
+# ---- 7. refusals through the Python surface ----------------------------------------------------------------------------
+def test_refusals_raise_before_any_launch(device):
+    import ctypes
+    from predict_pv_yield_amd import _lib
+    from predict_pv_yield_amd.hip_ops import ptr
+    K = _ops()
+    z = lambda *s: torch.zeros(*s, device=device)      # noqa: E731
+    with pytest.raises(ValueError, match="128 columns"):                       # widths beyond the limit
+        K.conv2d_s2_frame_horizon_fwd_f32(z(1, 4, 8, 130), z(1), z(32, 2, 3, 3), z(32))
+    with pytest.raises(ValueError, match="128 columns"):
+        K.convt2d_s2_frames_fwd_f32(z(1, 128, 8, 64), z(128, 32, 3, 3), z(32))
+    with pytest.raises(ValueError, match="x \\[N, 128"):                       # wrong channel pairs
+        K.convt2d_s2_frames_fwd_f32(z(1, 32, 8, 8), z(32, 32, 3, 3), z(32))
+    with pytest.raises(ValueError, match="weight \\[32, 2, 3, 3\\]"):
+        K.conv2d_s2_frame_horizon_fwd_f32(z(1, 4, 8, 8), z(1), z(32, 6, 3, 3), z(32))
+    with pytest.raises(ValueError, match="horizon"):
+        K.conv2d_s2_frame_horizon_fwd_f32(z(2, 4, 8, 8), z(8), z(32, 2, 3, 3), z(32))
+    with pytest.raises(TypeError):
+        K.convt2d_s2_frames_fwd_f32(z(1, 128, 8, 8).double(), z(128, 32, 3, 3), z(32))
+    with pytest.raises(TypeError):
+        K.conv2d_s2_frame_horizon_fwd_f32(z(1, 4, 8, 8), z(1).double(), z(32, 2, 3, 3), z(32))
+    model = _model_cls()().to(device)
+    good = _to(_full_batch(80, 2, 31), device)
+    with pytest.raises(ValueError, match="TARGET_SAT_IMAGE"):
+        model.training_step({**good, "TARGET_SAT_IMAGE": z(2, 17, 17)}, 0)
+    for side in (14, 129):
+        with pytest.raises(ValueError, match="15 to 128"):
+            model({**good, "HISTORICAL_SAT_IMAGES": z(2, 4, side, side)})
+    for frames in (3, 5):
+        with pytest.raises(ValueError, match="HISTORICAL_SAT_IMAGES"):
+            model({**good, "HISTORICAL_SAT_IMAGES": z(2, frames, 31, 31)})
+    with pytest.raises(ValueError, match="FORECAST_HORIZON"):
+        model({**good, "FORECAST_HORIZON": z(3)})
+    # the C ABI itself: a shape the glue would have stopped, and a workspace one byte short of what the query asks for
+    lib = _lib.get_lib()
+    need = ctypes.c_size_t(0)
+    x, dy, dw, db, ws = z(2, 128, 7, 7), z(2, 32, 15, 15), z(128, 32, 3, 3), z(32), z(1 << 20)
+    assert lib.pv_convt2d_s2_frames_fwd_f32(ptr(x), ptr(dw), ptr(db), ptr(dy), 2, 128, 32, 7, 64, 1, None) == -2
+    assert lib.pv_convt2d_s2_frames_bwd_weight_workspace_bytes(2, 128, 32, 7, 7, ctypes.byref(need)) == 0 and 0 < need.value < 1 << 22
+    dw.fill_(7.0)
+    assert lib.pv_convt2d_s2_frames_bwd_weight_f32(ptr(x), ptr(dy), None, ptr(dw), ptr(db), 2, 128, 32, 7, 7, ptr(ws),
+                                                   need.value - 1, None) == -1
+    torch.cuda.synchronize()
+    assert (dw == 7.0).all(), "nothing was launched"
