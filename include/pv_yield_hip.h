@@ -731,6 +731,43 @@ int pv_convt2d_s2_frames_bwd_weight_f32(const float* x, const float* dy, const f
                                         int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws,
                                         size_t ws_bytes, void* stream);
 
+/* ---- notebooks/05_more_image_inputs.ipynb: four-input first Conv2d, horizon ConvTranspose2d at stride 1 ---- */
+/* (line numbers: the raw 05_...ipynb file; the LitAutoEncoder cell starts at 1348 with STRIDE = 1, GROUPS = 1, CHANNELS = 32;
+ * encoder is at 1356-1363, decoder at 1365-1371, forward at 1373-1388.)  NCHW f32, exact f32, planes up to 128 wide; gates
+ * (NULL = none) and weight-gradient slabs follow the conventions of the pv_conv2d_ae_* entry points above.  encoder.2 / .4 are
+ * pv_conv2d_ae_*, decoder.2 is pv_convt2d_ae_*, decoder.4 is pv_convt2d_head_*.  Unsupported shapes return PV_ESIZE (h, w < 3
+ * for the first layer, a plane wider than 128, a tensor of 2^31 elements or more), null pointers and non-positive sizes
+ * PV_EINVAL, before any launch. */
+/* replaces: x_cat = torch.cat((x[INPUT_IMAGES], x[T0_IMAGES], x[OPTICAL_FLOW].squeeze()), dim=1); nn.Conv2d(4, CHANNELS,
+ * kernel_size=3) (+ nn.ReLU() if relu), 05_...ipynb:1357-1358, 1374-1380.  flow_pred [n][h][w], t0 [n][h][w] and flow_field
+ * [n][2][h][w] (x then y displacement) are read in place as input channels 0, 1 and 2 - 3: no [n][4][h][w] tensor exists.  w
+ * [32][4][3][3]; y [n][32][h - 2][w - 2]; bias may be NULL.  The inputs are data: there is no input gradient. */
+int pv_conv2d_ae_inputs_fwd_f32(const float* flow_pred, const float* t0, const float* flow_field, const float* w,
+                                const float* bias, float* y, int32_t n, int32_t h, int32_t w_img, int32_t relu, void* stream);
+/* bytes of the weight-gradient workspace: one partial [32][4 * 9 + 1] per slab of tiles */
+int pv_conv2d_ae_inputs_bwd_weight_workspace_bytes(int32_t n, int32_t h, int32_t w_img, size_t* bytes);
+/* replaces: the weight and bias gradients of encoder.0 (autograd of 05_...ipynb:1357), re-reading the three tensors as the
+ * forward does.  dy [n][32][h - 2][w - 2], zeroed where dy_gate <= 0; dw [32][4][3][3] and dbias [32] are overwritten; slab
+ * partials summed in slab order (no atomics, identical bits run to run). */
+int pv_conv2d_ae_inputs_bwd_weight_f32(const float* flow_pred, const float* t0, const float* flow_field, const float* dy,
+                                       const float* dy_gate, float* dw, float* dbias, int32_t n, int32_t h, int32_t w_img,
+                                       void* ws, size_t ws_bytes, void* stream);
+/* replaces: x[FORECAST_HORIZON].view(-1, 1, 1, 1).expand(...); torch.cat((embedding, forecast_horizon), dim=1);
+ * nn.ConvTranspose2d(CHANNELS + 1, CHANNELS, kernel_size=3, stride=1) (+ nn.ReLU() if relu), 05_...ipynb:1366-1367, 1382-1387.
+ * x [n][32][h][w]; horizon [n] (device f32): input channel 32 is horizon[i] inside the image, synthesised in the kernel; w
+ * [33][32][3][3]; y [n][32][h + 2][w + 2]; w + 2 <= 128; bias may be NULL.  The input gradient of the 32 real channels is
+ * pv_convt2d_ae_bwd_data_f32 on the first 32 rows of w. */
+int pv_convt2d_ae_horizon_fwd_f32(const float* x, const float* horizon, const float* w, const float* bias, float* y, int32_t n,
+                                  int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* bytes of the workspace of pv_convt2d_ae_horizon_bwd_weight_f32: one partial [32][33 * 9 + 1] per slab of tiles */
+int pv_convt2d_ae_horizon_bwd_weight_workspace_bytes(int32_t n, int32_t h_in, int32_t w_in, size_t* bytes);
+/* replaces: the weight and bias gradients of decoder.0 (autograd of 05_...ipynb:1366), re-synthesising the horizon channel as
+ * the forward does: dw [33][32][3][3], row 32 = sum_n horizon[n] sum_pos dy[n][co][pos + tap]; dbias [32] = the sum of dy
+ * (both with dy zeroed where dy_gate <= 0); deterministic. */
+int pv_convt2d_ae_horizon_bwd_weight_f32(const float* x, const float* horizon, const float* dy, const float* dy_gate, float* dw,
+                                         float* dbias, int32_t n, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
+                                         void* stream);
+
 /* MaxPool3d over x[B*C planes][Ti,Hi,Wi]; argmax (may be NULL) = flat winner offset inside the plane stack, first
  * maximum wins, NaN propagates (torch CPU semantics).  bwd overwrites dx by gathering dy through argmax. */
 int pv_maxpool3d_fwd_f32(const float* x, float* y, int32_t* argmax, const pv_conv3d_geom* d, void* stream);

@@ -124,7 +124,11 @@ _CONVT_HORIZON_BWD_WEIGHT = [c_vp] * 6 + [c_i32] * 3 + _WORKSPACE + [c_vp]   # x
 # _conv2d_family
 _FRAME_HORIZON_FWD = [c_vp] * 5 + [c_i32] * 4 + [c_i32, c_vp]        # history, horizon, weight, bias, y, dims, relu
 _FRAME_HORIZON_BWD_WEIGHT = [c_vp] * 6 + [c_i32] * 4 + _WORKSPACE + [c_vp]   # history, horizon, dy, dy_gate, dw, dbias, dims
-_MSE_NORM_TAIL = [c_vp, c_vp] + _WORKSPACE + [c_vp]                  # loss, grad, workspace, stream
+# ... notebook 05's four-input first layer takes (n, h, w) after its pointers; its stride-1 horizon ConvTranspose2d has the
+# prototypes of notebook 08's stride-2 one
+_INPUTS_FWD = [c_vp] * 6 + [c_i32] * 3 + [c_i32, c_vp]               # flow_pred, t0, flow_field, weight, bias, y, (n, h, w), relu
+_INPUTS_BWD_WEIGHT = [c_vp] * 7 + [c_i32] * 3 + _WORKSPACE + [c_vp]  # flow_pred, t0, flow_field, dy, dy_gate, dw, dbias, (n, h, w)
+_MSE_NORM_TAIL =[c_vp, c_vp] + _WORKSPACE + [c_vp]                  # loss, grad, workspace, stream
 
 
 def _conv2d_family(stem, ws_query):
@@ -261,6 +265,12 @@ SIGNATURES = {
     "pv_conv2d_s2_frame_horizon_bwd_weight_workspace_bytes": [c_i32] * 4 + [ctypes.POINTER(c_sz)],
     "pv_conv2d_s2_frame_horizon_bwd_weight_f32": _FRAME_HORIZON_BWD_WEIGHT,
     **_conv2d_family("convt2d_s2_frames", _WS_QUERY5),
+    "pv_conv2d_ae_inputs_fwd_f32": _INPUTS_FWD,
+    "pv_conv2d_ae_inputs_bwd_weight_workspace_bytes": [c_i32] * 3 + [ctypes.POINTER(c_sz)],
+    "pv_conv2d_ae_inputs_bwd_weight_f32": _INPUTS_BWD_WEIGHT,
+    "pv_convt2d_ae_horizon_fwd_f32": _CONVT_HORIZON_FWD,
+    "pv_convt2d_ae_horizon_bwd_weight_workspace_bytes": [c_i32] * 3 + [ctypes.POINTER(c_sz)],
+    "pv_convt2d_ae_horizon_bwd_weight_f32": _CONVT_HORIZON_BWD_WEIGHT,
     "pv_maxpool3d_fwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_maxpool3d_bwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_mse_loss_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp],

@@ -5,7 +5,9 @@ stride-2 Conv2d / ConvTranspose2d kernels of csrc/conv2d_s2_f32.hip (notebooks/1
 the padded 64 / 128-channel kernels, stripe first layer and stride-2 head of csrc/conv2d_wide_f32.hip (notebooks/10_just_conv.ipynb)
 and the stride-2 64 / 128-channel Conv2d / ConvTranspose2d kernels, stride-2 stripe first layer, one-channel ConvTranspose2d
 head and prediction-window MSE of csrc/conv2d_wide_s2_f32.hip (notebooks/09_horizon_represented_as_a_stripe.ipynb) and the
-per-frame first layer and 128 -> 32 ConvTranspose2d of csrc/conv2d_frames_f32.hip (notebooks/07_multiple_historical_images.ipynb).
+per-frame first layer and 128 -> 32 ConvTranspose2d of csrc/conv2d_frames_f32.hip (notebooks/07_multiple_historical_images.ipynb)
+and the four-input first layer and stride-1 horizon ConvTranspose2d of csrc/conv2d_inputs_f32.hip
+(notebooks/05_more_image_inputs.ipynb).
 
 Reference operators replaced:
   experiments/002_cnn_processes_single_sat_image_then_rnn.py
@@ -38,6 +40,11 @@ Reference operators replaced:
     stride 2, a ReLU after each; torch.cat(encoder_outs, dim=1)                                                :1364-1371, 1383-1394
     self.decoder_conv(encoder_outs): ConvTranspose2d 128 -> 32 -> 32 stride 2 with ReLU, ConvTranspose2d 32 -> 1 :1373-1379, 1396
     F.mse_loss(y_hat[:, :, :-1, :-1], y.unsqueeze(1))                                                          :1399-1402
+  notebooks/05_more_image_inputs.ipynb (raw lines of the .ipynb file)
+    self.encoder(cat(input_images, T0_IMAGES, optical_flow.squeeze())): Conv2d 4 -> 32 -> 32 -> 32, a ReLU after each :1356-1363, 1374-1380
+    self.decoder(cat(embedding, forecast horizon plane)): ConvTranspose2d 33 -> 32 -> 32 with ReLU, ConvTranspose2d 32 -> 1
+                                                                                                               :1365-1371, 1382-1387
+    F.mse_loss(y_hat, y)                                                                                       :1394
 
 Gating.  As in functional.Conv3dGeneralF32, the ReLU gating of an activation gradient is moved into the kernel that
 produces it.  x_is_relu_output -> this layer's dx leaves already zeroed where x <= 0 (the lower layer's pre-activation
@@ -83,6 +90,8 @@ COUNTS_S2_OPS = (K.conv2d_s2_counts_fwd_f32, K.conv2d_s2_counts_bwd_weight_f32)
 # the per-frame history plane plus horizon plane of notebook 07 (and its 128 -> 32 ConvTranspose2d, a plain family)
 FRAME_HORIZON_S2_OPS = (K.conv2d_s2_frame_horizon_fwd_f32, K.conv2d_s2_frame_horizon_bwd_weight_f32)
 CONVT2D_S2_FRAMES_OPS = (K.convt2d_s2_frames_fwd_f32, K.convt2d_s2_frames_bwd_data_f32, K.convt2d_s2_frames_bwd_weight_f32)
+# the flow prediction, t0 image and flow field of notebook 05, read in place as four channels
+INPUTS_AE_OPS = (K.conv2d_ae_inputs_fwd_f32, K.conv2d_ae_inputs_bwd_weight_f32)
 # ... and of the conv with fused MaxPool2d(3): the forward returns (pooled, codes), the gradients take the codes
 CONV2D144_POOL_OPS = (K.conv2d144_pool_fwd_f32, K.conv2d144_pool_bwd_data_f32, K.conv2d144_pool_bwd_weight_f32)
 CONV2D_AE_POOL_OPS = (K.conv2d_ae_pool_fwd_f32, K.conv2d_ae_pool_bwd_data_f32, K.conv2d_ae_pool_bwd_weight_f32)
@@ -97,6 +106,8 @@ class SynthConvReLU(torch.autograd.Function):
       COUNTS_AE_OPS, COUNTS_S2_OPS          history [N, 4, H, W], flow prediction [N, H, W] (counts, int16 or f32), horizon [N] f32
       STRIPE_WIDE_OPS, STRIPE_WIDE_S2_OPS   history [N, n_hist, H, W] f32, stripe_start [N] int32 (the stripe plane is 1 on columns
                                             stripe_start[i] <= c < stripe_start[i] + stripe_width); stripe_width
+      INPUTS_AE_OPS                         flow prediction [N, H, W], t0 image [N, H, W], flow field [N, 2, H, W], all f32: the four
+                                            channels of notebook 05's x_cat
       FRAME_HORIZON_S2_OPS                  history [N, F, H, W] f32, horizon [N] f32: every frame with the horizon as a second,
                                             constant channel, the frames folded into the batch -> [N F, 32, ..]
       conv3d_wide_functional.HORIZON_WIDE_OPS   history [N, D, H, W] f32, horizon [N] f32 as a second, constant channel"""
@@ -461,3 +472,53 @@ def nb07_multi_hist_f32(history, horizon, encoder_conv, decoder_conv):
                              lambda y: y.view(n, frames * y.shape[1], *y.shape[2:]),
                              (CONVT2D_S2_FRAMES_OPS, dec[0]), (CONVT2D_S2_OPS, dec[2]), (CONVT2D_HEAD_OPS, dec[4])],
                       last_relu=False)
+
+
+# ---- notebooks/05_more_image_inputs.ipynb ----------------------------------------------------------------------------------
+class HorizonConvTransposeS1ReLU(torch.autograd.Function):
+    """First decoder layer of notebook 05: nn.ConvTranspose2d(33, 32, 3) (+ ReLU) on x [N, 32, H, W] f32 plus the forecast
+    horizon [N] as a 33rd input channel, constant over the image, built inside the kernels (forward and weight gradient),
+    never stored.  The horizon has no gradient; the 32 real channels' data gradient is the plain ConvTranspose2d's on the
+    first 32 rows of the weight (contiguous, so a view).  The stride-1 twin of
+    conv3d_wide_functional.HorizonConvTransposeReLU."""
+
+    @staticmethod
+    def forward(ctx, x, horizon, weight, bias, x_is_relu_output, dy_pregated):
+        x, horizon = x.contiguous(), horizon.contiguous()
+        y = K.convt2d_ae_horizon_fwd_f32(x, horizon, weight.contiguous(), bias.contiguous(), True)
+        ctx.save_for_backward(x, horizon, weight, None if dy_pregated else y)
+        ctx.x_is_relu_output = x_is_relu_output
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, horizon, weight, y = ctx.saved_tensors
+        dy, weight = dy.contiguous(), weight.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.convt2d_ae_bwd_data_f32(dy, y, weight[:K.CONVT_HORIZON_C], x if ctx.x_is_relu_output else None,
+                                           tuple(x.shape))
+        dw, db = K.convt2d_ae_horizon_bwd_weight_f32(x, horizon, dy, y, tuple(weight.shape))
+        return dx, None, dw, db, None, None
+
+
+def inputs_conv_relu(flow_pred, t0, flow_field, weight, bias):
+    """relu(encoder.0(cat(input_images, T0_IMAGES, optical_flow))) of 05_more_image_inputs.ipynb:1357-1358, 1374-1380;
+    gradients to weight and bias only."""
+    return SynthConvReLU.apply(INPUTS_AE_OPS, (flow_pred, t0, flow_field), weight, bias, {}, False)
+
+
+def horizon_conv_transpose_s1_relu(x, horizon, weight, bias, x_is_relu_output=False):
+    """relu(decoder.0(cat(x, horizon plane))) of 05_more_image_inputs.ipynb:1366-1367, 1382-1387; no gradient to the horizon."""
+    return HorizonConvTransposeS1ReLU.apply(x, horizon, weight, bias, bool(x_is_relu_output), False)
+
+
+def nb05_more_inputs_f32(flow_pred, t0, flow_field, horizon, encoder, decoder):
+    """self.decoder(cat(self.encoder(cat(input_images, T0_IMAGES, optical_flow)), horizon plane)) of
+    05_more_image_inputs.ipynb:1373-1388; encoder / decoder = the notebook's two nn.Sequential (modules 0, 2, 4 nn.Conv2d /
+    nn.ConvTranspose2d).  flow_pred and t0 [N, H, W], flow_field [N, 2, H, W], horizon [N], all f32 -> [N, 1, H, W]: the sides go
+    down by 2 three times and up by 2 three times."""
+    return conv_chain(None, [(INPUTS_AE_OPS, encoder[0], (flow_pred, t0, flow_field)),
+                             (CONV2D_AE_OPS, encoder[2]), (CONV2D_AE_OPS, encoder[4]),
+                             (HorizonConvTransposeS1ReLU, decoder[0], (horizon,)),
+                             (CONVT2D_AE_OPS, decoder[2]), (CONVT2D_HEAD_OPS, decoder[4])], last_relu=False)

@@ -110,7 +110,8 @@ __device__ __forceinline__ float pool3_expand(const float* dyp, const uint8_t* c
 
 // What a pass reads, by source kind.  Each file's first layer synthesises its input while staging (its own load_in /
 // stage_in arm); the other two kinds are the same everywhere.
-enum Src { SRC_PLAIN, SRC_POOLED, SRC_SAT, SRC_COUNTS, SRC_DEPTH, SRC_HORIZON, SRC_FRAME_HORIZON, SRC_CH_GROUP, SRC_FRAME_SHARED };
+enum Src { SRC_PLAIN, SRC_POOLED, SRC_SAT, SRC_COUNTS, SRC_DEPTH, SRC_HORIZON, SRC_FRAME_HORIZON, SRC_CH_GROUP, SRC_FRAME_SHARED,
+           SRC_INPUTS4 };
 
 struct In {
   // SRC_PLAIN: x[n][c_in][h][w], zeroed where gate <= 0 (gate may be null)
@@ -125,10 +126,12 @@ struct In {
   //                    horizon[i / n_frames] as a constant second channel (c_in = 2)
   // SRC_CH_GROUP: the c_in channels [t_per_ex, t_per_ex + c_in) of x[n][t_total][h][w]; zeroed where gate <= 0 (may be null)
   // SRC_FRAME_SHARED: x[b][c_in][h][w] read by the n_frames images i = n_frames b + f of an example alike; gate as SRC_PLAIN
+  // SRC_INPUTS4: four channels from three tensors read in place (c_in = 4): channel 0 = x, the flow prediction [n][h][w];
+  //              channel 1 = xc, the t0 image [n][h][w]; channels 2, 3 = flow, the f32 flow field [n][2][h][w] (x then y)
   const float* x;
   const float* gate;
   const uint8_t* codes;    // SRC_POOLED: [n][c_in][ph][pw]
-  const float* xc;         // SRC_SAT: [b][w] geo x (varies along the last axis)
+  const float* xc;         // SRC_SAT: [b][w] geo x (varies along the last axis); SRC_INPUTS4: the t0 image [n][h][w]
   const float* yc;         // SRC_SAT: [b][h] geo y (varies along rows)
   const void* flow;
   const float* horizon;

@@ -7,7 +7,9 @@
 // split by column parity) instantiate them; each keeps its tile planner, its argument checks and its first layer's source
 // kind.  conv3d_s2_f32.hip (notebook 08) instantiates the stride-2 weight gradient over depth slices of NCDHW tensors
 // (SRC_DEPTH) and keeps forward-like kernels of its own, which run one K pass per depth tap.  conv2d_frames_f32.hip (notebook
-// 07) instantiates both at stride 2 over its per-frame sources (SRC_FRAME_HORIZON, SRC_FRAME_SHARED, SRC_CH_GROUP).  A
+// 07) instantiates both at stride 2 over its per-frame sources (SRC_FRAME_HORIZON, SRC_FRAME_SHARED, SRC_CH_GROUP).
+// conv2d_inputs_f32.hip (notebook 05) instantiates both at stride 1 with conv2d_ae_f32.hip's planners (conv2d_ae_plan_f32.h)
+// over its three-tensor first layer (SRC_INPUTS4) and the horizon channel (SRC_HORIZON, conv2d_horizon_f32.h).  A
 // forward-like output element's sum depends only on the (tap, channel group) order, not on the tile it
 // falls in; the weight gradient's bits depend on the row-major position order inside an item, the items per slab and the
 // slab order (fixed slabs, each block writing its own, added in slab order: no atomics, identical bits run to run).

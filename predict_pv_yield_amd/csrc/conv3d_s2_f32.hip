@@ -21,6 +21,7 @@
 // The horizon ConvTranspose2d synthesises its 33rd channel while the source tile is staged (SRC_HORIZON: horizon[n] inside
 // the source extent, 0 in the halo); in its weight gradient the same source kind is the operand at the output positions, so
 // row 32 is sum_n horizon[n] sum_pos dy[n][co][2 pos + tap].
+#include "conv2d_horizon_f32.h"
 #include "conv2d_s2_plan_f32.h"
 
 namespace pv {
@@ -33,13 +34,6 @@ __device__ __forceinline__ float load_in<SRC_DEPTH>(const In& s, int img, int ch
   const size_t off = ((((size_t)b * s.c_in + ch) * s.t_total + z) * s.h + r) * s.w + col;
   const float v = s.x[off];
   return (s.gate && !(s.gate[off] > 0.0f)) ? 0.0f : v;
-}
-
-// the real channels, then the horizon plane
-template <>
-__device__ __forceinline__ float load_in<SRC_HORIZON>(const In& s, int n, int ch, int r, int col) {
-  if (ch == s.c_in - 1) return s.horizon[n];
-  return s.x[(((size_t)n * (s.c_in - 1) + ch) * s.h + r) * s.w + col];
 }
 
 constexpr int kMaxWidth = 128;
@@ -160,12 +154,6 @@ __global__ __launch_bounds__(kBlock) void conv3d_s2_scatter(Fwd a, int dst_d) {
 In depth_in(const float* x, const float* gate, int c, int d, int per, int tap, int h, int w) {
   In s = {};
   s.x = x, s.gate = gate, s.c_in = c, s.t_total = d, s.n_frames = per, s.t_per_ex = tap, s.h = h, s.w = w;
-  return s;
-}
-
-In horizon_in(const float* x, const float* horizon, int c_real, int h, int w) {
-  In s = {};
-  s.x = x, s.horizon = horizon, s.c_in = c_real + 1, s.h = h, s.w = w;
   return s;
 }
 

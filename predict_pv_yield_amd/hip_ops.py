@@ -2115,7 +2115,9 @@ def conv3d_s2_bwd_weight_f32(x, dy, dy_gate, weight_shape):
     return _conv_bwd_weight(_CONV3D_S2, x, dy, dy_gate, weight_shape)
 
 
-def _check_convt_horizon(who, x, horizon, weight_shape):
+def _check_convt_horizon(who, x, horizon, weight_shape, out_hw):
+    """The shape rule of pv_convt2d_{s2,ae}_horizon_*; out_hw(h, w) = the output's sides.  Returns (n, h, w) and the output's
+    shape."""
     c = CONVT_HORIZON_C
     if x.dim() != 4 or x.shape[1] != c or tuple(weight_shape) != (c + 1, c, 3, 3):
         raise ValueError(f"{who}: x [N, {c}, H, W] and weight [{c + 1}, {c}, 3, 3] expected, got {tuple(x.shape)} / "
@@ -2123,40 +2125,116 @@ def _check_convt_horizon(who, x, horizon, weight_shape):
     n, _, h, w = (int(v) for v in x.shape)
     if tuple(horizon.shape) != (n,):
         raise ValueError(f"{who}: horizon [{n}] expected, got {tuple(horizon.shape)}")
-    if min(h, w) < 1 or 2 * w + 1 > WIDE_MAX_W:
+    if min(h, w) < 1 or out_hw(h, w)[1] > WIDE_MAX_W:
         raise ValueError(f"{who}: a non-empty plane whose output is at most {WIDE_MAX_W} columns wide expected, got {h} x {w}")
-    return n, h, w
+    return (n, h, w), (n, c, *out_hw(h, w))
+
+
+def _convt_horizon_fwd(stem, out_hw, x, horizon, weight, bias, relu):
+    who = f"{stem}_horizon_fwd_f32"
+    dims, y_shape = _check_convt_horizon(who, x, horizon, weight.shape, out_hw)
+    _check_bias(who, bias, CONVT_HORIZON_C)
+    require_cuda(x, horizon, weight, bias)
+    _f32_contig(x, horizon, weight, bias)
+    y = torch.empty(y_shape, dtype=torch.float32, device=x.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(horizon), ptr(weight), ptr(bias), ptr(y), *dims, int(relu),
+                                          current_stream_ptr()), "pv_" + who)
+    return y
+
+
+def _convt_horizon_bwd_weight(stem, out_hw, x, horizon, dy, dy_gate, weight_shape):
+    who = f"{stem}_horizon_bwd_weight_f32"
+    dims, y_shape = _check_convt_horizon(who, x, horizon, weight_shape, out_hw)
+    _check_dy(who, dy, dy_gate, y_shape)
+    require_cuda(x, horizon, dy, dy_gate)
+    _f32_contig(x, horizon, dy, dy_gate)
+    ws, nbytes = _wgrad_ws(f"{stem}_horizon", x.device, *dims)
+    dw, db = _grads_out(weight_shape, CONVT_HORIZON_C, x.device)
+    check(getattr(get_lib(), "pv_" + who)(ptr(x), ptr(horizon), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), *dims, ptr(ws), nbytes,
+                                          current_stream_ptr()), "pv_" + who)
+    return dw, db
+
+
+def _s2t_hw(h, w):
+    return 2 * h + 1, 2 * w + 1
 
 
 def convt2d_s2_horizon_fwd_f32(x, horizon, weight, bias, relu=True):
     """conv_transpose2d(cat(x, horizon plane), weight, stride 2) + bias (+ ReLU): x [N, 32, H, W] f32, input channel 32 of
     example i is horizon[i] everywhere -> [N, 32, 2 H + 1, 2 W + 1]; weight [33, 32, 3, 3]."""
-    who = "convt2d_s2_horizon_fwd_f32"
-    n, h, w = _check_convt_horizon(who, x, horizon, weight.shape)
-    _check_bias(who, bias, CONVT_HORIZON_C)
-    require_cuda(x, horizon, weight, bias)
-    _f32_contig(x, horizon, weight, bias)
-    y = torch.empty((n, CONVT_HORIZON_C, 2 * h + 1, 2 * w + 1), dtype=torch.float32, device=x.device)
-    check(get_lib().pv_convt2d_s2_horizon_fwd_f32(ptr(x), ptr(horizon), ptr(weight), ptr(bias), ptr(y), n, h, w, int(relu),
-                                                  current_stream_ptr()), "pv_" + who)
-    return y
+    return _convt_horizon_fwd("convt2d_s2", _s2t_hw, x, horizon, weight, bias, relu)
 
 
 def convt2d_s2_horizon_bwd_weight_f32(x, horizon, dy, dy_gate, weight_shape):
     """(dw [33, 32, 3, 3], dbias [32]) of convt2d_s2_horizon_fwd_f32; dy zeroed where dy_gate <= 0 (may be None);
     deterministic.  The data gradient of the 32 real channels is convt2d_s2_bwd_data_f32 on weight[:32]."""
-    who = "convt2d_s2_horizon_bwd_weight_f32"
-    n, h, w = _check_convt_horizon(who, x, horizon, weight_shape)
-    y_shape = (n, CONVT_HORIZON_C, 2 * h + 1, 2 * w + 1)
-    if tuple(dy.shape) != y_shape or (dy_gate is not None and tuple(dy_gate.shape) != y_shape):
-        raise ValueError(f"{who}: dy / dy_gate {y_shape} expected, got {tuple(dy.shape)}")
-    require_cuda(x, horizon, dy, dy_gate)
-    _f32_contig(x, horizon, dy, dy_gate)
-    ws, nbytes = _wgrad_ws("convt2d_s2_horizon", x.device, n, h, w)
-    dw, db = _grads_out(weight_shape, CONVT_HORIZON_C, x.device)
-    check(get_lib().pv_convt2d_s2_horizon_bwd_weight_f32(ptr(x), ptr(horizon), ptr(dy), ptr(dy_gate), ptr(dw), ptr(db), n, h, w,
-                                                         ptr(ws), nbytes, current_stream_ptr()), "pv_" + who)
+    return _convt_horizon_bwd_weight("convt2d_s2", _s2t_hw, x, horizon, dy, dy_gate, weight_shape)
+
+
+# ---- notebooks/05_more_image_inputs.ipynb: Conv2d 4 -> 32 whose four input channels are three tensors read in place, and
+# ConvTranspose2d 33 -> 32 at stride 1 whose last input channel is the forecast horizon (csrc/conv2d_inputs_f32.hip); planes
+# up to 128 wide.  The layers between them are conv2d_ae_*, convt2d_ae_* and convt2d_head_*. ----
+INPUTS_C_OUT = 32                                 # CHANNELS
+
+
+def _full_hw(h, w):
+    return h + 2, w + 2
+
+
+def _check_inputs4(who, flow_pred, t0, flow_field, weight_shape):
+    if flow_pred.dim() != 3 or tuple(t0.shape) != tuple(flow_pred.shape):
+        raise ValueError(f"{who}: flow prediction and t0 image [N, H, W] expected, got {tuple(flow_pred.shape)} / "
+                         f"{tuple(t0.shape)}")
+    n, h, w = (int(v) for v in flow_pred.shape)
+    if tuple(flow_field.shape) != (n, 2, h, w) or tuple(weight_shape) != (INPUTS_C_OUT, 4, 3, 3):
+        raise ValueError(f"{who}: flow field [{n}, 2, {h}, {w}] and weight [{INPUTS_C_OUT}, 4, 3, 3] expected, got "
+                         f"{tuple(flow_field.shape)} / {tuple(weight_shape)}")
+    require_cuda(flow_pred, t0, flow_field)
+    _f32_contig(flow_pred, t0, flow_field)
+    return n, h, w
+
+
+def conv2d_ae_inputs_fwd_f32(flow_pred, t0, flow_field, weight, bias, relu=True):
+    """conv2d(cat(flow_pred, t0, flow_field), weight) + bias (+ ReLU): flow prediction and t0 image [N, H, W], flow field
+    [N, 2, H, W] (x then y), all f32 and read in place as input channels 0, 1 and 2 - 3 -> [N, 32, H - 2, W - 2]; weight
+    [32, 4, 3, 3]; H, W >= 3, W <= 128."""
+    who = "conv2d_ae_inputs_fwd_f32"
+    n, h, w = _check_inputs4(who, flow_pred, t0, flow_field, weight.shape)
+    _check_bias(who, bias, INPUTS_C_OUT)
+    require_cuda(weight, bias)
+    _f32_contig(weight, bias)
+    # clamped: an undersized plane reaches the entry point, which names the smallest it takes
+    y = torch.empty((n, INPUTS_C_OUT, max(h - 2, 0), max(w - 2, 0)), dtype=torch.float32, device=flow_pred.device)
+    check(get_lib().pv_conv2d_ae_inputs_fwd_f32(ptr(flow_pred), ptr(t0), ptr(flow_field), ptr(weight), ptr(bias), ptr(y), n, h,
+                                                w, int(relu), current_stream_ptr()), "pv_" + who)
+    return y
+
+
+def conv2d_ae_inputs_bwd_weight_f32(flow_pred, t0, flow_field, dy, weight_shape, dy_gate=None):
+    """(dw [32, 4, 3, 3], dbias [32]) of conv2d_ae_inputs_fwd_f32; dy zeroed where dy_gate <= 0 (may be None); deterministic.
+    The inputs are data, so there is no data gradient."""
+    who = "conv2d_ae_inputs_bwd_weight_f32"
+    n, h, w = _check_inputs4(who, flow_pred, t0, flow_field, weight_shape)
+    _check_dy(who, dy, dy_gate, (n, INPUTS_C_OUT, h - 2, w - 2))
+    require_cuda(dy, dy_gate)
+    _f32_contig(dy, dy_gate)
+    ws, nbytes = _wgrad_ws("conv2d_ae_inputs", flow_pred.device, n, h, w)
+    dw, db = _grads_out(weight_shape, INPUTS_C_OUT, flow_pred.device)
+    check(get_lib().pv_conv2d_ae_inputs_bwd_weight_f32(ptr(flow_pred), ptr(t0), ptr(flow_field), ptr(dy), ptr(dy_gate), ptr(dw),
+                                                       ptr(db), n, h, w, ptr(ws), nbytes, current_stream_ptr()), "pv_" + who)
     return dw, db
+
+
+def convt2d_ae_horizon_fwd_f32(x, horizon, weight, bias, relu=True):
+    """conv_transpose2d(cat(x, horizon plane), weight) + bias (+ ReLU): x [N, 32, H, W] f32, input channel 32 of example i is
+    horizon[i] everywhere -> [N, 32, H + 2, W + 2]; weight [33, 32, 3, 3]; W + 2 <= 128."""
+    return _convt_horizon_fwd("convt2d_ae", _full_hw, x, horizon, weight, bias, relu)
+
+
+def convt2d_ae_horizon_bwd_weight_f32(x, horizon, dy, dy_gate, weight_shape):
+    """(dw [33, 32, 3, 3], dbias [32]) of convt2d_ae_horizon_fwd_f32; dy zeroed where dy_gate <= 0 (may be None);
+    deterministic.  The data gradient of the 32 real channels is convt2d_ae_bwd_data_f32 on weight[:32]."""
+    return _convt_horizon_bwd_weight("convt2d_ae", _full_hw, x, horizon, dy, dy_gate, weight_shape)
 
 
 # ---- notebooks/07_multiple_historical_images.ipynb: one Conv2d 2 -> 32 -> 32 -> 32 stride-2 encoder applied to every history

@@ -1,4 +1,4 @@
-"""What the notebook frame predictors' LitAutoEncoders (notebooks 08, 09, 10, 12, 15, 16) share: the checks of a batch's
+"""What the notebook frame predictors' LitAutoEncoders (notebooks 05, 07, 08, 09, 10, 12, 15, 16) share: the checks of a batch's
 tensors, the train / validation step with its logging, and the optimiser.  A model file keeps its layers, its side rule
 (output_side, target_side), the call into its chain builder and its loss line.
 
@@ -32,6 +32,8 @@ class NotebookAutoEncoder(pl.LightningModule):
     layers, and defines forward(x) and loss(y_hat, y)."""
     nb = None
     lr = 0.001
+    # the batch keys of the image whose sides set the target's, and of the target (notebook 05 spells them differently)
+    image_key, target_key = HISTORICAL_SAT_IMAGES, TARGET_SAT_IMAGE
 
     def history_and_horizon(self, x, horizon_dtype=None):
         """(history [B, 4, H, W] as float32, horizon [B] on its device, cast to horizon_dtype if given) of a batch whose horizon
@@ -62,13 +64,33 @@ class NotebookAutoEncoder(pl.LightningModule):
         history, flow_pred = (self.counts(t) for t in (history, flow_pred))
         return history, flow_pred, horizon.to(device=history.device, dtype=torch.float32).reshape(-1)
 
+    def flow_inputs_and_horizon(self, x, flow_pred_key, t0_key, flow_field_key, horizon_key):
+        """(flow prediction [B, H, W], t0 image [B, H, W], flow field [B, 2, H, W], horizon [B]), all float32, of a batch whose
+        flow prediction and t0 image are [B, 1, H, W] and whose flow field is [B, 1, 2, H, W] or [B, 2, H, W] (planar, x then
+        y).  The singleton axes are dropped as views and the batch axis survives B = 1."""
+        flow_pred, t0, field, horizon = x[flow_pred_key], x[t0_key], x[flow_field_key], x[horizon_key]
+        if flow_pred.dim() != 4 or flow_pred.shape[1] != 1 or tuple(t0.shape) != tuple(flow_pred.shape):
+            raise ValueError(f"{self.nb} LitAutoEncoder takes {flow_pred_key} and {t0_key} [B, 1, H, W], got "
+                             f"{tuple(flow_pred.shape)} / {tuple(t0.shape)}")
+        b, _, h, w = flow_pred.shape
+        if tuple(field.shape) not in ((b, 1, 2, h, w), (b, 2, h, w)):
+            raise ValueError(f"{self.nb} LitAutoEncoder takes {flow_field_key} [B, 1, 2, H, W] or [B, 2, H, W] = "
+                             f"[{b}, (1,) 2, {h}, {w}], got {tuple(field.shape)}")
+        if horizon.numel() != b:
+            raise ValueError(f"{self.nb} LitAutoEncoder takes {horizon_key} [B], got {tuple(horizon.shape)} for {b} examples")
+        _require_device(flow_pred, t0, field)
+        for side in (h, w):
+            self.output_side(int(side))
+        return (flow_pred.float().reshape(b, h, w), t0.float().reshape(b, h, w), field.float().reshape(b, 2, h, w),
+                horizon.to(device=flow_pred.device, dtype=torch.float32).reshape(-1))
+
     @staticmethod
     def counts(t):
         return t if t.dtype in (torch.int16, torch.float32) else t.float()
 
     def _training_or_validation_step(self, batch, is_train_step):
-        y = batch[TARGET_SAT_IMAGE]
-        self.check_target_side(tuple(batch[HISTORICAL_SAT_IMAGES].shape[-2:]), y.shape)
+        y = batch[self.target_key]
+        self.check_target_side(tuple(batch[self.image_key].shape[-2:]), y.shape)
         loss = self.loss(self(batch), y)
         tag = "Loss/Train" if is_train_step else "Loss/Validation"
         self.log_dict({tag: loss}, on_step=is_train_step, on_epoch=True)
