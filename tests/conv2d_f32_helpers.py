@@ -18,6 +18,11 @@ def _golden_module(experiment):
     return mod
 
 
+def params64(state, requires_grad=True):
+    """A state_dict (or name -> array) as float64 CPU leaves: the parameters of a tests/nbXX_reference.py forward64."""
+    return {k: torch.as_tensor(v).detach().cpu().double().clone().requires_grad_(requires_grad) for k, v in state.items()}
+
+
 def _rel(a, b):
     a, b = torch.as_tensor(a).double().cpu(), torch.as_tensor(b).double().cpu()
     return ((a - b).norm() / (b.norm() + 1e-30)).item()

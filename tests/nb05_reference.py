@@ -5,15 +5,11 @@ tests/golden/make_nb05_golden.py (draw_batch, draw_parameters)."""
 import torch
 import torch.nn.functional as F
 
-from conv2d_f32_helpers import _golden_module
+from conv2d_f32_helpers import _golden_module, params64  # noqa: F401
 
 ENCODER = (0, 2, 4)            # modules of encoder: Conv2d 3x3, a ReLU after each
 DECODER = (0, 2, 4)            # modules of decoder: ConvTranspose2d 3x3; no ReLU after the last
 G = _golden_module("nb05")
-
-
-def params64(state, requires_grad=True):
-    return {k: torch.as_tensor(v).detach().cpu().double().clone().requires_grad_(requires_grad) for k, v in state.items()}
 
 
 def encoder_input64(batch):

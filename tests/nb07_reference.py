@@ -6,16 +6,12 @@ concatenated, as the notebook does: the fold into the batch is the kernels' busi
 import torch
 import torch.nn.functional as F
 
-from conv2d_f32_helpers import _golden_module
+from conv2d_f32_helpers import _golden_module, params64  # noqa: F401
 
 N_HIST_IMAGES = 4
 ENCODER = (0, 2, 4)            # modules of encoder_conv: Conv2d 3x3, stride 2, a ReLU after each
 DECODER = ((0, 2), (2, 2), (4, 1))      # (module of decoder_conv, stride): ConvTranspose2d 3x3; no ReLU after the last
 G = _golden_module("nb07")
-
-
-def params64(state, requires_grad=True):
-    return {k: torch.as_tensor(v).detach().cpu().double().clone().requires_grad_(requires_grad) for k, v in state.items()}
 
 
 def frame_input64(history, horizon, f):

@@ -5,16 +5,12 @@ from seeds by tests/golden/make_nb08_golden.py (draw_batch, draw_parameters)."""
 import torch
 import torch.nn.functional as F
 
-from conv2d_f32_helpers import _golden_module
+from conv2d_f32_helpers import _golden_module, params64  # noqa: F401
 
 STRIDE = (1, 2, 2)
 ENCODER = (0, 2, 4)            # modules of encoder_conv: Conv3d (2, 3, 3), stride (1, 2, 2), a ReLU after each
 DECODER = ((0, 2), (2, 2), (4, 1))      # (module of decoder_conv, stride): ConvTranspose2d 3x3; no ReLU after the last
 G = _golden_module("nb08")
-
-
-def params64(state, requires_grad=True):
-    return {k: torch.as_tensor(v).detach().cpu().double().clone().requires_grad_(requires_grad) for k, v in state.items()}
 
 
 def decoder_input64(encoder_out, horizon):

@@ -5,7 +5,7 @@ tests/golden/make_nb10_golden.py (draw_batch, draw_parameters), which also names
 import torch
 import torch.nn.functional as F
 
-from conv2d_f32_helpers import _golden_module
+from conv2d_f32_helpers import _golden_module, params64  # noqa: F401
 
 STRIPE_WIDTH = 128 // 24
 CONVS = ((0, 0, 1), (2, 0, 1), (4, 2, 1), (6, 2, 2))       # (module of self.conv, padding, stride); no ReLU after the last
@@ -24,10 +24,6 @@ def input64(history, horizon):
     history = torch.as_tensor(history).cpu().double()
     start = (torch.as_tensor(horizon).cpu().double() * STRIPE_WIDTH).trunc()
     return torch.cat((history, stripe_plane64(start, *history.shape[2:])), dim=1)
-
-
-def params64(state, requires_grad=True):
-    return {k: torch.as_tensor(v).detach().cpu().double().clone().requires_grad_(requires_grad) for k, v in state.items()}
 
 
 def forward64(p, batch):

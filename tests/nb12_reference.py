@@ -5,7 +5,7 @@ tests/golden/make_nb12_golden.py (draw_batch, draw_parameters), which also names
 import torch
 import torch.nn.functional as F
 
-from conv2d_f32_helpers import _golden_module
+from conv2d_f32_helpers import _golden_module, params64  # noqa: F401
 
 # (module of self.conv, padding, stride); kernel (2, 3, 3); no ReLU after the last
 CONVS = ((0, (0, 1, 1), 1), (2, (0, 1, 1), 1), (4, (1, 1, 1), 1), (6, (0, 1, 1), 1), (8, (0, 1, 1), (1, 2, 2)))
@@ -18,10 +18,6 @@ def input64(history, horizon):
     history = torch.as_tensor(history).cpu().double().unsqueeze(1)
     plane = torch.as_tensor(horizon).cpu().double().view(-1, 1, 1, 1, 1).expand(*history.shape)
     return torch.cat((history, plane), dim=1)
-
-
-def params64(state, requires_grad=True):
-    return {k: torch.as_tensor(v).detach().cpu().double().clone().requires_grad_(requires_grad) for k, v in state.items()}
 
 
 def forward64(p, batch):

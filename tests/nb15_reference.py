@@ -5,6 +5,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from conv2d_f32_helpers import params64  # noqa: F401
+
 MEAN = float(np.float32(93.23458))
 STD = float(np.float32(115.34247))
 ENC = (0, 2, 4, 6)       # nn.Conv2d modules of self.conv, stride 2
@@ -21,10 +23,6 @@ def input64(history, flow_pred, horizon):
     images = normalise64(torch.cat((history.double(), flow_pred.double().unsqueeze(1)), dim=1))
     b, _, h, w = images.shape
     return torch.cat((images, horizon.double().view(-1, 1, 1, 1).expand(b, 1, h, w)), dim=1)
-
-
-def params64(state, requires_grad=True):
-    return {k: torch.as_tensor(v).detach().cpu().double().clone().requires_grad_(requires_grad) for k, v in state.items()}
 
 
 def forward64(p, batch):

@@ -108,6 +108,29 @@ def run(monkeypatch, fn, args, answers):
     return text, results, sorted(key for key, _ in K._workspaces), error
 
 
+def check_glue_case(monkeypatch, glue_case):
+    """One row (wrapper, arguments, calls, results, workspace keys) of a notebook's GLUE table (tests/test_nbXX_cpu.py): what the
+    wrapper hands to the C ABI."""
+    fn, args, want_calls, want_results, want_keys = glue_case
+    text, results, keys, error = run(monkeypatch, fn, args, {})
+    assert error is None, error
+    assert [t.split(" ")[0] if t.startswith("require_cuda") else t for t in text] == want_calls
+    assert results == want_results and keys == want_keys
+
+
+def check_new_symbols(new_symbols, notebook=None):
+    """A notebook's entry points (name -> parameter count) are declared in the header with that many parameters, bound with as
+    many argtypes and exported by the library; the header names the notebook."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    declared = {name: params.count(",") + 1 for name, params in re.findall(r"\b(pv_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
+    for name, arity in new_symbols.items():
+        assert declared.get(name) == arity, (name, declared.get(name))
+        assert len(_lib.SIGNATURES[name]) == arity, name
+    lib = _lib.get_lib()
+    assert all(hasattr(lib, name) for name in new_symbols)
+    assert notebook is None or notebook in open(HEADER).read()
+
+
 def case(fn, answers=None, **args):
     return fn, args, answers or {}
 

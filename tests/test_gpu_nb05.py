@@ -7,9 +7,8 @@ element's float64 sum of |products|, NORM_TOL relative norm for reductions.  The
 torch.nn.grad.conv2d_weight, F.conv_transpose2d and, for the ConvTranspose2d's gradients, float64 autograd of the 33-channel
 F.conv_transpose2d.
 
-Parameters after three Adam steps (golden), the bounds of tests/test_gpu_nb15.py and test_gpu_nb08.py: Adam's step is about lr =
-1e-3 per step whatever the gradient's size, so 99 % of the elements of every tensor must agree to 1e-5; the remaining elements
-are those whose gradient is ~ 0 and may take either sign in two correct implementations: 3 * 2e-3 (+ 1e-6) in all.
+The model-level checks (golden fixture, full size, determinism, HIP-graph replay, Trainer.fit) are notebook_model_checks.py's,
+run by tests/test_gpu_notebook_models.py.
 """
 import os
 
@@ -18,11 +17,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conv2d_f32_helpers import NORM_TOL, ROOT, _ops, _rel, _to, _within
+from conv2d_f32_helpers import NORM_TOL, ROOT, _ops, _rel, _within
+from notebook_model_checks import _g, _randn
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(ROOT, "tests", "golden", "nb05_small.npz")
 # (batch, height, width) of the first layer's inputs: one output; odd sides; two column bands; full width; the model's size
 INPUTS_SHAPES = [(1, 3, 3), (2, 4, 7), (3, 9, 70), (1, 5, 128), (2, 64, 64)]
 # (batch, height, width) of the horizon ConvTranspose2d's input; (2, 5, 63) -> 65 wide takes two column bands, (2, 3, 126) is
@@ -30,14 +29,6 @@ INPUTS_SHAPES = [(1, 3, 3), (2, 4, 7), (3, 9, 70), (1, 5, 128), (2, 64, 64)]
 HORIZON_SHAPES = [(1, 1, 1), (2, 2, 5), (3, 7, 7), (2, 5, 63), (2, 3, 126), (1, 58, 58)]
 GATES = ((True, True), (False, False))      # (dy_gate, x_gate): every gradient with and without its gates
 PLANE_SCALES = (1.0, 0.25, 3.0, 7.0)        # flow prediction, t0 image, flow x, flow y: a swapped channel shows
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _randn(g, *shape, scale=1.0):
-    return torch.randn(*shape, generator=g) * scale
 
 
 # ---- 1. Conv2d 4 -> 32 over three tensors read in place ------------------------------------------------------------------
@@ -119,142 +110,7 @@ def test_horizon_conv_transpose_against_float64(device, n, h, w):
         _within(dx, dx64 * (x_gate > 0) if use_xg else dx64, absdx, what=f"horizon convT dx gates {use_dg} {use_xg}")
 
 
-# ---- 3. the model against the golden fixture ---------------------------------------------------------------------------
-def _model_cls():
-    from predict_pv_yield_amd.models.conv2d.nb05_more_inputs import LitAutoEncoder
-    return LitAutoEncoder
-
-
-def _load_model(device, init):
-    model = _model_cls()()
-    model.load_state_dict(init)
-    return model.to(device)
-
-
-@pytest.mark.parametrize("tag", ["a", "b"])
-def test_model_against_golden_and_float64(device, tag):
-    import nb05_reference as R
-    gold = np.load(GOLDEN)
-    batch, init = R.golden_case(gold, tag)
-    model = _load_model(device, init)
-    dbatch = _to(batch, device)
-    y_hat = model(dbatch)
-    assert tuple(y_hat.shape) == tuple(gold[f"{tag}/y_hat"].shape)
-    assert _rel(y_hat.detach(), gold[f"{tag}/y_hat"]) <= NORM_TOL
-    p64 = R.params64(init)
-    y64 = R.forward64(p64, batch)
-    assert _rel(y_hat.detach(), y64.detach()) <= NORM_TOL
-    loss64 = R.loss64(y64, batch["target_images"])
-    loss64.backward()
-    opt = model.configure_optimizers()
-    losses = []
-    for step in range(3):
-        opt.zero_grad(set_to_none=True)
-        loss = model.training_step(dbatch, 0)
-        loss.backward()
-        if step == 0:
-            assert abs(loss.item() - loss64.item()) <= 1e-5 * loss64.item(), (loss.item(), loss64.item())
-            for k, p in model.named_parameters():
-                err, err_gold = _rel(p.grad, p64[k].grad), _rel(p.grad, gold[f"{tag}/grad/{k}"])
-                print(f"{tag} grad {k}: rel {err:.3e} vs float64, {err_gold:.3e} vs the notebook (bound {NORM_TOL})")
-                assert err <= NORM_TOL and err_gold <= NORM_TOL, (k, err, err_gold)
-        opt.step()
-        losses.append(loss.item())
-    for got, want in zip(losses, gold[f"{tag}/losses"]):
-        assert abs(got - want) <= 1e-5 * want, (losses, gold[f"{tag}/losses"])
-    for k, p in model.named_parameters():
-        want = torch.from_numpy(gold[f"{tag}/step3/{k}"]).double()
-        err = (p.detach().cpu().double() - want).abs()
-        moved = (want - init[k].double()).abs()
-        q99 = err.flatten().sort().values[int(0.99 * (err.numel() - 1))].item()
-        print(f"{tag} step3 {k}: max {err.max().item():.3e} 99% {q99:.3e} moved median {moved.median().item():.3e}")
-        assert moved.median().item() >= 1e-4, k       # the fixture's parameters did move (three steps of lr = 1e-3)
-        assert q99 <= 1e-5, (k, q99)
-        assert err.max().item() <= 3 * 2e-3 + 1e-6, k
-
-
-def _golden_train(device, tag, steps=3):
-    import nb05_reference as R
-    batch, init = R.golden_case(None, tag)
-    model = _load_model(device, init)
-    dbatch = _to(batch, device)
-    opt = model.configure_optimizers()
-    losses = []
-    for _ in range(steps):
-        opt.zero_grad(set_to_none=True)
-        loss = model.training_step(dbatch, 0)
-        loss.backward()
-        opt.step()
-        losses.append(loss.item())
-    return model, losses
-
-
-@pytest.mark.parametrize("tag", ["a", "b"])
-def test_two_eager_runs_are_equal_bit_for_bit(device, tag):
-    m1, l1 = _golden_train(device, tag)
-    m2, l2 = _golden_train(device, tag)
-    assert l1 == l2
-    for (k, p), q in zip(m1.named_parameters(), m2.parameters()):
-        assert torch.equal(p, q), k
-
-
-@pytest.mark.parametrize("tag", ["a", "b"])
-def test_train_step_replays_as_a_hip_graph(device, tag):
-    import nb05_reference as R
-    from predict_pv_yield_amd.graphs import GraphedTrainStep
-    from predict_pv_yield_amd.optim import HipAdam
-    batch, init = R.golden_case(None, tag)
-    # the golden batch and two more of its shape: the replay reads what is copied into the captured batch
-    batches = [_to(batch, device)] + [_to(R.G.draw_batch(tag, seed=2000 + s), device) for s in range(2)]
-
-    def make(capturable):
-        model = _load_model(device, init)
-        return model, HipAdam(model.parameters(), lr=0.001, capturable=capturable)
-
-    model_e, opt_e = make(False)
-    model_g, opt_g = make(True)
-    step = GraphedTrainStep(model_g, opt_g, batches[0], warmup=2)
-    try:
-        for _ in range(2):
-            opt_e.zero_grad(set_to_none=True)
-            model_e.training_step(batches[0], 0).backward()
-            opt_e.step()
-        for i in range(5):
-            opt_e.zero_grad(set_to_none=True)
-            loss = model_e.training_step(batches[i % 3], 0)
-            loss.backward()
-            opt_e.step()
-            assert float(step(batches[i % 3])) == float(loss), f"step {i}"
-        for p, q in zip(model_g.parameters(), model_e.parameters()):
-            assert torch.equal(p, q)
-    finally:
-        step.close()
-
-
-def test_full_size_forward_loss_and_a_batch_of_one(device):
-    """The notebook's size (S = 64 -> [B, 1, 64, 64]) at B = 10, from which the 32 -> 32 Conv2d layers take their large-launch
-    route, and B = 1 at the smallest side, whose batch axis the notebook's squeeze() would drop; the field with and without its
-    singleton axis."""
-    import nb05_reference as R
-    torch.manual_seed(5)
-    model = _model_cls()().to(device)
-    g = _g(50)
-    for b, s in ((10, 64), (1, 7)):
-        batch = {"input_images": _randn(g, b, 1, s, s), "T0_IMAGES": _randn(g, b, 1, s, s),
-                 "optical_flow": _randn(g, b, 1, 2, s, s, scale=3.0), "forecast_horizon": _randn(g, b),
-                 "target_images": _randn(g, b, 1, s, s)}
-        dbatch = _to(batch, device)
-        y_hat = model(dbatch)
-        assert tuple(y_hat.shape) == (b, 1, s, s)
-        assert torch.equal(y_hat, model({**dbatch, "optical_flow": dbatch["optical_flow"].squeeze(1)}))
-        loss = model.training_step(dbatch, 0)
-        y64 = R.forward64(R.params64(model.state_dict(), requires_grad=False), batch)
-        assert _rel(y_hat.detach(), y64) <= NORM_TOL
-        ref = R.loss64(y64, batch["target_images"]).item()
-        assert abs(loss.item() - ref) <= 1e-5 * ref, (loss.item(), ref)
-
-
-# ---- 4. the data path on a hand-made device super-batch ------------------------------------------------------------------
+# ---- 3. the data path on a hand-made device super-batch ------------------------------------------------------------------
 def _hand_made_super_batch(device, t=5, h=40, w=36, border=6):
     """Pixel values encode (frame, row, column); the predictions carry a NaN border of 6 pixels; the field's x plane is the
     code + 0.25, its y plane the code + 0.5."""
@@ -315,7 +171,7 @@ def test_data_path_crops_one_window_from_all_four_tensors(device):
         D.super_batch_to_example(sb, np.random.default_rng(1), 30, max_retries=4)
 
 
-# ---- 5. one epoch through run.py's surface ---------------------------------------------------------------------------------
+# ---- 4. one epoch through run.py's surface ---------------------------------------------------------------------------------
 def test_one_epoch_of_the_configured_run(device, tmp_path, monkeypatch):
     """`run.py model=nb05_more_inputs datamodule=nb05_fake callbacks=none trainer.max_epochs=1` on a small fake set."""
     from predict_pv_yield_amd import hydra_lite as H

@@ -7,24 +7,20 @@ element's float64 sum of |products|, NORM_TOL relative norm for reductions.  The
 explicitly built [F B, 2, H, W] input, torch.nn.grad.conv2d_weight, F.conv_transpose2d and its float64 autograd (this torch
 has no torch.nn.grad function for the transposed form's weight gradient).
 
-Parameters after three Adam steps (golden), the bounds of tests/test_gpu_nb08.py: Adam's step is about lr = 1e-3 per step
-whatever the gradient's size, so 99 % of the elements of every tensor must agree to 1e-5; the remaining elements are those
-whose gradient is ~ 0 and may take either sign in two correct implementations: 3 * 2e-3 (+ 1e-6) in all.
+The model-level checks (golden fixture, full size, determinism, HIP-graph replay, Trainer.fit) are notebook_model_checks.py's,
+run by tests/test_gpu_notebook_models.py.
 """
-import os
-
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import nb07_reference as R
-from conv2d_f32_helpers import NORM_TOL, ROOT, _ops, _rel, _to, _within
-from predict_pv_yield_amd.models.conv2d.nb07_multi_hist import LitAutoEncoder, target_side      # absent: the file fails at import
+from conv2d_f32_helpers import NORM_TOL, _ops, _rel, _to, _within
+from notebook_model_checks import CASES, _g, _randn
+from predict_pv_yield_amd.models.conv2d.nb07_multi_hist import LitAutoEncoder      # absent: the file fails at import
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(ROOT, "tests", "golden", "nb07_small.npz")
 # (batch, height, width) of the history frames: one output; an unread row and column; odd and even sides; one block of nine
 # 16-position tiles over its four waves; the model's second size, the only one whose forward takes several row bands (31
 # rows of outputs as 16 + 15); full width, 7 x 63 outputs: one block in the forward, two row bands (the 384-position limit) in
@@ -34,14 +30,6 @@ FIRST_SHAPES = [(1, 3, 3), (2, 4, 4), (3, 7, 12), (2, 26, 26), (1, 63, 63), (2, 
 FRAMES_SHAPES = [(1, 1, 1), (2, 2, 5), (3, 7, 7), (1, 15, 15), (2, 5, 60), (2, 40, 3)]
 GATES = ((True, True), (False, False))      # (dy_gate, x_gate): every gradient with and without its gates
 HORIZONS = [0.0, -1.3, 0.7]                 # per example distinct: zero and both signs
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _randn(g, *shape, scale=1.0):
-    return torch.randn(*shape, generator=g) * scale
 
 
 def _out(s):
@@ -157,191 +145,7 @@ def test_frames_conv_transpose_of_one_frame_is_the_32_channel_layer(device, f):
     _within(y, F.conv_transpose2d(x64, w64, b64, stride=2), absref, what=f"frame {f} against float64")
 
 
-# ---- 3. the model against the golden fixture ---------------------------------------------------------------------------
-def _model_cls():
-    return LitAutoEncoder
-
-
-def _load_model(device, init):
-    model = _model_cls()()
-    model.load_state_dict(init)
-    return model.to(device)
-
-
-@pytest.mark.parametrize("tag", ["a", "b"])
-def test_model_against_golden(device, tag):
-    gold = np.load(GOLDEN)
-    batch, init = R.golden_case(gold, tag)
-    model = _load_model(device, init)
-    dbatch = _to(batch, device)
-    y_hat = model(dbatch)
-    assert tuple(y_hat.shape) == tuple(gold[f"{tag}/y_hat"].shape)
-    assert _rel(y_hat.detach(), gold[f"{tag}/y_hat"]) <= NORM_TOL
-    opt = model.configure_optimizers()
-    losses = []
-    for step in range(3):
-        opt.zero_grad(set_to_none=True)
-        loss = model.training_step(dbatch, 0)
-        loss.backward()
-        if step == 0:
-            for k, p in model.named_parameters():
-                err = _rel(p.grad, gold[f"{tag}/grad/{k}"])
-                print(f"{tag} grad {k}: rel {err:.3e} (bound {NORM_TOL})")
-                assert err <= NORM_TOL, (k, err)
-        opt.step()
-        losses.append(loss.item())
-    for got, want in zip(losses, gold[f"{tag}/losses"]):
-        assert abs(got - want) <= 1e-5 * want, (losses, gold[f"{tag}/losses"])
-    for k, p in model.named_parameters():
-        want = torch.from_numpy(gold[f"{tag}/step3/{k}"]).double()
-        err = (p.detach().cpu().double() - want).abs()
-        moved = (want - init[k].double()).abs()
-        q99 = err.flatten().sort().values[int(0.99 * (err.numel() - 1))].item()
-        print(f"{tag} step3 {k}: max {err.max().item():.3e} 99% {q99:.3e} moved median {moved.median().item():.3e}")
-        assert moved.median().item() >= 1e-4, k       # the fixture's parameters did move (three steps of lr = 1e-3)
-        assert q99 <= 1e-5, (k, q99)
-        assert err.max().item() <= 3 * 2e-3 + 1e-6, k
-
-
-# ---- 4. full size ------------------------------------------------------------------------------------------------------
-def _full_batch(seed, b=4, s=128):
-    g = _g(seed)
-    t = target_side(s)
-    return {"HISTORICAL_SAT_IMAGES": _randn(g, b, 4, s, s), "FORECAST_HORIZON": _randn(g, b),
-            "TARGET_SAT_IMAGE": _randn(g, b, t, t)}
-
-
-@pytest.mark.parametrize("b, s, out", [(4, 128, 65), (2, 15, 9)])
-def test_full_size_forward_and_loss(device, b, s, out):
-    """The notebook's size (S = 128 -> [B, 1, 65, 65]) and the smallest image the model takes (15 -> 1 x 1 inside)."""
-    torch.manual_seed(5)
-    model = _model_cls()().to(device)
-    batch = _full_batch(50, b, s)
-    y_hat = model(_to(batch, device))
-    assert tuple(y_hat.shape) == (b, 1, out, out)
-    loss = model.training_step(_to(batch, device), 0)
-    p = R.params64(model.state_dict(), requires_grad=False)
-    y64 = R.forward64(p, batch)
-    assert _rel(y_hat.detach(), y64) <= NORM_TOL
-    ref = R.loss64(y64, batch["TARGET_SAT_IMAGE"]).item()
-    assert abs(loss.item() - ref) <= 1e-5 * ref, (loss.item(), ref)
-
-
-def test_a_batch_of_one(device):
-    torch.manual_seed(6)
-    model = _model_cls()().to(device)
-    batch = _to(_full_batch(51, 1, 31), device)
-    assert tuple(model(batch).shape) == (1, 1, 17, 17)
-    assert torch.isfinite(model.training_step(batch, 0))
-
-
-# ---- 5. determinism and HIP-graph replay -------------------------------------------------------------------------------
-def _train(device, steps, seed=3, b=4):
-    torch.manual_seed(seed)
-    model = _model_cls()().to(device)
-    opt = model.configure_optimizers()
-    losses = []
-    for i in range(steps):
-        batch = _to(_full_batch(60 + i, b=b), device)
-        opt.zero_grad(set_to_none=True)
-        loss = model.training_step(batch, i)
-        loss.backward()
-        opt.step()
-        losses.append(loss.item())
-    return model, losses
-
-
-def test_train_steps_are_deterministic(device):
-    m1, l1 = _train(device, 3)
-    m2, l2 = _train(device, 3)
-    assert l1 == l2
-    for (k, p), q in zip(m1.named_parameters(), m2.parameters()):
-        assert torch.equal(p, q), k
-
-
-def test_train_step_replays_as_a_hip_graph(device):
-    from predict_pv_yield_amd.graphs import GraphedTrainStep
-    from predict_pv_yield_amd.optim import HipAdam
-    batches = [_to(_full_batch(70 + s), device) for s in range(3)]
-
-    def make(capturable):
-        torch.manual_seed(11)
-        model = _model_cls()().to(device)
-        return model, HipAdam(model.parameters(), lr=0.001, capturable=capturable)
-
-    model_e, opt_e = make(False)
-    model_g, opt_g = make(True)
-    step = GraphedTrainStep(model_g, opt_g, batches[0], warmup=2)
-    try:
-        for _ in range(2):
-            opt_e.zero_grad(set_to_none=True)
-            model_e.training_step(batches[0], 0).backward()
-            opt_e.step()
-        for i in range(5):
-            opt_e.zero_grad(set_to_none=True)
-            loss = model_e.training_step(batches[i % 3], 0)
-            loss.backward()
-            opt_e.step()
-            assert float(step(batches[i % 3])) == float(loss), f"step {i}"
-        for p, q in zip(model_g.parameters(), model_e.parameters()):
-            assert torch.equal(p, q)
-    finally:
-        step.close()
-
-
-# ---- 6. Trainer.fit on the fake datamodule -----------------------------------------------------------------------------
-def test_trainer_fit_on_the_fake_datamodule(device, tmp_path):
-    from predict_pv_yield_amd import lightning as pl
-    from predict_pv_yield_amd.data.nb08_datamodule import Nb08DataModule
-    class Recording(LitAutoEncoder):
-        seen = []
-
-        def log_dict(self, d, **kw):
-            type(self).seen.extend((k, v.detach()) for k, v in d.items())
-            return super().log_dict(d, **kw)
-
-    Recording.seen = []
-    torch.manual_seed(1)
-    model = Recording()
-    dm = Nb08DataModule(batch_size=4, n_train_data=3, n_val_data=1, n_super_batches=1)
-    ckpt = pl.ModelCheckpoint(save_last=True, dirpath=str(tmp_path / "ck"))
-    trainer = pl.Trainer(gpus=1, max_epochs=1, callbacks=[ckpt], log_every_n_steps=1)
-    trainer.fit(model, datamodule=dm)
-    batch = next(iter(dm.train_dataloader()))
-    assert tuple(batch["HISTORICAL_SAT_IMAGES"].shape) == (4, 4, 128, 128) and tuple(batch["TARGET_SAT_IMAGE"].shape) == (4, 64, 64)
-    assert batch["FORECAST_HORIZON"].dtype == torch.float32
-    train = [float(v) for k, v in Recording.seen if k == "Loss/Train"]
-    assert len(train) == 3 and all(np.isfinite(train)), train
-    assert any(k == "Loss/Validation" for k, _ in Recording.seen)
-    state = torch.load(ckpt.last_model_path)["state_dict"]
-    assert list(state) == [f"{part}_conv.{i}.{w}" for part in ("encoder", "decoder") for i in (0, 2, 4)
-                           for w in ("weight", "bias")]
-    fresh = LitAutoEncoder()
-    fresh.load_state_dict(state)
-    for (k, p), q in zip(model.state_dict().items(), fresh.state_dict().values()):
-        assert torch.equal(p.cpu(), q), k
-
-
-def test_trainer_fit_with_hip_graph_matches_the_eager_fit(device):
-    """`run.py ... +trainer.hip_graph=true`: Trainer(hip_graph=True) replays the step after its eager steps; more batches
-    than those, same parameters and logged losses as the eager fit."""
-    from predict_pv_yield_amd import lightning as pl
-    from predict_pv_yield_amd.data.nb08_datamodule import Nb08DataModule
-    dm = Nb08DataModule(batch_size=4, n_train_data=pl.Trainer.GRAPH_EAGER_STEPS + 3, n_val_data=1, n_super_batches=1)
-    results = []
-    for graph in (False, True):
-        torch.manual_seed(2)
-        model = _model_cls()()
-        trainer = pl.Trainer(gpus=1, max_epochs=1, hip_graph=graph, log_every_n_steps=1)
-        trainer.fit(model, datamodule=dm)
-        results.append(({k: v.detach().clone() for k, v in model.state_dict().items()}, dict(trainer.callback_metrics)))
-    (sd_e, log_e), (sd_g, log_g) = results
-    for k in sd_e:
-        assert torch.equal(sd_e[k], sd_g[k]), k
-    assert np.isfinite(float(log_g["Loss/Train_epoch"])) and float(log_g["Loss/Train_epoch"]) == float(log_e["Loss/Train_epoch"])
-
-
-# ---- 7. refusals through the Python surface ----------------------------------------------------------------------------
+# ---- 3. refusals through the Python surface ----------------------------------------------------------------------------
 def test_refusals_raise_before_any_launch(device):
     import ctypes
     from predict_pv_yield_amd import _lib
@@ -362,8 +166,8 @@ def test_refusals_raise_before_any_launch(device):
         K.convt2d_s2_frames_fwd_f32(z(1, 128, 8, 8).double(), z(128, 32, 3, 3), z(32))
     with pytest.raises(TypeError):
         K.conv2d_s2_frame_horizon_fwd_f32(z(1, 4, 8, 8), z(1).double(), z(32, 2, 3, 3), z(32))
-    model = _model_cls()().to(device)
-    good = _to(_full_batch(80, 2, 31), device)
+    model = LitAutoEncoder().to(device)
+    good = _to(CASES["nb07"].full_batch(80, 2, 31), device)
     with pytest.raises(ValueError, match="TARGET_SAT_IMAGE"):
         model.training_step({**good, "TARGET_SAT_IMAGE": z(2, 17, 17)}, 0)
     for side in (14, 129):

@@ -6,28 +6,24 @@ element's float64 sum of |products| (an element whose reference is exactly 0 mus
 reductions (weight and bias gradients).  The model has no pool, so the golden fixture (torch float32 on the CPU, the
 notebook's own cell) holds every gradient to NORM_TOL.
 
-Parameters after three Adam steps (golden), the rule stated at the top of tests/test_gpu_nb15.py: Adam's step is about lr =
-1e-3 whatever the gradient's size, so 99 % of the (stored) entries of every tensor must agree to 1e-5; the rest are entries
-whose gradient is ~ 0 and may take either sign in two correct implementations: 2 * lr per step, 3 * 2e-3 (+ 1e-6) in all.
+The model-level checks (golden fixture, full size, determinism, HIP-graph replay, Trainer.fit) are notebook_model_checks.py's,
+run by tests/test_gpu_notebook_models.py.
 
 Shapes are (batch, height, width) of the layer's input.  The tile planners of the gather and scatter forms take smaller tiles
 while the grid stays under 512 blocks, so the small shapes all run the smallest tile; PLANNER_* are tiny planes at a batch
 large enough that the larger tiles (256 / 128 positions per block in the gather, 128 class positions in the scatter) and
 weight-gradient slabs of several tiles are taken.
 """
-import os
-
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import nb09_reference as R
-from conv2d_f32_helpers import NORM_TOL, ROOT, _ops, _rel, _to, _within
+from conv2d_f32_helpers import NORM_TOL, _ops, _rel, _within
+from notebook_model_checks import _g, _randn
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(ROOT, "tests", "golden", "nb09_small.npz")
 # one output; non-square; even sides (dx's last row and column exactly 0); full width (63 output columns, every column band
 # the planner makes); the model's own third-layer plane
 CONV_SHAPES = [(1, 3, 3), (2, 5, 7), (2, 8, 10), (1, 4, 128), (2, 31, 31)]
@@ -41,14 +37,6 @@ STRIPE_SHAPES = [(1, 128, 128), (2, 9, 50), (3, 20, 54), (9, 128, 128)]      # t
 HEAD_SHAPES = [(1, 1, 1), (2, 4, 5), (3, 10, 47), (1, 63, 63), (1, 3, 126)]
 LOSS_SHAPES = [((2, 9, 25), (2, 8, 24)), ((1, 65, 65), (1, 64, 64))]
 GATES = ((True, True), (False, False))      # (dy_gate, x_gate): every gradient with and without its gates
-
-
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _randn(g, *shape, scale=1.0):
-    return torch.randn(*shape, generator=g) * scale
 
 
 def _conv_params(g, c_out, c_in, transposed=False):
@@ -317,127 +305,3 @@ def test_refusals_raise_before_any_launch(device):
     assert "workspace" in lib.pv_last_error().decode()
     torch.cuda.synchronize()
     assert (dw == 7.0).all(), "a refused call wrote its output"
-
-
-# ---- 7. the model against the golden -----------------------------------------------------------------------------------
-def _load_model(device, init):
-    from predict_pv_yield_amd.models.conv2d.nb09_stripe_ae import LitAutoEncoder
-    model = LitAutoEncoder()
-    model.load_state_dict(init)
-    return model.to(device)
-
-
-@pytest.mark.parametrize("tag", ["a", "b"])
-def test_model_against_golden(device, tag):
-    gold = np.load(GOLDEN)
-    batch, init = R.G.draw_batch(tag), R.G.draw_parameters()
-    model = _load_model(device, init)
-    dbatch = _to(batch, device)
-    y_hat = model(dbatch)
-    assert tuple(y_hat.shape) == tuple(gold[f"{tag}/y_hat"].shape)
-    R.check_stored(gold, f"{tag}/y_hat", y_hat, NORM_TOL)
-    opt = model.configure_optimizers()
-    losses = []
-    for step in range(3):
-        opt.zero_grad(set_to_none=True)
-        loss = model.training_step(dbatch, 0)
-        loss.backward()
-        if step == 0:
-            for k, p in model.named_parameters():       # every figure first, then the assertions
-                err = R.check_stored(gold, f"{tag}/grad/{k}", p.grad, NORM_TOL, entries_only=True)
-                print(f"{tag} grad {k}: rel {err:.3e} (bound {NORM_TOL})")
-            for k, p in model.named_parameters():
-                R.check_stored(gold, f"{tag}/grad/{k}", p.grad, NORM_TOL)
-        opt.step()
-        losses.append(loss.item())
-    for got, want in zip(losses, gold[f"{tag}/losses"]):
-        assert abs(got - want) <= 1e-5 * want, (losses, gold[f"{tag}/losses"])
-    for k, p in model.named_parameters():
-        got, _ = R.stored(f"{tag}/step3/{k}", p)
-        first, _ = R.stored(f"{tag}/step3/{k}", init[k])
-        want = torch.from_numpy(gold[f"{tag}/step3/{k}"]).double().reshape(got.shape)
-        err = (got - want).abs()
-        moved = (want - first).abs()
-        q99 = err.flatten().sort().values[int(0.99 * (err.numel() - 1))].item()
-        print(f"{tag} step3 {k}: max {err.max().item():.3e} 99% {q99:.3e} moved median {moved.median().item():.3e}")
-        assert moved.median().item() >= 1e-4, k       # the fixture's parameters did move (three steps of lr = 1e-3)
-        assert q99 <= 1e-5, (k, q99)
-        assert err.max().item() <= 3 * 2e-3 + 1e-6, k
-
-
-# ---- 8. full size, determinism and HIP-graph replay --------------------------------------------------------------------
-def _full_batch(seed, b=2, s=128):
-    g = _g(seed)
-    return {"HISTORICAL_SAT_IMAGES": _randn(g, b, 4, s, s), "FORECAST_HORIZON": torch.randint(1, 24, (b,), generator=g),
-            "TARGET_SAT_IMAGE": _randn(g, b, 64, 64)}
-
-
-def test_full_size_forward_and_loss(device):
-    """The notebook's size (S = 128 -> [B, 1, 65, 65], target 64 x 64) with a float horizon and one beyond the image, against
-    float64."""
-    from predict_pv_yield_amd.models.conv2d.nb09_stripe_ae import LitAutoEncoder
-    torch.manual_seed(5)
-    model = LitAutoEncoder().to(device)
-    batch = _full_batch(50)
-    batch["FORECAST_HORIZON"] = torch.tensor([7.9, 26.0])
-    y_hat = model(_to(batch, device))
-    assert tuple(y_hat.shape) == (2, 1, 65, 65)
-    loss = model.training_step(_to(batch, device), 0)
-    y64 = R.forward64(R.params64(model.state_dict(), requires_grad=False), batch)
-    assert _rel(y_hat.detach(), y64) <= NORM_TOL
-    ref = R.loss64(y64, batch["TARGET_SAT_IMAGE"]).item()
-    assert abs(loss.item() - ref) <= 1e-5 * ref, (loss.item(), ref)
-
-
-def test_train_step_replays_as_a_hip_graph(device):
-    """Three steps through GraphedTrainStep: losses and parameters bit-identical to three eager steps from the same state."""
-    from predict_pv_yield_amd.graphs import GraphedTrainStep
-    from predict_pv_yield_amd.models.conv2d.nb09_stripe_ae import LitAutoEncoder
-    from predict_pv_yield_amd.optim import HipAdam
-    batches = [_to(_full_batch(70 + s), device) for s in range(3)]
-
-    def make(capturable):
-        torch.manual_seed(11)
-        model = LitAutoEncoder().to(device)
-        return model, HipAdam(model.parameters(), lr=0.001, capturable=capturable)
-
-    model_e, opt_e = make(False)
-    model_g, opt_g = make(True)
-    step = GraphedTrainStep(model_g, opt_g, batches[0], warmup=2)
-    try:
-        for _ in range(2):                      # the warm-up steps are training steps: the eager model takes them too
-            opt_e.zero_grad(set_to_none=True)
-            model_e.training_step(batches[0], 0).backward()
-            opt_e.step()
-        for p, q in zip(model_g.parameters(), model_e.parameters()):
-            assert torch.equal(p, q)
-        for i in range(3):
-            opt_e.zero_grad(set_to_none=True)
-            loss = model_e.training_step(batches[i], 0)
-            loss.backward()
-            opt_e.step()
-            assert float(step(batches[i])) == float(loss), f"step {i}"
-        for p, q in zip(model_g.parameters(), model_e.parameters()):
-            assert torch.equal(p, q)
-    finally:
-        step.close()
-
-
-def test_trainer_fit_on_the_fake_datamodule(device):
-    """`run.py model=nb09_stripe_ae datamodule=nb10_fake` in small: an epoch, eagerly and graph-replayed, same parameters."""
-    from predict_pv_yield_amd import lightning as pl
-    from predict_pv_yield_amd.data.nb10_datamodule import Nb10DataModule
-    from predict_pv_yield_amd.models.conv2d.nb09_stripe_ae import LitAutoEncoder
-    dm = Nb10DataModule(batch_size=2, n_train_data=pl.Trainer.GRAPH_EAGER_STEPS + 2, n_val_data=1, n_super_batches=1,
-                        n_timesteps=12)
-    results = []
-    for graph in (False, True):
-        torch.manual_seed(2)
-        model = LitAutoEncoder()
-        trainer = pl.Trainer(gpus=1, max_epochs=1, hip_graph=graph, log_every_n_steps=1)
-        trainer.fit(model, datamodule=dm)
-        results.append(({k: v.detach().clone() for k, v in model.state_dict().items()}, dict(trainer.callback_metrics)))
-    (sd_e, log_e), (sd_g, log_g) = results
-    for k in sd_e:
-        assert torch.equal(sd_e[k], sd_g[k]), k
-    assert np.isfinite(float(log_g["Loss/Train_epoch"])) and float(log_g["Loss/Train_epoch"]) == float(log_e["Loss/Train_epoch"])

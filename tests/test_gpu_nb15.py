@@ -5,24 +5,19 @@ Tolerances are the project's own for exact-f32 conv kernels (conv2d_f32_helpers)
 element's float64 sum of |products|, NORM_TOL relative norm for reductions.  The model has no pool, so the golden fixture
 (torch float32 on the CPU) holds every gradient to NORM_TOL.
 
-Parameters after three Adam steps (golden, case a), the bounds of tests/test_gpu_nb16.py: Adam's step is lr * m / (sqrt(v)
-+ eps), about lr = 1e-3 per step whatever the gradient's size, so 99 % of the elements of every tensor must agree to 1e-5;
-the remaining elements are those whose gradient is ~ 0 and may take either sign in two correct implementations: they may
-differ by 2 * lr per step, 3 * 2e-3 (+ 1e-6) in all.
+The model-level checks (golden fixture, full size, determinism, HIP-graph replay, Trainer.fit) are notebook_model_checks.py's,
+run by tests/test_gpu_notebook_models.py.
 """
-import os
-
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import nb15_reference as R
-from conv2d_f32_helpers import NORM_TOL, ROOT, _ops, _rel, _to, _within
+from conv2d_f32_helpers import NORM_TOL, _ops, _rel, _within
+from notebook_model_checks import _counts, _g, _randn
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(ROOT, "tests", "golden", "nb15_small.npz")
 # (batch, height, width) of a Conv2d's input: one output; one output with an unread row and column; an unread column only;
 # even sides over several tiles; the model's second layer at full size; full width over several row bands
 CONV_SHAPES = [(1, 3, 3), (2, 4, 4), (3, 7, 12), (2, 26, 26), (1, 63, 63), (2, 15, 128)]
@@ -32,24 +27,8 @@ CONVT_SHAPES = [(1, 1, 1), (2, 2, 5), (3, 7, 7), (1, 15, 15), (2, 31, 31), (1, 5
 GATES = ((True, True), (False, False))      # (dy_gate, x_gate): every gradient with and without its gates
 
 
-def _g(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def _randn(g, *shape, scale=1.0):
-    return torch.randn(*shape, generator=g) * scale
-
-
 def _conv_params(g, c_out, c_in):
     return _randn(g, c_out, c_in, 3, 3, scale=(9 * c_in) ** -0.5), _randn(g, c_out, scale=0.1)
-
-
-def _counts(g, n, h, w, integer_flow=False):
-    hist = torch.randint(0, 1024, (n, 4, h, w), generator=g).to(torch.int16)
-    flow = torch.randint(0, 1024, (n, h, w), generator=g).float()
-    if not integer_flow:
-        flow = flow + torch.rand(n, h, w, generator=g) * 0.5
-    return hist, flow, _randn(g, n)
 
 
 def _out(s):
@@ -189,191 +168,7 @@ def test_window_normalised_mse_against_float64(device, dtype, n, side):
     _within(grad, 2 * d64 / count, 2 * (y_hat.double().abs() + t64.abs()) / count, what="dy_hat")
 
 
-# ---- 5. the model against the golden -----------------------------------------------------------------------------------
-def _load_model(device, init):
-    from predict_pv_yield_amd.models.conv2d.nb15_strided_ae import LitAutoEncoder
-    model = LitAutoEncoder()
-    model.load_state_dict(init)
-    return model.to(device)
-
-
-@pytest.mark.parametrize("tag", ["a", "b"])
-def test_model_against_golden(device, tag):
-    gold = np.load(GOLDEN)
-    batch, init = R.golden_case(gold, tag)
-    model = _load_model(device, init)
-    dbatch = _to(batch, device)
-    y_hat = model(dbatch)
-    assert tuple(y_hat.shape) == tuple(gold[f"{tag}/y_hat"].shape)
-    assert _rel(y_hat.detach(), gold[f"{tag}/y_hat"]) <= NORM_TOL
-    opt = model.configure_optimizers()
-    losses = []
-    for step in range(3):
-        opt.zero_grad(set_to_none=True)
-        loss = model.training_step(dbatch, 0)
-        loss.backward()
-        if step == 0:
-            for k, p in model.named_parameters():
-                err = _rel(p.grad, gold[f"{tag}/grad/{k}"])
-                print(f"{tag} grad {k}: rel {err:.3e} (bound {NORM_TOL})")
-                assert err <= NORM_TOL, (k, err)
-        opt.step()
-        losses.append(loss.item())
-    for got, want in zip(losses, gold[f"{tag}/losses"]):
-        assert abs(got - want) <= 1e-5 * want, (losses, gold[f"{tag}/losses"])
-    if f"{tag}/step3/conv.0.weight" not in gold.files:
-        return                                     # case b stores losses only after the first step (fixture size)
-    for k, p in model.named_parameters():
-        want = torch.from_numpy(gold[f"{tag}/step3/{k}"]).double()
-        err = (p.detach().cpu().double() - want).abs()
-        moved = (want - init[k].double()).abs()
-        q99 = err.flatten().sort().values[int(0.99 * (err.numel() - 1))].item()
-        print(f"{tag} step3 {k}: max {err.max().item():.3e} 99% {q99:.3e} moved median {moved.median().item():.3e}")
-        assert moved.median().item() >= 1e-4, k       # the fixture's parameters did move (three steps of lr = 1e-3)
-        assert q99 <= 1e-5, (k, q99)
-        assert err.max().item() <= 3 * 2e-3 + 1e-6, k
-
-
-# ---- 6. full size ------------------------------------------------------------------------------------------------------
-def _full_batch(seed, b=4, s=128):
-    from predict_pv_yield_amd.models.conv2d.nb15_strided_ae import target_side
-    g = _g(seed)
-    hist, flow, hor = _counts(g, b, s, s)
-    t = target_side(s)
-    target = torch.randint(0, 1024, (b, t, t), generator=g).to(torch.int16)
-    return {"HISTORICAL_SAT_IMAGES": hist, "OPTICAL_FLOW_PREDICTIONS": flow, "FORECAST_HORIZON": hor,
-            "TARGET_SAT_IMAGE": target}
-
-
-@pytest.mark.parametrize("b, s, out", [(4, 128, 63), (2, 31, 15)])
-def test_full_size_forward_and_loss(device, b, s, out):
-    """The notebook's size (B = 4, S = 128 -> [4, 1, 63, 63]) and the smallest image the model takes (31 -> 1 x 1 inside)."""
-    from predict_pv_yield_amd.models.conv2d.nb15_strided_ae import LitAutoEncoder
-    torch.manual_seed(5)
-    model = LitAutoEncoder().to(device)
-    batch = _full_batch(50, b, s)
-    y_hat = model(_to(batch, device))
-    assert tuple(y_hat.shape) == (b, 1, out, out)
-    loss = model.training_step(_to(batch, device), 0)
-    p = R.params64(model.state_dict(), requires_grad=False)
-    y64 = R.forward64(p, batch)
-    assert _rel(y_hat.detach(), y64) <= NORM_TOL
-    ref = R.loss64(y64, batch["TARGET_SAT_IMAGE"]).item()
-    assert abs(loss.item() - ref) <= 1e-5 * ref, (loss.item(), ref)
-
-
-# ---- 7. determinism and HIP-graph replay -------------------------------------------------------------------------------
-def _train(device, steps, seed=3, b=4):
-    from predict_pv_yield_amd.models.conv2d.nb15_strided_ae import LitAutoEncoder
-    torch.manual_seed(seed)
-    model = LitAutoEncoder().to(device)
-    opt = model.configure_optimizers()
-    losses = []
-    for i in range(steps):
-        batch = _to(_full_batch(60 + i, b=b), device)
-        opt.zero_grad(set_to_none=True)
-        loss = model.training_step(batch, i)
-        loss.backward()
-        opt.step()
-        losses.append(loss.item())
-    return model, losses
-
-
-def test_train_steps_are_deterministic(device):
-    m1, l1 = _train(device, 3)
-    m2, l2 = _train(device, 3)
-    assert l1 == l2
-    for (k, p), q in zip(m1.named_parameters(), m2.parameters()):
-        assert torch.equal(p, q), k
-
-
-def test_train_step_replays_as_a_hip_graph(device):
-    from predict_pv_yield_amd.graphs import GraphedTrainStep
-    from predict_pv_yield_amd.models.conv2d.nb15_strided_ae import LitAutoEncoder
-    from predict_pv_yield_amd.optim import HipAdam
-    batches = [_to(_full_batch(70 + s), device) for s in range(3)]
-
-    def make(capturable):
-        torch.manual_seed(11)
-        model = LitAutoEncoder().to(device)
-        return model, HipAdam(model.parameters(), lr=0.001, capturable=capturable)
-
-    model_e, opt_e = make(False)
-    model_g, opt_g = make(True)
-    step = GraphedTrainStep(model_g, opt_g, batches[0], warmup=2)
-    try:
-        for _ in range(2):
-            opt_e.zero_grad(set_to_none=True)
-            model_e.training_step(batches[0], 0).backward()
-            opt_e.step()
-        for i in range(5):
-            opt_e.zero_grad(set_to_none=True)
-            loss = model_e.training_step(batches[i % 3], 0)
-            loss.backward()
-            opt_e.step()
-            assert float(step(batches[i % 3])) == float(loss), f"step {i}"
-        for p, q in zip(model_g.parameters(), model_e.parameters()):
-            assert torch.equal(p, q)
-    finally:
-        step.close()
-
-
-# ---- 8. Trainer.fit on the fake datamodule -----------------------------------------------------------------------------
-def test_trainer_fit_on_the_fake_datamodule(device, tmp_path):
-    from predict_pv_yield_amd import lightning as pl
-    from predict_pv_yield_amd.data.nb15_datamodule import Nb15DataModule
-    from predict_pv_yield_amd.models.conv2d.nb15_strided_ae import LitAutoEncoder
-
-    class Recording(LitAutoEncoder):
-        seen = []
-
-        def log_dict(self, d, **kw):
-            type(self).seen.extend((k, v.detach()) for k, v in d.items())
-            return super().log_dict(d, **kw)
-
-    Recording.seen = []
-    torch.manual_seed(1)
-    model = Recording()
-    dm = Nb15DataModule(batch_size=4, n_train_data=3, n_val_data=1, n_super_batches=1)
-    ckpt = pl.ModelCheckpoint(save_last=True, dirpath=str(tmp_path / "ck"))
-    trainer = pl.Trainer(gpus=1, max_epochs=1, callbacks=[ckpt], log_every_n_steps=1)
-    trainer.fit(model, datamodule=dm)
-    batch = next(iter(dm.train_dataloader()))
-    assert batch["HISTORICAL_SAT_IMAGES"].dtype == torch.int16 and tuple(batch["HISTORICAL_SAT_IMAGES"].shape) == (4, 4, 128, 128)
-    assert batch["OPTICAL_FLOW_PREDICTIONS"].dtype == torch.float32 and tuple(batch["TARGET_SAT_IMAGE"].shape) == (4, 64, 64)
-    assert float(batch["HISTORICAL_SAT_IMAGES"].float().max()) > 10.0          # raw counts, not normalised
-    train = [float(v) for k, v in Recording.seen if k == "Loss/Train"]
-    assert len(train) == 3 and all(np.isfinite(train)), train
-    assert any(k == "Loss/Validation" for k, _ in Recording.seen)
-    state = torch.load(ckpt.last_model_path)["state_dict"]
-    assert list(state) == [f"conv.{i}.{w}" for i in R.ENC + R.DEC for w in ("weight", "bias")]
-    fresh = LitAutoEncoder()
-    fresh.load_state_dict(state)
-    for (k, p), q in zip(model.state_dict().items(), fresh.state_dict().values()):
-        assert torch.equal(p.cpu(), q), k
-
-
-def test_trainer_fit_with_hip_graph_matches_the_eager_fit(device):
-    """`run.py ... +trainer.hip_graph=true`: Trainer(hip_graph=True) replays the step after its eager steps; more batches
-    than those, same parameters and logged losses as the eager fit."""
-    from predict_pv_yield_amd import lightning as pl
-    from predict_pv_yield_amd.data.nb15_datamodule import Nb15DataModule
-    from predict_pv_yield_amd.models.conv2d.nb15_strided_ae import LitAutoEncoder
-    dm = Nb15DataModule(batch_size=4, n_train_data=pl.Trainer.GRAPH_EAGER_STEPS + 3, n_val_data=1, n_super_batches=1)
-    results = []
-    for graph in (False, True):
-        torch.manual_seed(2)
-        model = LitAutoEncoder()
-        trainer = pl.Trainer(gpus=1, max_epochs=1, hip_graph=graph, log_every_n_steps=1)
-        trainer.fit(model, datamodule=dm)
-        results.append(({k: v.detach().clone() for k, v in model.state_dict().items()}, dict(trainer.callback_metrics)))
-    (sd_e, log_e), (sd_g, log_g) = results
-    for k in sd_e:
-        assert torch.equal(sd_e[k], sd_g[k]), k
-    assert np.isfinite(float(log_g["Loss/Train_epoch"])) and float(log_g["Loss/Train_epoch"]) == float(log_e["Loss/Train_epoch"])
-
-
-# ---- 9. refusals through the Python surface ----------------------------------------------------------------------------
+# ---- 5. refusals through the Python surface ----------------------------------------------------------------------------
 def test_refusals_raise_before_any_launch(device):
     import ctypes
     from predict_pv_yield_amd import _lib

@@ -4,7 +4,6 @@ count and side rule, its refusals, the configs, the data path's host index rule 
 arithmetic, and the C ABI's glue and refusals."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,10 +11,10 @@ import torch
 
 import nb05_reference as R
 from conv2d_f32_helpers import NORM_TOL, ROOT, _rel
-from test_conv2d_glue_cpu import T, run
+from notebook_model_checks import check_fit64
+from test_conv2d_glue_cpu import T, check_glue_case, check_new_symbols
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "nb05_small.npz")
-HEADER = os.path.join(ROOT, "include", "pv_yield_hip.h")
 NEW_SYMBOLS = {"pv_conv2d_ae_inputs_fwd_f32": 11, "pv_conv2d_ae_inputs_bwd_weight_workspace_bytes": 4,
                "pv_conv2d_ae_inputs_bwd_weight_f32": 13, "pv_convt2d_ae_horizon_fwd_f32": 10,
                "pv_convt2d_ae_horizon_bwd_weight_workspace_bytes": 4, "pv_convt2d_ae_horizon_bwd_weight_f32": 12}
@@ -36,18 +35,7 @@ def test_reference_matches_the_golden(tag):
     loss.backward()
     for k, v in p.items():
         assert _rel(v.grad, gold[f"{tag}/grad/{k}"]) <= NORM_TOL, k
-    # three float64 Adam steps land where the notebook's float32 ones did (the maker's check_fit, restated)
-    p = R.params64(R.G.draw_parameters())
-    opt = torch.optim.Adam(list(p.values()), lr=R.G.LR)
-    for want in gold[f"{tag}/losses"]:
-        opt.zero_grad()
-        loss = R.loss64(R.forward64(p, batch), batch["target_images"])
-        assert abs(loss.item() - want) <= 1e-5 * want
-        loss.backward()
-        opt.step()
-    for k, v in p.items():
-        err = (v.detach() - torch.from_numpy(gold[f"{tag}/step3/{k}"]).double()).abs().flatten().sort().values
-        assert err[int(0.99 * (err.numel() - 1))].item() <= R.G.FIT_Q99, k
+    check_fit64(R, gold, tag, batch, "target_images")
 
 
 def test_golden_cases_are_the_ones_the_issue_names():
@@ -228,15 +216,7 @@ def test_config_composes_and_instantiates():
 
 
 def test_new_symbols_are_declared_and_bound_with_matching_arity():
-    from predict_pv_yield_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = {name: params.count(",") + 1 for name, params in re.findall(r"\b(pv_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
-    for name, arity in NEW_SYMBOLS.items():
-        assert declared.get(name) == arity, (name, declared.get(name))
-        assert len(_lib.SIGNATURES[name]) == arity, name
-    lib = _lib.get_lib()
-    assert all(hasattr(lib, name) for name in NEW_SYMBOLS)
-    assert "05_more_image_inputs.ipynb" in open(HEADER).read()
+    check_new_symbols(NEW_SYMBOLS, "05_more_image_inputs.ipynb")
 
 
 def test_entry_points_refuse_bad_arguments_without_launching():
@@ -321,11 +301,7 @@ GLUE = {
 
 @pytest.mark.parametrize("case_id", sorted(GLUE))
 def test_new_wrappers_hand_the_abi_what_the_table_pins(monkeypatch, case_id):
-    fn, args, want_calls, want_results, want_keys = GLUE[case_id]
-    text, results, keys, error = run(monkeypatch, fn, args, {})
-    assert error is None, error
-    assert [t.split(" ")[0] if t.startswith("require_cuda") else t for t in text] == want_calls
-    assert results == want_results and keys == want_keys
+    check_glue_case(monkeypatch, GLUE[case_id])
 
 
 def test_functional_names_the_new_layers_and_chain():

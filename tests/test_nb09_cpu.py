@@ -11,7 +11,7 @@ import torch
 
 import nb09_reference as R
 from conv2d_f32_helpers import NORM_TOL, ROOT
-from test_conv2d_glue_cpu import T, run
+from test_conv2d_glue_cpu import T, check_glue_case, run
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "nb09_small.npz")
 KEYS = [f"{m}.{i}.{w}" for m in ("encoder_conv", "decoder_conv") for i in (0, 2, 4) for w in ("weight", "bias")]
@@ -253,11 +253,7 @@ GLUE_ERRORS = {
 
 @pytest.mark.parametrize("case_id", sorted(GLUE))
 def test_new_wrappers_hand_the_abi_what_the_table_pins(monkeypatch, case_id):
-    fn, args, want_calls, want_results, want_keys = GLUE[case_id]
-    text, results, keys, error = run(monkeypatch, fn, args, {})
-    assert error is None, error
-    assert [t.split(" ")[0] if t.startswith("require_cuda") else t for t in text] == want_calls
-    assert results == want_results and keys == want_keys
+    check_glue_case(monkeypatch, GLUE[case_id])
 
 
 @pytest.mark.parametrize("case_id", sorted(GLUE_ERRORS))

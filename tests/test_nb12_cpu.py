@@ -4,7 +4,6 @@ rule, its refusals, the config, the fake datamodule's draws against the notebook
 identical cells produced), its horizons against the notebook's formula, and the C ABI's glue and refusals."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,10 +11,10 @@ import torch
 
 import nb12_reference as R
 from conv2d_f32_helpers import NORM_TOL, ROOT, _golden_module
+from test_conv2d_glue_cpu import check_new_symbols
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "nb12_small.npz")
 SAMPLER = os.path.join(ROOT, "tests", "golden", "nb10_sampler.npz")
-HEADER = os.path.join(ROOT, "include", "pv_yield_hip.h")
 NEW_SYMBOLS = {"pv_conv3d_wide_fwd_f32": 14, "pv_conv3d_wide_bwd_data_f32": 14, "pv_conv3d_wide_bwd_weight_workspace_bytes": 9,
                "pv_conv3d_wide_bwd_weight_f32": 16, "pv_conv3d_wide_horizon_fwd_f32": 11,
                "pv_conv3d_wide_horizon_bwd_weight_workspace_bytes": 6, "pv_conv3d_wide_horizon_bwd_weight_f32": 13,
@@ -174,14 +173,7 @@ def test_datamodule_batches_on_the_cpu():
 
 
 def test_new_symbols_are_declared_and_bound_with_matching_arity():
-    from predict_pv_yield_amd import _lib
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = {name: params.count(",") + 1 for name, params in re.findall(r"\b(pv_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
-    for name, arity in NEW_SYMBOLS.items():
-        assert declared.get(name) == arity, (name, declared.get(name))
-        assert len(_lib.SIGNATURES[name]) == arity, name
-    lib = _lib.get_lib()
-    assert all(hasattr(lib, name) for name in NEW_SYMBOLS)
+    check_new_symbols(NEW_SYMBOLS)
 
 
 def test_entry_points_refuse_bad_arguments_without_launching():

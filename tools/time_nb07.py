@@ -12,14 +12,13 @@ Warm-up first, device-side event timing of INNER back-to-back calls per sample, 
 general, torch, ours, ...), inputs resident before the timed region; the samples' min and max are kept as the spread.  Prints
 a table and one JSON line.
    python tools/time_nb07.py [batch=64] [reps=7]"""
-import json, os, sys, time
+import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
+import nb_timing as NT
 from predict_pv_yield_amd import hip_ops as K
-from predict_pv_yield_amd.graphs import GraphedTrainStep
 from predict_pv_yield_amd.models.conv2d.nb07_multi_hist import LitAutoEncoder, target_side
-from predict_pv_yield_amd.optim import HipAdam
 
 dev = torch.device("cuda:0")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
@@ -34,39 +33,9 @@ batch = {"HISTORICAL_SAT_IMAGES": torch.randn(B, FRAMES, S, S, generator=g).to(d
          "FORECAST_HORIZON": ((torch.randint(1, 25, (B,), generator=g).float() - 12.5) / 6.9222).to(dev),
          "TARGET_SAT_IMAGE": torch.randn(B, T, T, generator=g).to(dev)}
 
-# ---- the train step ------------------------------------------------------------------------------------------------
-torch.manual_seed(0)
-model = LitAutoEncoder().to(dev)
-opt = model.configure_optimizers()
-
-
-def step():
-    opt.zero_grad(set_to_none=True)
-    model.training_step(batch, 0).backward()
-    opt.step()
-
-
-def wall(fn):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(REPS):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / REPS
-
-
-eager = wall(step)
-torch.manual_seed(0)
-gmodel = LitAutoEncoder().to(dev)
-gopt = HipAdam(gmodel.parameters(), lr=0.001, capturable=True)
-graphed = GraphedTrainStep(gmodel, gopt, batch, warmup=2)
-replay = wall(lambda: graphed(batch))
-graphed.close()
-del gmodel, gopt, graphed
-print(f"nb07 LitAutoEncoder B={B} {S}x{S}: eager {eager * 1e3:.3f} ms/step ({B / eager:.1f} samples/s), HIP graph "
-      f"{replay * 1e3:.3f} ms/step ({B / replay:.1f} samples/s)", flush=True)
+# ---- the train step, eager and replayed (tools/nb_timing.py) ----------------------------------------------------------
+model, eager, replay = NT.graph_and_eager(LitAutoEncoder, batch, 0.001, REPS, warmup=2)
+print(NT.step_line("nb07", B, S, eager, replay), flush=True)
 
 # ---- every conv launch of the step -------------------------------------------------------------------------------------
 hist, horizon = batch["HISTORICAL_SAT_IMAGES"], batch["FORECAST_HORIZON"]
@@ -150,70 +119,22 @@ cases += convt_rows("decoder_conv.4 32->1 s1 (head)", d2, wd4, bd4, dy_d4, 1,
                     lambda: K.convt2d_head_bwd_weight_f32(d2, dy_d4, None, tuple(wd4.shape)))
 
 
-def device_ms(fn):
-    e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0_.record()
-    for _ in range(INNER):
-        fn()
-    e1_.record()
-    e1_.synchronize()
-    return e0_.elapsed_time(e1_) / INNER
+rows_out, ratios, refused, tot, ours_all = [], {}, {}, NT.totals(), 0.0
+print(NT.spread_header(58))
+for i, r in enumerate(NT.time_cases(cases, REPS, INNER, warmup=2)):
+    ours_all += r.ours.med
+    rows_out.append(NT.spread_record(r, new_kernel=i in NEW))
+    if r.general:                  # a refused launch is left out of both sums
+        NT.add(tot, r)
+        ratios[r.name] = rows_out[-1]["ours_over_general"]
+    else:
+        refused[r.name] = r.why_general
+    print(NT.spread_line(r, 58), flush=True)
 
-
-def usable(fn):
-    """None where the route takes the launch, else its message: such a launch is reported, not timed."""
-    try:
-        fn()
-        torch.cuda.synchronize()
-        return None
-    except Exception as e:
-        return f"{type(e).__name__}: {str(e)[:200]}"
-
-
-med = lambda v: sorted(v)[len(v) // 2] if v else float("nan")      # noqa: E731
-r4 = lambda v: round(v, 4) if v == v else None      # noqa: E731
-rows_out, ratios, refused = [], {}, {}
-tot = {"ours": 0.0, "general": 0.0, "torch": 0.0, "gflop": 0.0, "ours_all": 0.0}
-print(f"{'launch':58s} {'GFLOP':>7s} {'ours ms':>8s} {'spread':>15s} {'general ms':>10s} {'spread':>15s} {'ours/gen':>8s} "
-      f"{'torch ms':>9s}")
-for i, (name, gflop, ours, general, torch_fn) in enumerate(cases):
-    for _ in range(2):
-        ours()
-    why_g, why_t = usable(general), usable(torch_fn)
-    ok_g, ok_t = why_g is None, why_t is None
-    if not ok_g:
-        refused[name] = why_g
-        print(f"{name}: the general route refuses it: {why_g}")
-    if not ok_t:
-        print(f"{name}: torch: {why_t}")
-    ta, tg, tt = [], [], []
-    for _ in range(REPS):     # alternate the three
-        ta.append(device_ms(ours))
-        if ok_g:
-            tg.append(device_ms(general))
-        if ok_t:
-            tt.append(device_ms(torch_fn))
-    ma, mg, mt = med(ta), med(tg), med(tt)
-    tot["ours_all"] += ma
-    if ok_g:                  # a refused launch is left out of both sums
-        tot["ours"] += ma
-        tot["general"] += mg
-        tot["torch"] += mt if ok_t else 0.0
-        tot["gflop"] += gflop
-        ratios[name] = round(ma / mg, 4)
-    rows_out.append({"launch": name, "new_kernel": i in NEW, "gflop": round(gflop, 4), "ours_ms": r4(ma), "ours_ms_min": r4(min(ta)),
-                     "ours_ms_max": r4(max(ta)), "general_ms": r4(mg), "general_ms_min": r4(min(tg)) if tg else None,
-                     "general_ms_max": r4(max(tg)) if tg else None, "ours_over_general": ratios.get(name),
-                     "torch_ms": r4(mt)})
-    gs = f"{min(tg):7.3f}-{max(tg):7.3f}" if tg else f"{'':15s}"
-    print(f"{name:58s} {gflop:7.3f} {ma:8.3f} {min(ta):7.3f}-{max(ta):7.3f} {mg:10.3f} {gs} {ma / mg if ok_g else float('nan'):8.3f} "
-          f"{mt:9.3f}", flush=True)
-
-print(f"{'conv launches the general route takes (median each, summed)':58s} {tot['gflop']:7.3f} {tot['ours']:8.3f} {'':15s} "
-      f"{tot['general']:10.3f} {'':15s} {tot['ours'] / tot['general'] if tot['general'] else float('nan'):8.3f} {tot['torch']:9.3f}")
+print(NT.spread_total_line("conv launches the general route takes (median each, summed)", 58, tot))
 print(json.dumps({"tool": "time_nb07", "batch": B, "image": S, "reps": REPS, "calls_per_sample": INNER,
                   "eager_ms": round(eager * 1e3, 4), "graph_ms": round(replay * 1e3, 4),
                   "samples_per_s_graph": round(B / replay, 2), "compared_gflop": round(tot["gflop"], 3),
                   "launches_ours_ms": round(tot["ours"], 4), "launches_general_ms": round(tot["general"], 4),
-                  "launches_torch_ms": round(tot["torch"], 4), "all_launches_ours_ms": round(tot["ours_all"], 4),
+                  "launches_torch_ms": round(tot["torch"], 4), "all_launches_ours_ms": round(ours_all, 4),
                   "refused_by_general_route": refused, "time_over_general_route": ratios, "launches": rows_out}))

@@ -9,58 +9,28 @@ Passes the general route refuses (128-channel weights beyond its LDS tile) are l
 table and one JSON line; exits non-zero when the compared launches sum to more than the general route's (the
 requirement is a ratio <= 1.0).
    python tools/time_nb10.py [batch=64] [reps=10]"""
-import json, os, sys, time
+import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
+import nb_timing as NT
 from predict_pv_yield_amd import hip_ops as K
 from predict_pv_yield_amd.conv2d_functional import STRIPE_WIDTH, stripe_start_from_horizon
-from predict_pv_yield_amd.graphs import GraphedTrainStep
 from predict_pv_yield_amd.models.conv2d.nb10_just_conv import LitAutoEncoder, output_side
-from predict_pv_yield_amd.optim import HipAdam
 
 dev = torch.device("cuda:0")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 S = 128
 T = output_side(S)
-PEAK_TFLOPS = 157.3      # f32 matrix peak of the MI355X at its 2.4 GHz engine clock
 
 g = torch.Generator().manual_seed(1)
 batch = {"HISTORICAL_SAT_IMAGES": torch.randn(B, 4, S, S, generator=g).to(dev),
          "FORECAST_HORIZON": torch.randint(1, 24, (B,), generator=g).to(dev),
          "TARGET_SAT_IMAGE": torch.randn(B, T, T, generator=g).to(dev)}
 
-# ---- the train step ------------------------------------------------------------------------------------------------
-torch.manual_seed(0)
-model = LitAutoEncoder().to(dev)
-opt = model.configure_optimizers()
-
-
-def step():
-    opt.zero_grad(set_to_none=True)
-    model.training_step(batch, 0).backward()
-    opt.step()
-
-
-def wall(fn):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(REPS):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / REPS
-
-
-eager = wall(step)
-torch.manual_seed(0)
-gmodel = LitAutoEncoder().to(dev)
-gopt = HipAdam(gmodel.parameters(), lr=0.001, capturable=True)
-graphed = GraphedTrainStep(gmodel, gopt, batch, warmup=3)
-replay = wall(lambda: graphed(batch))
-graphed.close()
+# ---- the train step, eager and replayed (tools/nb_timing.py) ----------------------------------------------------------
+model, eager, replay = NT.graph_and_eager(LitAutoEncoder, batch, 0.001, REPS, warmup=3)
 
 # ---- every conv launch of the step -------------------------------------------------------------------------------------
 hist = batch["HISTORICAL_SAT_IMAGES"]
@@ -115,68 +85,25 @@ cases += conv_rows("conv.6 128->1 s2 p2 (head)", y3, w4, b4, dy4, 2, 2, False,
 
 
 INNER = 4      # back-to-back calls per event pair
-
-
-def device_ms(fn):
-    e0, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(INNER):
-        fn()
-    e1_.record()
-    e1_.synchronize()
-    return e0.elapsed_time(e1_) / INNER
-
-
-def usable(fn, what):
-    try:
-        fn()
-        torch.cuda.synchronize()
-        return True
-    except Exception as e:            # a route that does not take a shape is reported, not timed
-        print(f"{what}: {type(e).__name__}: {str(e)[:200]}")
-        return False
-
-
-rows_out = []
-tot = {"ours": 0.0, "general": 0.0, "torch": 0.0, "gflop": 0.0}
-print(f"nb10 LitAutoEncoder B={B} {S}x{S}: eager {eager * 1e3:.3f} ms/step ({B / eager:.0f} samples/s), HIP graph "
-      f"{replay * 1e3:.3f} ms/step ({B / replay:.0f} samples/s)", flush=True)
-print(f"{'launch':50s} {'GFLOP':>7s} {'ours ms':>8s} {'of peak':>7s} {'general ms':>10s} {'torch ms':>9s}")
-unexpressed = []      # passes the general route refuses: left out of both sums of the ratio, and named
-tot_cmp = 0.0
-for name, gflop, ours, general, torch_fn in cases:
-    for _ in range(3):
-        ours()
-    ok_g, ok_t = usable(general, f"{name}: general Conv3d route"), usable(torch_fn, f"{name}: torch")
-    ta, tg, tt = [], [], []
-    for _ in range(REPS):     # alternate the three
-        ta.append(device_ms(ours))
-        if ok_g:
-            tg.append(device_ms(general))
-        if ok_t:
-            tt.append(device_ms(torch_fn))
-    med = lambda v: sorted(v)[len(v) // 2] if v else float("nan")      # noqa: E731
-    ma, mg, mt = med(ta), med(tg), med(tt)
-    if ok_g:
-        tot_cmp += ma
+rows_out, tot = [], NT.totals()
+unexpressed, tot_cmp = [], 0.0      # passes the general route refuses: left out of both sums of the ratio, and named
+print(NT.step_line("nb10", B, S, eager, replay, digits=0), flush=True)
+print(NT.peak_header(50))
+for r in NT.time_cases(cases, REPS, INNER, warmup=3, general_name="general Conv3d route"):
+    NT.add(tot, r)
+    if r.general:
+        tot_cmp += r.ours.med
     else:
-        unexpressed.append(name)
-    tot["ours"] += ma
-    tot["general"] += mg if ok_g else 0.0
-    tot["torch"] += mt if ok_t else 0.0
-    tot["gflop"] += gflop
-    rows_out.append({"launch": name, "gflop": round(gflop, 3), "ours_ms": round(ma, 4),
-                     "of_peak": round(gflop / ma / PEAK_TFLOPS, 4),
-                     "general_ms": round(mg, 4) if ok_g else None, "torch_ms": round(mt, 4) if ok_t else None})
-    print(f"{name:50s} {gflop:7.2f} {ma:8.3f} {gflop / ma / PEAK_TFLOPS:7.3f} {mg:10.3f} {mt:9.3f}", flush=True)
+        unexpressed.append(r.name)
+    rows_out.append(NT.peak_record(r))
+    print(NT.peak_line(r, 50), flush=True)
 ratio = tot_cmp / tot["general"] if tot["general"] > 0 else None
 print(f"the step's launches the general Conv3d f32 route can express: {tot_cmp:.3f} ms against its {tot['general']:.3f} ms, "
       f"ratio {ratio} (required <= 1.0); it refuses: {unexpressed}")
-print(f"{'conv launches of a step (median each, summed)':50s} {tot['gflop']:7.2f} {tot['ours']:8.3f} "
-      f"{tot['gflop'] / tot['ours'] / PEAK_TFLOPS:7.3f} {tot['general']:10.3f} {tot['torch']:9.3f}")
+print(NT.peak_total_line(50, tot))
 print(json.dumps({"tool": "time_nb10", "batch": B, "image": S, "reps": REPS, "eager_ms": round(eager * 1e3, 4),
                   "graph_ms": round(replay * 1e3, 4), "samples_per_s_graph": round(B / replay, 1),
-                  "step_gflop": round(tot["gflop"], 2), "step_of_peak_graph": round(tot["gflop"] / replay / 1e3 / PEAK_TFLOPS, 4),
+                  "step_gflop": round(tot["gflop"], 2), "step_of_peak_graph": round(tot["gflop"] / replay / 1e3 / NT.PEAK_TFLOPS, 4),
                   "launches_ours_ms": round(tot["ours"], 4), "launches_ours_compared_ms": round(tot_cmp, 4),
                   "general_route_refuses": unexpressed, "launches_general_ms": round(tot["general"], 4),
                   "launches_torch_ms": round(tot["torch"], 4), "ours_over_general": round(ratio, 4) if ratio else None,

@@ -12,21 +12,19 @@ Warm-up first, device-side event timing of INNER back-to-back calls per sample, 
 torch, ours, ...), inputs resident before the timed region; the samples' min and max are kept as the spread.  Prints a table
 and one JSON line.
    python tools/time_nb12.py [batch=64] [reps=7]"""
-import json, os, sys, time
+import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
+import nb_timing as NT
 from predict_pv_yield_amd import hip_ops as K
-from predict_pv_yield_amd.graphs import GraphedTrainStep
 from predict_pv_yield_amd.models.conv3d.nb12_just_3d_conv import LitAutoEncoder, output_side
-from predict_pv_yield_amd.optim import HipAdam
 
 dev = torch.device("cuda:0")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 7
 S = 128
 T = output_side(S)
-PEAK_TFLOPS = 157.3      # f32 matrix peak of the MI355X at its 2.4 GHz engine clock
 INNER = 2                # back-to-back calls per event pair
 
 g = torch.Generator().manual_seed(1)
@@ -34,39 +32,9 @@ batch = {"HISTORICAL_SAT_IMAGES": torch.randn(B, 4, S, S, generator=g).to(dev),
          "FORECAST_HORIZON": ((torch.randint(1, 25, (B,), generator=g).float() - 12.5) / 6.9222).to(dev),
          "TARGET_SAT_IMAGE": torch.randn(B, T, T, generator=g).to(dev)}
 
-# ---- the train step ------------------------------------------------------------------------------------------------
-torch.manual_seed(0)
-model = LitAutoEncoder().to(dev)
-opt = model.configure_optimizers()
-
-
-def step():
-    opt.zero_grad(set_to_none=True)
-    model.training_step(batch, 0).backward()
-    opt.step()
-
-
-def wall(fn):
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(REPS):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / REPS
-
-
-eager = wall(step)
-torch.manual_seed(0)
-gmodel = LitAutoEncoder().to(dev)
-gopt = HipAdam(gmodel.parameters(), lr=0.0001, capturable=True)
-graphed = GraphedTrainStep(gmodel, gopt, batch, warmup=2)
-replay = wall(lambda: graphed(batch))
-graphed.close()
-del gmodel, gopt, graphed
-print(f"nb12 LitAutoEncoder B={B} {S}x{S}: eager {eager * 1e3:.3f} ms/step ({B / eager:.1f} samples/s), HIP graph "
-      f"{replay * 1e3:.3f} ms/step ({B / replay:.1f} samples/s)", flush=True)
+# ---- the train step, eager and replayed (tools/nb_timing.py) ----------------------------------------------------------
+model, eager, replay = NT.graph_and_eager(LitAutoEncoder, batch, 0.0001, REPS, warmup=2)
+print(NT.step_line("nb12", B, S, eager, replay), flush=True)
 
 # ---- every conv launch of the step -------------------------------------------------------------------------------------
 hist, horizon = batch["HISTORICAL_SAT_IMAGES"], batch["FORECAST_HORIZON"]
@@ -133,53 +101,25 @@ yard = [("conv2d_wide 128->128 p2 fwd", gf_y, gf_y, lambda: K.conv2d_wide_fwd_f3
          lambda: K.conv2d_wide_bwd_weight_f32(xs, dys, None, tuple(ws.shape), padding=2), None)]
 
 
-def device_ms(fn):
-    e0, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(INNER):
-        fn()
-    e1_.record()
-    e1_.synchronize()
-    return e0.elapsed_time(e1_) / INNER
-
-
-def usable(fn, what):
-    if fn is None:
-        return False
-    try:
-        fn()
-        torch.cuda.synchronize()
-        return True
-    except Exception as e:            # a route that does not take a shape is reported, not timed
-        print(f"{what}: {type(e).__name__}: {str(e)[:200]}")
-        return False
-
-
-med = lambda v: sorted(v)[len(v) // 2] if v else float("nan")      # noqa: E731
 rows_out, rate = [], {}
 tot = {"ours": 0.0, "torch": 0.0, "gflop": 0.0, "run": 0.0}
+run_of = {name: run for name, _, run, _, _ in cases + yard}
+in_step = {name for name, *_ in cases}
 print(f"{'launch':50s} {'GFLOP':>8s} {'run':>8s} {'ours ms':>8s} {'spread':>15s} {'of peak':>7s} {'torch ms':>9s}")
-for name, gflop, run, ours, torch_fn in cases + yard:
-    for _ in range(2):
-        ours()
-    ok_t = usable(torch_fn, f"{name}: torch")
-    ta, tt = [], []
-    for _ in range(REPS):     # alternate the two
-        ta.append(device_ms(ours))
-        if ok_t:
-            tt.append(device_ms(torch_fn))
-    ma, mt = med(ta), med(tt)
-    rate[name] = run / ma      # GFLOP / ms = TFLOP/s
-    if (name, gflop, run, ours, torch_fn) in cases:
-        tot["ours"] += ma
-        tot["torch"] += mt if ok_t else 0.0
-        tot["gflop"] += gflop
+# two routes here, ours and torch in turn: there is no general route for these layers
+for r in NT.time_cases([(name, gflop, ours, None, torch_fn) for name, gflop, _, ours, torch_fn in cases + yard], REPS, INNER, warmup=2):
+    run = run_of[r.name]
+    rate[r.name] = run / r.ours.med      # GFLOP / ms = TFLOP/s
+    if r.name in in_step:
+        tot["ours"] += r.ours.med
+        tot["torch"] += r.torch.med if r.torch else 0.0
+        tot["gflop"] += r.gflop
         tot["run"] += run
-    rows_out.append({"launch": name, "gflop": round(gflop, 3), "gflop_run": round(run, 3), "ours_ms": round(ma, 4),
-                     "ours_ms_min": round(min(ta), 4), "ours_ms_max": round(max(ta), 4),
-                     "of_peak": round(run / ma / PEAK_TFLOPS, 4), "torch_ms": round(mt, 4) if ok_t else None})
-    print(f"{name:50s} {gflop:8.2f} {run:8.2f} {ma:8.3f} {min(ta):7.3f}-{max(ta):7.3f} {run / ma / PEAK_TFLOPS:7.3f} {mt:9.3f}",
-          flush=True)
+    rows_out.append({"launch": r.name, "gflop": round(r.gflop, 3), "gflop_run": round(run, 3), "ours_ms": round(r.ours.med, 4),
+                     "ours_ms_min": round(r.ours.lo, 4), "ours_ms_max": round(r.ours.hi, 4),
+                     "of_peak": round(run / r.ours.med / NT.PEAK_TFLOPS, 4), "torch_ms": NT.r4(r.torch.med)})
+    print(f"{r.name:50s} {r.gflop:8.2f} {run:8.2f} {r.ours.med:8.3f} {NT.spread(r.ours)} {run / r.ours.med / NT.PEAK_TFLOPS:7.3f} "
+          f"{r.torch.med:9.3f}", flush=True)
 
 ratios = {}
 for layer in ("conv.4 128->128 pd1", "conv.6 128->128 pd0"):
@@ -187,11 +127,11 @@ for layer in ("conv.4 128->128 pd1", "conv.6 128->128 pd0"):
         ratios[f"{layer} {p}"] = round(rate[f"{layer} {p}"] / rate[f"conv2d_wide 128->128 p2 {p}"], 4)
 print("FLOP rate of each new 128 -> 128 pass over the same pass of conv2d_wide 128 -> 128 p2:", ratios)
 print(f"{'conv launches of a step (median each, summed)':50s} {tot['gflop']:8.2f} {tot['run']:8.2f} {tot['ours']:8.3f} "
-      f"{'':15s} {tot['run'] / tot['ours'] / PEAK_TFLOPS:7.3f} {tot['torch']:9.3f}")
+      f"{'':15s} {tot['run'] / tot['ours'] / NT.PEAK_TFLOPS:7.3f} {tot['torch']:9.3f}")
 print(json.dumps({"tool": "time_nb12", "batch": B, "image": S, "reps": REPS, "calls_per_sample": INNER,
                   "eager_ms": round(eager * 1e3, 4), "graph_ms": round(replay * 1e3, 4),
                   "samples_per_s_graph": round(B / replay, 2), "step_gflop": round(tot["gflop"], 2),
                   "step_gflop_run": round(tot["run"], 2),
-                  "step_of_peak_graph": round(tot["run"] / replay / 1e3 / PEAK_TFLOPS, 4),
+                  "step_of_peak_graph": round(tot["run"] / replay / 1e3 / NT.PEAK_TFLOPS, 4),
                   "launches_ours_ms": round(tot["ours"], 4), "launches_torch_ms": round(tot["torch"], 4),
                   "rate_over_conv2d_wide_128_p2": ratios, "launches": rows_out}))

@@ -8,20 +8,18 @@ own F.conv2d / F.conv_transpose2d (comparison only: the package never calls them
 timing of INNER back-to-back calls per sample, the median of REPS alternating samples, inputs resident before the timed region.  Prints a table and one JSON
 line; exits non-zero when the step's launches sum to more than the general route's (the requirement is a ratio <= 1.0).
    python tools/time_nb16.py [batch=64] [reps=20]"""
-import json, os, sys, time
+import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.nn.functional as F
+import nb_timing as NT
 from predict_pv_yield_amd import hip_ops as K
-from predict_pv_yield_amd.graphs import GraphedTrainStep
 from predict_pv_yield_amd.models.conv2d.nb16_maxpool import LitAutoEncoder
-from predict_pv_yield_amd.optim import HipAdam
 
 dev = torch.device("cuda:0")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 REPS = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 S, T = 128, 64
-PEAK_TFLOPS = 157.3      # f32 matrix peak of the MI355X at its 2.4 GHz engine clock
 
 g = torch.Generator().manual_seed(1)
 batch = {"HISTORICAL_SAT_IMAGES": torch.randint(0, 1024, (B, 4, S, S), generator=g).to(torch.int16).to(dev),
@@ -30,36 +28,8 @@ batch = {"HISTORICAL_SAT_IMAGES": torch.randint(0, 1024, (B, 4, S, S), generator
          "FORECAST_HORIZON": torch.randn(B, generator=g).to(dev),
          "TARGET_SAT_IMAGE": torch.randint(0, 1024, (B, T, T), generator=g).to(torch.int16).to(dev)}
 
-# ---- the train step ------------------------------------------------------------------------------------------------
-torch.manual_seed(0)
-model = LitAutoEncoder().to(dev)
-opt = model.configure_optimizers()
-
-
-def step():
-    opt.zero_grad(set_to_none=True)
-    model.training_step(batch, 0).backward()
-    opt.step()
-
-
-def wall(fn):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(REPS):
-        fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / REPS
-
-
-eager = wall(step)
-torch.manual_seed(0)
-gmodel = LitAutoEncoder().to(dev)
-gopt = HipAdam(gmodel.parameters(), lr=0.001, capturable=True)
-graphed = GraphedTrainStep(gmodel, gopt, batch, warmup=3)
-replay = wall(lambda: graphed(batch))
-graphed.close()
+# ---- the train step, eager and replayed (tools/nb_timing.py) ----------------------------------------------------------
+model, eager, replay = NT.graph_and_eager(LitAutoEncoder, batch, 0.001, REPS, warmup=3)
 
 # ---- every conv launch of the step -------------------------------------------------------------------------------------
 hist, flow, hor = batch["HISTORICAL_SAT_IMAGES"], batch["OPTICAL_FLOW_PREDICTIONS"], batch["FORECAST_HORIZON"]
@@ -149,73 +119,29 @@ cases += convt_rows("decoder_conv4 T 16->1", z3, u4, e4, c4, dz4, False)
 
 
 INNER = 8      # back-to-back calls per event pair: the small decoder launches are microseconds each
-
-
-def device_ms(fn):
-    e0, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(INNER):
-        fn()
-    e1_.record()
-    e1_.synchronize()
-    return e0.elapsed_time(e1_) / INNER
-
-
-def usable(fn, what):
-    try:
-        fn()
-        torch.cuda.synchronize()
-        return True
-    except Exception as e:            # a route that does not take a shape is reported, not timed
-        print(f"{what}: {type(e).__name__}: {str(e)[:200]}")
-        return False
-
-
-rows_out = []
-tot = {"ours": 0.0, "general": 0.0, "torch": 0.0, "gflop": 0.0, "new_ours": 0.0, "new_general": 0.0}
-print(f"nb16 LitAutoEncoder B={B} {S}x{S}: eager {eager * 1e3:.3f} ms/step ({B / eager:.0f} samples/s), HIP graph "
-      f"{replay * 1e3:.3f} ms/step ({B / replay:.0f} samples/s)", flush=True)
-print(f"{'launch':62s} {'GFLOP':>7s} {'ours ms':>8s} {'of peak':>7s} {'general ms':>10s} {'torch ms':>9s}")
-complete = True
-for name, gflop, ours, general, torch_fn in cases:
-    routed = name.endswith(R)      # the entry point itself runs the general kernel at this size
-    for _ in range(3):
-        ours()
-    ok_g, ok_t = usable(general, f"{name}: general Conv3d route"), usable(torch_fn, f"{name}: torch")
-    ta, tg, tt = [], [], []
-    for _ in range(REPS):     # alternate the three
-        ta.append(device_ms(ours))
-        if ok_g:
-            tg.append(device_ms(general))
-        if ok_t:
-            tt.append(device_ms(torch_fn))
-    med = lambda v: sorted(v)[len(v) // 2] if v else float("nan")      # noqa: E731
-    ma, mg, mt = med(ta), med(tg), med(tt)
-    complete = complete and ok_g
-    tot["ours"] += ma
-    tot["general"] += mg if ok_g else 0.0
-    tot["torch"] += mt if ok_t else 0.0
-    tot["gflop"] += gflop
+rows_out, tot, new = [], NT.totals(), NT.totals()      # new: the launches that run csrc/conv2d_ae_f32.hip's own kernels
+print(NT.step_line("nb16", B, S, eager, replay, digits=0), flush=True)
+print(NT.peak_header(62))
+for r in NT.time_cases(cases, REPS, INNER, warmup=3, general_name="general Conv3d route"):
+    routed = r.name.endswith(R)      # the entry point itself runs the general kernel at this size
+    NT.add(tot, r)
     if not routed:
-        tot["new_ours"] += ma
-        tot["new_general"] += mg if ok_g else 0.0
-    rows_out.append({"launch": name, "routed_to_general": routed, "gflop": round(gflop, 3), "ours_ms": round(ma, 4),
-                     "of_peak": round(gflop / ma / PEAK_TFLOPS, 4),
-                     "general_ms": round(mg, 4) if ok_g else None, "torch_ms": round(mt, 4) if ok_t else None})
-    print(f"{name:62s} {gflop:7.2f} {ma:8.3f} {gflop / ma / PEAK_TFLOPS:7.3f} {mg:10.3f} {mt:9.3f}", flush=True)
+        NT.add(new, r)
+    rows_out.append(NT.peak_record(r, routed_to_general=routed))
+    print(NT.peak_line(r, 62), flush=True)
+complete = all(row["general_ms"] is not None for row in rows_out)
 ratio = tot["ours"] / tot["general"] if complete and tot["general"] > 0 else None
-ratio_new = tot["new_ours"] / tot["new_general"] if complete and tot["new_general"] > 0 else None
+ratio_new = new["ours"] / new["general"] if complete and new["general"] > 0 else None
 print(f"sum of the step's launches / the same layers on the general Conv3d f32 route: {ratio} (required <= 1.0); launches "
-      f"that run csrc/conv2d_ae_f32.hip's own kernels only: {tot['new_ours']:.3f} ms against {tot['new_general']:.3f} ms = "
+      f"that run csrc/conv2d_ae_f32.hip's own kernels only: {new['ours']:.3f} ms against {new['general']:.3f} ms = "
       f"{ratio_new}; rows marked [general route] are the general kernel's own time and fraction of peak")
-print(f"{'conv launches of a step (median each, summed)':62s} {tot['gflop']:7.2f} {tot['ours']:8.3f} "
-      f"{tot['gflop'] / tot['ours'] / PEAK_TFLOPS:7.3f} {tot['general']:10.3f} {tot['torch']:9.3f}")
+print(NT.peak_total_line(62, tot))
 print(json.dumps({"tool": "time_nb16", "batch": B, "image": S, "reps": REPS, "eager_ms": round(eager * 1e3, 4),
                   "graph_ms": round(replay * 1e3, 4), "samples_per_s_graph": round(B / replay, 1),
-                  "step_gflop": round(tot["gflop"], 2), "step_of_peak_graph": round(tot["gflop"] / replay / 1e3 / PEAK_TFLOPS, 4),
+                  "step_gflop": round(tot["gflop"], 2), "step_of_peak_graph": round(tot["gflop"] / replay / 1e3 / NT.PEAK_TFLOPS, 4),
                   "launches_ours_ms": round(tot["ours"], 4), "launches_general_ms": round(tot["general"], 4),
                   "launches_torch_ms": round(tot["torch"], 4), "ours_over_general": round(ratio, 4) if ratio else None,
-                  "new_kernels_ours_ms": round(tot["new_ours"], 4), "new_kernels_general_ms": round(tot["new_general"], 4),
+                  "new_kernels_ours_ms": round(new["ours"], 4), "new_kernels_general_ms": round(new["general"], 4),
                   "new_kernels_over_general": round(ratio_new, 4) if ratio_new else None, "calls_per_sample": INNER,
                   "launches": rows_out}))
 if ratio is None or ratio > 1.0:
