@@ -5,6 +5,7 @@ csrc/conv2d_pool_f32.hip.
 Tolerances (as tests/test_gpu_exp002.py).  The kernels multiply in exact f32 with f32 accumulation in another summation
 order than torch: each output element is held to 1e-6 of its own sum of |products| (computed alongside in float64), each
 weight / bias gradient to 1e-5 relative norm against float64.
+The plain 144 -> 144 layer's three passes are the record `conv2d144` of tests/conv_family_checks.py, checked by its check_family.
 Pool routing.  Where two entries of a window lie closer than that rounding, f32 may pick either as the maximum, and the
 gradient follows the pick.  So the codes are checked on their own -- the picked entry is within the tolerance of the float64
 maximum, dead windows have a maximum within the tolerance of <= 0 -- and the float64 gradients are then routed through the
@@ -20,6 +21,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_family_checks as C
 from conv2d_f32_helpers import ELEM_TOL, NORM_TOL, ROOT, _golden_module, _ops, _rel, _to, _within
 
 pytestmark = pytest.mark.gpu
@@ -126,40 +128,6 @@ def test_pooled_layer_against_float64(device, n, h, w):
     assert _rel(dw, wr.grad) <= NORM_TOL and _rel(db, br.grad) <= NORM_TOL, (_rel(dw, wr.grad), _rel(db, br.grad))
 
 
-PLAIN_SHAPES = [(2, 13, 13), (1, 3, 3), (3, 7, 11), (1, 45, 50)]
-
-
-@pytest.mark.parametrize("n,h,w", PLAIN_SHAPES)
-def test_plain_layer_against_float64(device, n, h, w):
-    K = _ops()
-    g = torch.Generator().manual_seed(n * 1000 + h * 10 + w + 7)
-    x = torch.randn(n, 144, h, w, generator=g).relu()
-    wt = torch.randn(144, 144, 3, 3, generator=g) / 36.0
-    b = torch.randn(144, generator=g) * 0.1
-    x64, w64, b64 = x.double(), wt.double(), b.double()
-    xd, wd, bd = x.to(device), wt.to(device), b.to(device)
-    pre64 = F.conv2d(x64, w64, b64)
-    abs64 = F.conv2d(x64.abs(), w64.abs(), b64.abs())
-    _within(K.conv2d144_fwd_f32(xd, wd, bd, relu=False), pre64, abs64, what="forward")
-    yr = K.conv2d144_fwd_f32(xd, wd, bd, relu=True)
-    _within(yr, pre64.relu(), abs64, what="forward+relu")
-    _within(K.conv2d144_fwd_f32(xd, wd, None, relu=False), F.conv2d(x64, w64), abs64, what="forward, no bias")
-
-    dy = torch.randn(n, 144, h - 2, w - 2, generator=g)
-    gate = (yr.cpu() > 0).double()
-    dz = dy.double() * gate
-    dx64 = torch.nn.grad.conv2d_input(x.shape, w64, dz) * (x64 > 0)
-    dx_abs = torch.nn.grad.conv2d_input(x.shape, w64.abs(), dz.abs())
-    dx = K.conv2d144_bwd_data_f32(dy.to(device), yr, wd, xd, tuple(x.shape))
-    _within(dx, dx64, dx_abs, what="dgrad (gated)")
-    dx = K.conv2d144_bwd_data_f32(dy.to(device), None, wd, None, tuple(x.shape))
-    _within(dx, torch.nn.grad.conv2d_input(x.shape, w64, dy.double()),
-            torch.nn.grad.conv2d_input(x.shape, w64.abs(), dy.double().abs()), what="dgrad (ungated)")
-    dw, db = K.conv2d144_bwd_weight_f32(xd, dy.to(device), yr, tuple(wt.shape))
-    assert _rel(dw, torch.nn.grad.conv2d_weight(x64, wt.shape, dz)) <= NORM_TOL
-    assert _rel(db, dz.sum((0, 2, 3))) <= NORM_TOL
-
-
 @pytest.mark.parametrize("b,t,s,n_frames", [(2, 19, 128, 7), (1, 3, 17, 3), (3, 9, 10, 7), (1, 8, 5, 1)])
 def test_first_layer_against_the_reference_stacking(device, b, t, s, n_frames):
     K = _ops()
@@ -212,6 +180,12 @@ def test_ties_go_to_the_first_window_position_and_dead_windows_pass_nothing(devi
     dx = K.conv2d144_pool_bwd_data_f32(dyp.to(device), codes.to(device), wt2.to(device), None, (n, 144, h, w))
     _within(dx, torch.nn.grad.conv2d_input((n, 144, h, w), wt2.double(), dz.double()),
             torch.nn.grad.conv2d_input((n, 144, h, w), wt2.double().abs(), dz.double().abs()), what="tie dgrad")
+
+
+# ---- the plain families' three passes: the records and the checker of tests/conv_family_checks.py ------------------------
+@C.cases_of("conv2d144", ids="{shape}")
+def test_plain_layer_against_float64(device, fam, c_in, c_out, shape):
+    C.check_family(_ops(), device, fam, c_in, c_out, shape)
 
 
 # ---- the whole model ----------------------------------------------------------------------------------------------------

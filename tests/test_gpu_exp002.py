@@ -5,6 +5,7 @@ Tolerances.  The kernels multiply in exact f32 (one rounding per product, f32 ac
 from torch: an output element's error is then a few ulp of its sum of |products| (about 1e-7 of it per rounding at these
 depths, K <= 288), so each element is held to 1e-6 of its own sum of |products|, computed alongside in float64.  The weight
 gradients add up to 600 000 products per element: held to 1e-5 relative norm against float64.
+The 32 -> 32 and 32 -> 4 layers' three passes are the record `conv2d` of tests/conv_family_checks.py, checked by its check_family.
 """
 import os
 import subprocess
@@ -15,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_family_checks as C
 from conv2d_f32_helpers import NORM_TOL, ROOT, _golden_module, _ops, _rel, _to, _within
 
 pytestmark = pytest.mark.gpu
@@ -22,46 +24,10 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(ROOT, "tests", "golden", "exp002_small.npz")
 
 
-# ---- entry points against float64 torch.nn.functional.conv2d ------------------------------------------------------------
-SHAPES = [(32, 30, 30), (32, 28, 28), (1, 3, 3), (3, 7, 11), (1, 13, 13), (3, 13, 13)]
-
-
-@pytest.mark.parametrize("n,h,w", SHAPES)
-@pytest.mark.parametrize("c_out", [32, 4])
-def test_conv2d_entry_points_against_float64(device, n, h, w, c_out):
-    K = _ops()
-    g = torch.Generator().manual_seed(n * 1000 + h * 10 + w + c_out)
-    x = torch.randn(n, 32, h, w, generator=g).relu()               # a ReLU output, as in the model
-    wt = torch.randn(c_out, 32, 3, 3, generator=g) / 17.0
-    b = torch.randn(c_out, generator=g) * 0.1
-    x64, w64, b64 = x.double(), wt.double(), b.double()
-    xd, wd, bd = x.to(device), wt.to(device), b.to(device)
-
-    # forward, plain and with the fused ReLU
-    pre64 = F.conv2d(x64, w64, b64)
-    abs64 = F.conv2d(x64.abs(), w64.abs(), b64.abs())
-    y = K.conv2d_fwd_f32(xd, wd, bd, relu=False)
-    _within(y, pre64, abs64, what="forward")
-    yr = K.conv2d_fwd_f32(xd, wd, bd, relu=True)
-    _within(yr, pre64.relu(), abs64, what="forward+relu")
-
-    # data gradient: dy gated by the layer's ReLU output, dx gated by the (ReLU) input
-    dy = torch.randn(n, c_out, h - 2, w - 2, generator=g)
-    gate = torch.randn(n, c_out, h - 2, w - 2, generator=g).relu()
-    dyg = torch.where(gate > 0, dy, torch.zeros_like(dy)).double()
-    dx64 = torch.nn.grad.conv2d_input(x.shape, w64, dyg)
-    dxabs = torch.nn.grad.conv2d_input(x.shape, w64.abs(), dyg.abs())
-    dx64 = torch.where(x64 > 0, dx64, torch.zeros_like(dx64))
-    dx = K.conv2d_bwd_data_f32(dy.to(device), gate.to(device), wd, xd, tuple(x.shape))
-    _within(dx, dx64, dxabs, what="dgrad")
-    dx_plain = K.conv2d_bwd_data_f32(dyg.float().to(device), None, wd, None, tuple(x.shape))
-    _within(dx_plain, torch.nn.grad.conv2d_input(x.shape, w64, dyg), dxabs, what="dgrad ungated")
-
-    # weight and bias gradients
-    dw64 = torch.nn.grad.conv2d_weight(x64, wt.shape, dyg)
-    db64 = dyg.sum(dim=(0, 2, 3))
-    dw, db = K.conv2d_bwd_weight_f32(xd, dy.to(device), gate.to(device), tuple(wt.shape))
-    assert _rel(dw, dw64) <= NORM_TOL and _rel(db, db64) <= NORM_TOL, (_rel(dw, dw64), _rel(db, db64))
+# ---- the plain families' three passes: the records and the checker of tests/conv_family_checks.py ------------------------
+@C.cases_of("conv2d", ids="{c_out}-{shape}")
+def test_conv2d_entry_points_against_float64(device, fam, c_in, c_out, shape):
+    C.check_family(_ops(), device, fam, c_in, c_out, shape)
 
 
 # ---- layer 1: the 17-channel input built by the kernels -----------------------------------------------------------------

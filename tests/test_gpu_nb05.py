@@ -3,9 +3,11 @@
 the CPU.
 
 Tolerances are the project's own for exact-f32 conv kernels (conv2d_f32_helpers): ELEM_TOL per element relative to the
-element's float64 sum of |products|, NORM_TOL relative norm for reductions.  The references are float64 F.conv2d,
-torch.nn.grad.conv2d_weight, F.conv_transpose2d and, for the ConvTranspose2d's gradients, float64 autograd of the 33-channel
-F.conv_transpose2d.
+element's float64 sum of |products|, NORM_TOL relative norm for reductions.  The references are float64 F.conv2d and
+torch.nn.grad.conv2d_weight.
+
+The horizon ConvTranspose2d's shapes and its check (float64 autograd of the 33-channel F.conv_transpose2d) are
+tests/conv_family_checks.py's, shared with its stride-2 twin of notebook 08.
 
 The model-level checks (golden fixture, full size, determinism, HIP-graph replay, Trainer.fit) are notebook_model_checks.py's,
 run by tests/test_gpu_notebook_models.py.
@@ -17,6 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_family_checks as C
 from conv2d_f32_helpers import NORM_TOL, ROOT, _ops, _rel, _within
 from notebook_model_checks import _g, _randn
 
@@ -24,11 +27,13 @@ pytestmark = pytest.mark.gpu
 
 # (batch, height, width) of the first layer's inputs: one output; odd sides; two column bands; full width; the model's size
 INPUTS_SHAPES = [(1, 3, 3), (2, 4, 7), (3, 9, 70), (1, 5, 128), (2, 64, 64)]
-# (batch, height, width) of the horizon ConvTranspose2d's input; (2, 5, 63) -> 65 wide takes two column bands, (2, 3, 126) is
-# 128 wide, (1, 58, 58) is the model's own
-HORIZON_SHAPES = [(1, 1, 1), (2, 2, 5), (3, 7, 7), (2, 5, 63), (2, 3, 126), (1, 58, 58)]
-GATES = ((True, True), (False, False))      # (dy_gate, x_gate): every gradient with and without its gates
 PLANE_SCALES = (1.0, 0.25, 3.0, 7.0)        # flow prediction, t0 image, flow x, flow y: a swapped channel shows
+
+
+# ---- the plain families' three passes: the records and the checker of tests/conv_family_checks.py ------------------------
+@C.twin_shapes("convt2d_ae_horizon")
+def test_horizon_conv_transpose_against_float64(device, twin, shape):
+    C.check_horizon_conv_transpose(_ops(), device, twin, shape)
 
 
 # ---- 1. Conv2d 4 -> 32 over three tensors read in place ------------------------------------------------------------------
@@ -67,50 +72,7 @@ def test_inputs_conv_against_float64(device, n, h, w):
         assert torch.equal(dw, dw2) and torch.equal(db, db2), "slab partials summed in slab order: identical bits"
 
 
-# ---- 2. ConvTranspose2d 33 -> 32 at stride 1 with the horizon as its last input channel -----------------------------------
-@pytest.mark.parametrize("n, h, w", HORIZON_SHAPES)
-def test_horizon_conv_transpose_against_float64(device, n, h, w):
-    K = _ops()
-    g = _g(1500 + w + h)
-    x = _randn(g, n, 32, h, w)
-    horizon = torch.tensor([0.0, -1.3, 0.7][:n]) if n > 1 else torch.tensor([-0.4])      # zero and both signs
-    wt = _randn(g, 33, 32, 3, 3, scale=(9 * 33) ** -0.5)
-    b = _randn(g, 32, scale=0.1)
-    xd, hd, wd, bd = x.to(device), horizon.to(device), wt.to(device), b.to(device)
-    x33 = torch.cat((x.double(), horizon.double().view(n, 1, 1, 1).expand(n, 1, h, w)), dim=1).requires_grad_(True)
-    w64, b64 = wt.double().requires_grad_(True), b.double().requires_grad_(True)
-    pre = F.conv_transpose2d(x33, w64, b64)
-    absref = F.conv_transpose2d(x33.detach().abs(), w64.detach().abs(), b64.detach().abs())
-    for relu in (True, False):
-        y = K.convt2d_ae_horizon_fwd_f32(xd, hd, wd, bd, relu=relu)
-        assert tuple(y.shape) == (n, 32, h + 2, w + 2)
-        _within(y, pre.detach().relu() if relu else pre.detach(), absref, what=f"horizon convT forward relu={relu}")
-    _within(K.convt2d_ae_horizon_fwd_f32(xd, hd, wd, None, relu=False), pre.detach() - b64.detach().view(1, -1, 1, 1), absref,
-            what="horizon convT forward without bias")
-    dy, dy_gate, x_gate = _randn(g, *pre.shape), _randn(g, *pre.shape), _randn(g, *x.shape)
-    for use_dg, use_xg in GATES:
-        dyg = dy.double() * (dy_gate > 0) if use_dg else dy.double()
-        gate_d = dy_gate.to(device) if use_dg else None
-        for t in (x33, w64, b64):
-            t.grad = None
-        pre.backward(dyg, retain_graph=True)
-        dw, db = K.convt2d_ae_horizon_bwd_weight_f32(xd, hd, dy.to(device), gate_d, tuple(wt.shape))
-        assert tuple(dw.shape) == (33, 32, 3, 3) and tuple(db.shape) == (32,)
-        dw64 = w64.grad      # float64 autograd of conv_transpose2d (torch has no torch.nn.grad.conv_transpose2d_weight)
-        assert _rel(dw, dw64) <= NORM_TOL, (use_dg, _rel(dw, dw64))
-        assert _rel(dw[32], dw64[32]) <= NORM_TOL, (use_dg, "horizon row", _rel(dw[32], dw64[32]))
-        assert _rel(dw[:32], dw64[:32]) <= NORM_TOL, (use_dg, "real rows", _rel(dw[:32], dw64[:32]))
-        assert _rel(db, b64.grad) <= NORM_TOL, (use_dg, _rel(db, b64.grad))
-        dw2, db2 = K.convt2d_ae_horizon_bwd_weight_f32(xd, hd, dy.to(device), gate_d, tuple(wt.shape))
-        assert torch.equal(dw, dw2) and torch.equal(db, db2), "deterministic"
-        # the 32 real channels' data gradient: the existing entry point on the first 32 rows of the weight (contiguous)
-        dx = K.convt2d_ae_bwd_data_f32(dy.to(device), gate_d, wd[:32], x_gate.to(device) if use_xg else None, tuple(x.shape))
-        absdx = F.conv2d(dyg.abs(), w64.detach()[:32].abs())
-        dx64 = x33.grad[:, :32]
-        _within(dx, dx64 * (x_gate > 0) if use_xg else dx64, absdx, what=f"horizon convT dx gates {use_dg} {use_xg}")
-
-
-# ---- 3. the data path on a hand-made device super-batch ------------------------------------------------------------------
+# ---- 2. the data path on a hand-made device super-batch ------------------------------------------------------------------
 def _hand_made_super_batch(device, t=5, h=40, w=36, border=6):
     """Pixel values encode (frame, row, column); the predictions carry a NaN border of 6 pixels; the field's x plane is the
     code + 0.25, its y plane the code + 0.5."""
@@ -171,7 +133,7 @@ def test_data_path_crops_one_window_from_all_four_tensors(device):
         D.super_batch_to_example(sb, np.random.default_rng(1), 30, max_retries=4)
 
 
-# ---- 4. one epoch through run.py's surface ---------------------------------------------------------------------------------
+# ---- 3. one epoch through run.py's surface ---------------------------------------------------------------------------------
 def test_one_epoch_of_the_configured_run(device, tmp_path, monkeypatch):
     """`run.py model=nb05_more_inputs datamodule=nb05_fake callbacks=none trainer.max_epochs=1` on a small fake set."""
     from predict_pv_yield_amd import hydra_lite as H

@@ -1,11 +1,13 @@
-"""GPU: the weight-shared per-frame encoder's first layer and the 128 -> 32 ConvTranspose2d of
+"""GPU: the weight-shared per-frame encoder's first layer and the one-frame identity of the 128 -> 32 ConvTranspose2d of
 notebooks/07_multiple_historical_images.ipynb (csrc/conv2d_frames_f32.hip, conv2d_functional,
 models/conv2d/nb07_multi_hist.py) against float64 on the CPU.
 
 Tolerances are the project's own for exact-f32 conv kernels (conv2d_f32_helpers): ELEM_TOL per element relative to the
 element's float64 sum of |products|, NORM_TOL relative norm for reductions.  The references are float64 F.conv2d on the
-explicitly built [F B, 2, H, W] input, torch.nn.grad.conv2d_weight, F.conv_transpose2d and its float64 autograd (this torch
-has no torch.nn.grad function for the transposed form's weight gradient).
+explicitly built [F B, 2, H, W] input, torch.nn.grad.conv2d_weight and F.conv_transpose2d.
+
+The three passes of convt2d_s2_frames are checked below by the records
+and the one checker of tests/conv_family_checks.py.
 
 The model-level checks (golden fixture, full size, determinism, HIP-graph replay, Trainer.fit) are notebook_model_checks.py's,
 run by tests/test_gpu_notebook_models.py.
@@ -15,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 import nb07_reference as R
+import conv_family_checks as C
 from conv2d_f32_helpers import NORM_TOL, _ops, _rel, _to, _within
 from notebook_model_checks import CASES, _g, _randn
 from predict_pv_yield_amd.models.conv2d.nb07_multi_hist import LitAutoEncoder      # absent: the file fails at import
@@ -26,14 +29,17 @@ pytestmark = pytest.mark.gpu
 # rows of outputs as 16 + 15); full width, 7 x 63 outputs: one block in the forward, two row bands (the 384-position limit) in
 # the weight gradient
 FIRST_SHAPES = [(1, 3, 3), (2, 4, 4), (3, 7, 12), (2, 26, 26), (1, 63, 63), (2, 15, 128)]
-# (batch, height, width) of the 128 -> 32 ConvTranspose2d's input; (2, 5, 60) -> 11 x 121 takes two column bands
-FRAMES_SHAPES = [(1, 1, 1), (2, 2, 5), (3, 7, 7), (1, 15, 15), (2, 5, 60), (2, 40, 3)]
-GATES = ((True, True), (False, False))      # (dy_gate, x_gate): every gradient with and without its gates
 HORIZONS = [0.0, -1.3, 0.7]                 # per example distinct: zero and both signs
 
 
 def _out(s):
     return (s - 3) // 2 + 1
+
+
+# ---- the plain families' three passes: the records and the checker of tests/conv_family_checks.py ------------------------
+@C.cases_of("convt2d_s2_frames", ids="{shape}")
+def test_frames_conv_transpose_against_float64(device, fam, c_in, c_out, shape):
+    C.check_family(_ops(), device, fam, c_in, c_out, shape)
 
 
 # ---- 1. the first layer: every frame with the horizon as a second channel, folded into the batch -------------------------
@@ -88,43 +94,6 @@ def test_first_layer_with_all_horizons_zero(device):
 
 
 # ---- 2. ConvTranspose2d 128 -> 32 along the frame seam -------------------------------------------------------------------
-@pytest.mark.parametrize("n, h, w", FRAMES_SHAPES)
-def test_frames_conv_transpose_against_float64(device, n, h, w):
-    K = _ops()
-    g = _g(1100 + w + h)
-    x = _randn(g, n, 128, h, w)
-    wt, b = _randn(g, 128, 32, 3, 3, scale=(9 * 128) ** -0.5), _randn(g, 32, scale=0.1)
-    xd, wd, bd = x.to(device), wt.to(device), b.to(device)
-    x64, w64, b64 = x.double().requires_grad_(True), wt.double().requires_grad_(True), b.double().requires_grad_(True)
-    pre = F.conv_transpose2d(x64, w64, b64, stride=2)
-    absref = F.conv_transpose2d(x64.detach().abs(), w64.detach().abs(), b64.detach().abs(), stride=2)
-    for relu in (True, False):
-        y = K.convt2d_s2_frames_fwd_f32(xd, wd, bd, relu=relu)
-        assert tuple(y.shape) == (n, 32, 2 * h + 1, 2 * w + 1)
-        _within(y, pre.detach().relu() if relu else pre.detach(), absref, what=f"frames convT forward relu={relu}")
-    _within(K.convt2d_s2_frames_fwd_f32(xd, wd, None, relu=False), pre.detach() - b64.detach().view(1, -1, 1, 1), absref,
-            what="frames convT forward without bias")
-    dy, dy_gate, x_gate = _randn(g, *pre.shape), _randn(g, *pre.shape), _randn(g, *x.shape)
-    for use_dg, use_xg in GATES:
-        dyg = dy.double() * (dy_gate > 0) if use_dg else dy.double()
-        gate_d = dy_gate.to(device) if use_dg else None
-        for t in (x64, w64, b64):
-            t.grad = None
-        pre.backward(dyg, retain_graph=True)
-        dw, db = K.convt2d_s2_frames_bwd_weight_f32(xd, dy.to(device), gate_d, tuple(wt.shape))
-        assert tuple(dw.shape) == (128, 32, 3, 3) and tuple(db.shape) == (32,)
-        dx = K.convt2d_s2_frames_bwd_data_f32(dy.to(device), gate_d, wd, x_gate.to(device) if use_xg else None, tuple(x.shape))
-        assert tuple(dx.shape) == tuple(x.shape)
-        dx64 = x64.grad * (x_gate > 0) if use_xg else x64.grad
-        for f in range(4):      # per frame slice: a dropped, doubled or swapped frame shows
-            rows = slice(32 * f, 32 * f + 32)
-            err = _rel(dw[rows], w64.grad[rows])
-            assert err <= NORM_TOL, (use_dg, f, err)
-            absdx = F.conv2d(dyg.abs(), w64.detach()[rows].abs(), stride=2)
-            _within(dx[:, rows], dx64[:, rows], absdx, what=f"frames convT dx frame {f} gates {use_dg} {use_xg}")
-        assert _rel(db, b64.grad) <= NORM_TOL, (use_dg, _rel(db, b64.grad))
-
-
 @pytest.mark.parametrize("f", range(4))
 def test_frames_conv_transpose_of_one_frame_is_the_32_channel_layer(device, f):
     """x nonzero in frame f only: the forward is pv_convt2d_s2_fwd_f32 on that slice and weight slice (the other frames'

@@ -7,6 +7,9 @@ running sum's error relative to sum|p| does not grow with K, so the 2 304 produc
 bound; torch float32 on the CPU is itself 6.4e-8 (elements) and 6.2e-7 (weight gradient) from float64 at these shapes, which
 leaves the reference more than 15 x margin.
 
+The three passes of conv3d_wide at both depth paddings and of conv2d_head_s2p1 are checked below by the records
+and the one checker of tests/conv_family_checks.py.
+
 The model-level checks (golden fixture, full size, determinism, HIP-graph replay, Trainer.fit) are notebook_model_checks.py's,
 run by tests/test_gpu_notebook_models.py.
 """
@@ -16,71 +19,31 @@ import torch
 import torch.nn.functional as F
 
 import nb12_reference as R
+import conv_family_checks as C
 from conv2d_f32_helpers import NORM_TOL, _ops, _rel, _within
 from notebook_model_checks import _g, _randn
 
 pytestmark = pytest.mark.gpu
 
-# (batch, depth, height, width) of the layer's input.  Depth padding 0: one voxel (eight of nine taps padding); odd sides;
-# several row bands; full width (three column bands); an odd width over one band.  Depth padding 1: each output slice sees one
-# real and one skipped slice; small; wide
-WIDE_SHAPES = {0: [(1, 2, 1, 1), (2, 3, 5, 7), (2, 4, 9, 50), (1, 2, 6, 128), (2, 3, 7, 47)],
-               1: [(1, 1, 1, 1), (2, 2, 2, 5), (1, 2, 12, 124)]}
 HORIZON_SHAPES = [(1, 128, 128), (2, 9, 50), (3, 5, 7)]
-HEAD_SHAPES = [(1, 1, 1), (2, 4, 5), (3, 10, 47), (2, 9, 46), (1, 128, 128)]
-GATES = ((True, True), (False, False))      # (dy_gate, x_gate): every gradient with and without its gates
 
 
 def _conv_params(g, c_out, c_in, kernel=(2, 3, 3)):
     return _randn(g, c_out, c_in, *kernel, scale=(int(np.prod(kernel)) * c_in) ** -0.5), _randn(g, c_out, scale=0.1)
 
 
-# ---- 1. the wide family ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("c_in", [64, 128])
-@pytest.mark.parametrize("pd, n, d, h, w", [(p, *s) for p, shapes in WIDE_SHAPES.items() for s in shapes])
-def test_wide_conv3d_against_float64(device, c_in, pd, n, d, h, w):
-    """Forward, data gradient (128 -> c_in, so also 128 -> 64) and weight / bias gradient against float64 F.conv3d."""
-    K = _ops()
-    pad = (pd, 1, 1)
-    g = _g(300 + 7 * w + c_in + pd + 13 * d)
-    x = _randn(g, n, c_in, d, h, w)
-    wt, b = _conv_params(g, 128, c_in)
-    x64, w64, b64 = x.double(), wt.double(), b.double()
-    pre = F.conv3d(x64, w64, b64, padding=pad)
-    absref = F.conv3d(x64.abs(), w64.abs(), b64.abs(), padding=pad)
-    assert tuple(pre.shape) == (n, 128, d + 2 * pd - 1, h, w)
-    xd, wd, bd = x.to(device), wt.to(device), b.to(device)
-    y = K.conv3d_wide_fwd_f32(xd, wd, bd, relu=True, padding=pad)
-    assert tuple(y.shape) == tuple(pre.shape)
-    _within(y, pre.relu(), absref, what="forward relu")
-    _within(K.conv3d_wide_fwd_f32(xd, wd, bd, relu=False, padding=pad), pre, absref, what="forward without relu")
-    _within(K.conv3d_wide_fwd_f32(xd, wd, None, relu=False, padding=pad), pre - b64.view(1, -1, 1, 1, 1), absref,
-            what="forward plain")
-    dy = _randn(g, *pre.shape)
-    dy_gate, x_gate = _randn(g, *pre.shape), _randn(g, *x.shape)
-    for use_dg, use_xg in GATES:
-        dyg = dy.double() * (dy_gate > 0) if use_dg else dy.double()
-        gate_d = dy_gate.to(device) if use_dg else None
-        dx64 = F.conv_transpose3d(dyg, w64, padding=pad)
-        absdx = F.conv_transpose3d(dyg.abs(), w64.abs(), padding=pad)
-        assert tuple(dx64.shape) == tuple(x.shape)
-        if use_xg:
-            dx64 = dx64 * (x_gate > 0)
-        dx = K.conv3d_wide_bwd_data_f32(dy.to(device), gate_d, wd, x_gate.to(device) if use_xg else None, tuple(x.shape),
-                                        padding=pad)
-        assert tuple(dx.shape) == tuple(x.shape)
-        _within(dx, dx64, absdx, what=f"dx gates {use_dg} {use_xg}")
-        dw, db = K.conv3d_wide_bwd_weight_f32(xd, dy.to(device), gate_d, tuple(wt.shape), padding=pad)
-        dw2, db2 = K.conv3d_wide_bwd_weight_f32(xd, dy.to(device), gate_d, tuple(wt.shape), padding=pad)
-        assert torch.equal(dw, dw2) and torch.equal(db, db2), "the weight gradient's bits differ run to run"
-        assert tuple(dw.shape) == tuple(wt.shape) and tuple(db.shape) == (128,)
-        err_w = _rel(dw, torch.nn.grad.conv3d_weight(x64, tuple(wt.shape), dyg, padding=pad))
-        err_b = _rel(db, dyg.sum((0, 2, 3, 4)))
-        print(f"wide3d {c_in} pd {pd} {(n, d, h, w)} gates {use_dg}: dw {err_w:.2e} db {err_b:.2e} (bound {NORM_TOL})")
-        assert err_w <= NORM_TOL and err_b <= NORM_TOL
+# ---- the plain families' three passes: the records and the checker of tests/conv_family_checks.py ------------------------
+@C.cases_of({"conv3d_wide_pd0": 0, "conv3d_wide_pd1": 1}, ids="{tag}-{shape}-{c_in}")
+def test_wide_conv3d_against_float64(device, fam, c_in, c_out, shape):
+    C.check_family(_ops(), device, fam, c_in, c_out, shape)
 
 
-# ---- 2. the horizon first layer ----------------------------------------------------------------------------------------
+@C.cases_of("conv2d_head_s2p1", ids="{shape}-{c_in}")
+def test_head_against_float64(device, fam, c_in, c_out, shape):
+    C.check_family(_ops(), device, fam, c_in, c_out, shape)
+
+
+# ---- 1. the horizon first layer ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("d_in", [4, 2])
 @pytest.mark.parametrize("n, h, w", HORIZON_SHAPES)
 def test_horizon_layer_against_float64(device, d_in, n, h, w):
@@ -113,42 +76,7 @@ def test_horizon_layer_against_float64(device, d_in, n, h, w):
             assert (dw[:, 1] == 0).all(), "the horizon channel's gradient is not exactly 0 under all-zero horizons"
 
 
-# ---- 3. the stride-2 padding-1 head ------------------------------------------------------------------------------------
-@pytest.mark.parametrize("c_in", [256, 32])
-@pytest.mark.parametrize("n, h, w", HEAD_SHAPES)
-def test_head_against_float64(device, c_in, n, h, w):
-    K = _ops()
-    g = _g(500 + w + c_in)
-    x = _randn(g, n, c_in, h, w)
-    wt, b = _conv_params(g, 1, c_in, kernel=(3, 3))
-    x64, w64, b64 = x.double(), wt.double(), b.double()
-    pre = F.conv2d(x64, w64, b64, stride=2, padding=1)
-    absref = F.conv2d(x64.abs(), w64.abs(), b64.abs(), stride=2, padding=1)
-    assert tuple(pre.shape) == (n, 1, (h - 1) // 2 + 1, (w - 1) // 2 + 1)
-    xd, wd, bd = x.to(device), wt.to(device), b.to(device)
-    y = K.conv2d_head_s2p1_fwd_f32(xd, wd, bd)
-    assert tuple(y.shape) == tuple(pre.shape)
-    _within(y, pre, absref, what="head forward")
-    _within(K.conv2d_head_s2p1_fwd_f32(xd, wd, None), pre - b64.view(1, -1, 1, 1), absref, what="head forward without bias")
-    assert torch.equal(y, K.conv2d_head_s2p1_fwd_f32(xd, wd, bd))
-    dy, x_gate = _randn(g, *pre.shape), _randn(g, *x.shape)
-    opad = ((h + 1) % 2, (w + 1) % 2)              # the last row / column of an even side, which the forward never reads
-    dx64 = F.conv_transpose2d(dy.double(), w64, stride=2, padding=1, output_padding=opad)
-    absdx = F.conv_transpose2d(dy.double().abs(), w64.abs(), stride=2, padding=1, output_padding=opad)
-    assert tuple(dx64.shape) == tuple(x.shape)
-    for use_xg in (True, False):
-        dx = K.conv2d_head_s2p1_bwd_data_f32(dy.to(device), None, wd, x_gate.to(device) if use_xg else None, tuple(x.shape))
-        _within(dx, dx64 * (x_gate > 0) if use_xg else dx64, absdx, what=f"head dx gate {use_xg}")
-    dw, db = K.conv2d_head_s2p1_bwd_weight_f32(xd, dy.to(device), None, tuple(wt.shape))
-    dw2, db2 = K.conv2d_head_s2p1_bwd_weight_f32(xd, dy.to(device), None, tuple(wt.shape))
-    assert torch.equal(dw, dw2) and torch.equal(db, db2), "the head's weight gradient differs run to run"
-    assert tuple(dw.shape) == tuple(wt.shape) and tuple(db.shape) == (1,)
-    err_w = _rel(dw, torch.nn.grad.conv2d_weight(x64, tuple(wt.shape), dy.double(), stride=2, padding=1))
-    err_b = _rel(db, dy.double().sum((0, 2, 3)))
-    print(f"head p1 {c_in} {(n, h, w)}: dw {err_w:.2e} db {err_b:.2e} (bound {NORM_TOL})")
-    assert err_w <= NORM_TOL and err_b <= NORM_TOL
-
-
+# ---- 2. the stride-2 padding-1 head against its twins ------------------------------------------------------------------
 def test_strided_heads_are_one_kernel_set_at_two_paddings(device):
     """The padding-2 head on x and the padding-1 head on x with a ring of zeros are the same kernels at PAD = 2 and 1, so they
     agree bit for bit: a tap in the zero ring is fmaf(w, 0.0f, s), exactly what the out-of-image predicate gives, and the
@@ -202,7 +130,7 @@ def test_head_depth2_view_against_float64_conv3d(device, n, h, w):
     assert _rel(dw, w64.grad) <= NORM_TOL and _rel(db, b64.grad) <= NORM_TOL
 
 
-# ---- 4. refusals before any launch -------------------------------------------------------------------------------------
+# ---- 3. refusals before any launch -------------------------------------------------------------------------------------
 def test_refusals_raise_before_any_launch(device):
     import ctypes
     from predict_pv_yield_amd import _lib
