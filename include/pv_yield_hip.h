@@ -768,6 +768,67 @@ int pv_convt2d_ae_horizon_bwd_weight_f32(const float* x, const float* horizon, c
                                          float* dbias, int32_t n, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
                                          void* stream);
 
+/* ---- notebooks/11_just_conv_and_conv_over_time.ipynb: per-frame padded Conv2d stack, convolution over time ---- */
+/* (line numbers: the raw 11_...ipynb file; the LitAutoEncoder cell starts at 1385 with CHANNELS = 32, N_HIST_IMAGES = 4,
+ * STRIPE_WIDTH = 128 // 24; the live self.conv is at 1407-1416, self.temporal_conv at 1420-1426, forward at 1428-1451.)  NCHW
+ * f32, exact f32, planes up to 128 wide; gates (NULL = none) and weight-gradient slabs follow the conventions of the
+ * pv_conv2d_ae_* entry points above.  The four calls of self.conv with the same weights are folded into the batch, image index
+ * frames * b + f: conv.2 is pv_conv2d_ae_* and conv.6 pv_conv2d_head_s2_* at n = frames * B.  Unsupported shapes return
+ * PV_ESIZE, null pointers, non-positive sizes and a short workspace PV_EINVAL, before any launch. */
+/* replaces: forecast_horizon_img[example_i, 0, :, stripe_col_start:stripe_col_end] = 1; hist_img = hist_images[:, i:i+1];
+ * torch.cat((hist_img, forecast_horizon_img), dim=1); nn.Conv2d(2, CHANNELS//2, kernel_size=3), nn.ReLU() for every i,
+ * 11_...ipynb:1408-1409, 1431-1445.  history [n][frames][h][w_img] read in place; stripe_start [n] (device int32): input channel
+ * 1 of image (b, f) is 1 on columns stripe_start[b] <= c < stripe_start[b] + stripe_width inside the plane, synthesised in the
+ * kernel (no [frames * n][2][h][w] tensor and no stripe plane exist); w [16][2][3][3]; y [n * frames][16][h - 2][w_img - 2];
+ * frames 1..7, c_out = 16, h, w_img >= 3, w_img <= 128, stripe_width >= 0. */
+int pv_conv2d_ae_frame_stripe_fwd_f32(const float* history, const int32_t* stripe_start, const float* w, const float* bias,
+                                      float* y, int32_t n, int32_t frames, int32_t h, int32_t w_img, int32_t c_out,
+                                      int32_t stripe_width, void* stream);
+/* bytes of the weight-gradient workspace: one partial [16][2 * 9 + 1] per slab of tiles */
+int pv_conv2d_ae_frame_stripe_bwd_weight_workspace_bytes(int32_t n, int32_t frames, int32_t h, int32_t w_img, size_t* bytes);
+/* replaces: the weight and bias gradients of conv.0 summed over its frames calls (autograd of 11_...ipynb:1408, 1441-1445),
+ * re-synthesising the stripe plane as the forward does: dw [16][2][3][3], dbias [16]; dy [n * frames][16][h - 2][w_img - 2] is
+ * the pre-activation gradient (already gated); deterministic.  The layer's input is data: there is no data gradient. */
+int pv_conv2d_ae_frame_stripe_bwd_weight_f32(const float* history, const int32_t* stripe_start, const float* dy, float* dw,
+                                             float* dbias, int32_t n, int32_t frames, int32_t h, int32_t w_img, int32_t c_out,
+                                             int32_t stripe_width, void* ws, size_t ws_bytes, void* stream);
+/* replaces: nn.Conv2d(CHANNELS, CHANNELS, kernel_size=3, stride=1, padding=2) (+ nn.ReLU() if relu), conv.4 of
+ * 11_...ipynb:1412-1413.  (c_in, c_out) = (32, 32) only; x [n][32][h][w], w [32][32][3][3], y [n][32][h + 2][w + 2]; w_in + 2
+ * <= 128; bias may be NULL.  The arithmetic of pv_convt2d_ae_fwd_f32 with the weight read as it lies (no flipped or
+ * transposed copy). */
+int pv_conv2d_ae_p2_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                            int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream);
+/* replaces: the input gradient of conv.4 (autograd of 11_...ipynb:1412): the unpadded conv of dy [n][32][h + 2][w + 2] with the
+ * mirrored, channel-swapped weight, read through its strides; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0. */
+int pv_conv2d_ae_p2_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                                 int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream);
+/* bytes of the workspace of pv_conv2d_ae_p2_bwd_weight_f32: one partial [32][32 * 9 + 1] per slab of tiles */
+int pv_conv2d_ae_p2_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                               size_t* bytes);
+/* replaces: the weight and bias gradients of conv.4 (autograd of 11_...ipynb:1412): dw [32][32][3][3] over the positions of dy
+ * against x zero-padded by 2, dbias [32] = the sum of dy (both with dy zeroed where dy_gate <= 0); deterministic. */
+int pv_conv2d_ae_p2_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias, int32_t n,
+                                   int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
+                                   void* stream);
+/* replaces: conv_out.view((-1, 1, 4096, 1)) per frame, torch.cat(conv_outs, dim=3), self.temporal_conv (nn.Conv2d(1, 16, (1,
+ * 2)), nn.ReLU(), nn.Conv2d(16, 16, (1, 2)), nn.ReLU(), nn.Conv2d(16, 1, (1, 2))) and out.view((-1, 1, 64, 64)),
+ * 11_...ipynb:1420-1426, 1446-1451.  u [n * frames][p] = [n][4][p]: the per-frame stack's output as it lies, p pixels per
+ * image; w1 [16][1][1][2], b1 [16], w2 [16][16][1][2], b2 [16], w3 [1][16][1][2], b3 [1]; y [n][p].  The three layers of a
+ * pixel run in registers: neither the [n][1][p][4] image nor a hidden layer is stored.  frames = 4 and c_mid = 16 only. */
+int pv_conv_time_fwd_f32(const float* u, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                         const float* b3, float* y, int32_t n, int32_t frames, int32_t c_mid, int32_t p, void* stream);
+/* bytes of the workspace of pv_conv_time_bwd_f32: one partial of the 609 parameter gradients per block */
+int pv_conv_time_bwd_workspace_bytes(int32_t n, int32_t frames, int32_t c_mid, int32_t p, size_t* bytes);
+/* replaces: autograd of self.temporal_conv and of the view / cat in front of it (11_...ipynb:1446-1451) in one launch plus the
+ * ordered slab sums: dy [n][p]; the hidden layers are recomputed from u and their ReLU gates taken from the recomputed values;
+ * du [n][4][p] and the six parameter gradients are overwritten; per-block partial sums added in block order (no atomics,
+ * identical bits run to run).  u_is_relu_output: u is the output of conv.6's ReLU (11_...ipynb:1415), so du leaves zeroed
+ * where u <= 0 and is conv.6's pre-activation gradient (pv_conv2d_head_s2_* take no dy_gate). */
+int pv_conv_time_bwd_f32(const float* u, const float* dy, const float* w1, const float* b1, const float* w2, const float* b2,
+                         const float* w3, float* du, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3,
+                         int32_t n, int32_t frames, int32_t c_mid, int32_t p, int32_t u_is_relu_output, void* ws,
+                         size_t ws_bytes, void* stream);
+
 /* MaxPool3d over x[B*C planes][Ti,Hi,Wi]; argmax (may be NULL) = flat winner offset inside the plane stack, first
  * maximum wins, NaN propagates (torch CPU semantics).  bwd overwrites dx by gathering dy through argmax. */
 int pv_maxpool3d_fwd_f32(const float* x, float* y, int32_t* argmax, const pv_conv3d_geom* d, void* stream);

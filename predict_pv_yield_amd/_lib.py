@@ -271,6 +271,16 @@ SIGNATURES = {
     "pv_convt2d_ae_horizon_fwd_f32": _CONVT_HORIZON_FWD,
     "pv_convt2d_ae_horizon_bwd_weight_workspace_bytes": [c_i32] * 3 + [ctypes.POINTER(c_sz)],
     "pv_convt2d_ae_horizon_bwd_weight_f32": _CONVT_HORIZON_BWD_WEIGHT,
+    # notebook 11: the per-frame stripe first layer has the stripe prototypes (n, frames, h, w, c_out, stripe_width), the
+    # padded 32 -> 32 layer is a _conv2d_family, the convolution over time takes (n, frames, c_mid, p) after its pointers (its backward then
+    # the flag that u is a ReLU output)
+    "pv_conv2d_ae_frame_stripe_fwd_f32": _STRIPE_FWD,
+    "pv_conv2d_ae_frame_stripe_bwd_weight_workspace_bytes": [c_i32] * 4 + [ctypes.POINTER(c_sz)],
+    "pv_conv2d_ae_frame_stripe_bwd_weight_f32": _STRIPE_BWD_WEIGHT,
+    **_conv2d_family("conv2d_ae_p2", _WS_QUERY5),
+    "pv_conv_time_fwd_f32": [c_vp] * 8 + [c_i32] * 4 + [c_vp],        # u, w1, b1, w2, b2, w3, b3, y
+    "pv_conv_time_bwd_workspace_bytes": [c_i32] * 4 + [ctypes.POINTER(c_sz)],
+    "pv_conv_time_bwd_f32": [c_vp] * 14 + [c_i32] * 5 + _WORKSPACE + [c_vp],   # u, dy, w1, b1, w2, b2, w3, du, six gradients
     "pv_maxpool3d_fwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_maxpool3d_bwd_f32": [c_vp, c_vp, c_vp, _PCG, c_vp],
     "pv_mse_loss_f32": [c_vp, c_vp, c_i64, c_f32, c_vp, c_vp, c_vp],

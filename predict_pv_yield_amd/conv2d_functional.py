@@ -7,7 +7,8 @@ and the stride-2 64 / 128-channel Conv2d / ConvTranspose2d kernels, stride-2 str
 head and prediction-window MSE of csrc/conv2d_wide_s2_f32.hip (notebooks/09_horizon_represented_as_a_stripe.ipynb) and the
 per-frame first layer and 128 -> 32 ConvTranspose2d of csrc/conv2d_frames_f32.hip (notebooks/07_multiple_historical_images.ipynb)
 and the four-input first layer and stride-1 horizon ConvTranspose2d of csrc/conv2d_inputs_f32.hip
-(notebooks/05_more_image_inputs.ipynb).
+(notebooks/05_more_image_inputs.ipynb) and the per-frame stripe first layer and padded 32 -> 32 layer of csrc/conv2d_ae_f32.hip
+with the convolution over time of csrc/conv_time_f32.hip (notebooks/11_just_conv_and_conv_over_time.ipynb).
 
 Reference operators replaced:
   experiments/002_cnn_processes_single_sat_image_then_rnn.py
@@ -45,6 +46,10 @@ Reference operators replaced:
     self.decoder(cat(embedding, forecast horizon plane)): ConvTranspose2d 33 -> 32 -> 32 with ReLU, ConvTranspose2d 32 -> 1
                                                                                                                :1365-1371, 1382-1387
     F.mse_loss(y_hat, y)                                                                                       :1394
+  notebooks/11_just_conv_and_conv_over_time.ipynb (raw lines of the .ipynb file)
+    for each of the 4 history frames: self.conv(cat(hist_img, forecast-horizon stripe plane)): Conv2d 2 -> 16 -> 32 -> 32
+    (padding 2) -> 1 (stride 2, padding 2), a ReLU after each; conv_out.view((-1, 1, 4096, 1))                  :1407-1416, 1431-1447
+    self.temporal_conv(torch.cat(conv_outs, dim=3)): Conv2d 1 -> 16 -> 16 -> 1, kernel (1, 2), ReLU between      :1420-1426, 1449-1451
 
 Gating.  As in functional.Conv3dGeneralF32, the ReLU gating of an activation gradient is moved into the kernel that
 produces it.  x_is_relu_output -> this layer's dx leaves already zeroed where x <= 0 (the lower layer's pre-activation
@@ -92,6 +97,24 @@ FRAME_HORIZON_S2_OPS = (K.conv2d_s2_frame_horizon_fwd_f32, K.conv2d_s2_frame_hor
 CONVT2D_S2_FRAMES_OPS = (K.convt2d_s2_frames_fwd_f32, K.convt2d_s2_frames_bwd_data_f32, K.convt2d_s2_frames_bwd_weight_f32)
 # the flow prediction, t0 image and flow field of notebook 05, read in place as four channels
 INPUTS_AE_OPS = (K.conv2d_ae_inputs_fwd_f32, K.conv2d_ae_inputs_bwd_weight_f32)
+# notebook 11: the padded 32 -> 32 layer under the three-pass signatures (conv2d_ae_* with padding=2; hip_ops keeps one name
+# per pass) and the per-frame history plane plus stripe plane
+
+
+def _conv2d_ae_p2_fwd(x, weight, bias, relu=True):
+    return K.conv2d_ae_fwd_f32(x, weight, bias, relu, padding=2)
+
+
+def _conv2d_ae_p2_bwd_data(dy, dy_gate, weight, x_gate, x_shape):
+    return K.conv2d_ae_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape, padding=2)
+
+
+def _conv2d_ae_p2_bwd_weight(x, dy, dy_gate, weight_shape):
+    return K.conv2d_ae_bwd_weight_f32(x, dy, dy_gate, weight_shape, padding=2)
+
+
+CONV2D_AE_P2_OPS = (_conv2d_ae_p2_fwd, _conv2d_ae_p2_bwd_data, _conv2d_ae_p2_bwd_weight)
+FRAME_STRIPE_AE_OPS = (K.conv2d_ae_frame_stripe_fwd_f32, K.conv2d_ae_frame_stripe_bwd_weight_f32)
 # ... and of the conv with fused MaxPool2d(3): the forward returns (pooled, codes), the gradients take the codes
 CONV2D144_POOL_OPS = (K.conv2d144_pool_fwd_f32, K.conv2d144_pool_bwd_data_f32, K.conv2d144_pool_bwd_weight_f32)
 CONV2D_AE_POOL_OPS = (K.conv2d_ae_pool_fwd_f32, K.conv2d_ae_pool_bwd_data_f32, K.conv2d_ae_pool_bwd_weight_f32)
@@ -110,6 +133,8 @@ class SynthConvReLU(torch.autograd.Function):
                                             channels of notebook 05's x_cat
       FRAME_HORIZON_S2_OPS                  history [N, F, H, W] f32, horizon [N] f32: every frame with the horizon as a second,
                                             constant channel, the frames folded into the batch -> [N F, 32, ..]
+      FRAME_STRIPE_AE_OPS                   history [N, F, H, W] f32, stripe_start [N] int32: every frame with the example's stripe
+                                            plane as a second channel, the frames folded into the batch -> [N F, 16, ..]; stripe_width
       conv3d_wide_functional.HORIZON_WIDE_OPS   history [N, D, H, W] f32, horizon [N] f32 as a second, constant channel"""
 
     @staticmethod
@@ -206,8 +231,8 @@ def conv_chain(x, layers, last_relu):
     own.  layers, in order, each one of
       (ops, module)                     ConvReLU, or ConvPool where ops is one of POOL_OPS
       (ops, module, inputs[, scalars])  with x None: SynthConvReLU on the (forward, weight gradient) pair ops
-      (Function, module, inputs)        a Function of one family that ends in a ReLU, applied as (y, *inputs, weight, bias,
-                                        x_is_relu_output, dy_pregated)
+      (Function, module, inputs)        a Function of one family that ends in a ReLU (or, as the last layer with last_relu False,
+                                        in none), applied as (y, *inputs, weight, bias, x_is_relu_output, dy_pregated)
       a callable                        a view of the activation (squeeze, unsqueeze): the values, so the flags, stand
     Every layer but the last ends in a ReLU (the nn.ReLU modules of the notebooks' nn.Sequential are fused into the layers'
     kernels); the last one does where last_relu.
@@ -522,3 +547,54 @@ def nb05_more_inputs_f32(flow_pred, t0, flow_field, horizon, encoder, decoder):
                              (CONV2D_AE_OPS, encoder[2]), (CONV2D_AE_OPS, encoder[4]),
                              (HorizonConvTransposeS1ReLU, decoder[0], (horizon,)),
                              (CONVT2D_AE_OPS, decoder[2]), (CONVT2D_HEAD_OPS, decoder[4])], last_relu=False)
+
+
+# ---- notebooks/11_just_conv_and_conv_over_time.ipynb ------------------------------------------------------------------------
+class ConvOverTime(torch.autograd.Function):
+    """self.temporal_conv of notebook 11 on the per-frame stack's output u [4 N, 1, H, W] (image 4 i + f): three (1, 2)
+    convolutions over the four frame values of each pixel, ReLU between, in registers -> [N, 1, H, W].  Saves u and the
+    parameters; backward recomputes the hidden layers and returns du and the six parameter gradients from one launch.
+    Argument order as conv_chain applies a Function: the activation, the first two layers' parameters, then the last
+    layer's weight and bias and the two flags.  x_is_relu_output: du leaves gated by u > 0, the pre-activation gradient of
+    the layer that made u (pv_conv2d_head_s2_* take no dy_gate).  No ReLU follows the last layer, so dy is never pregated."""
+
+    @staticmethod
+    def forward(ctx, u, w1, b1, w2, b2, w3, b3, x_is_relu_output, dy_pregated):
+        assert not dy_pregated, "no ReLU follows temporal_conv: it is a chain's last layer, with last_relu False"
+        tensors = tuple(t.contiguous() for t in (u, w1, b1, w2, b2, w3, b3))
+        ctx.save_for_backward(*tensors[:-1])
+        ctx.x_is_relu_output = x_is_relu_output
+        return K.conv_time_fwd_f32(*tensors)
+
+    @staticmethod
+    def backward(ctx, dy):
+        u, *params = ctx.saved_tensors
+        return K.conv_time_bwd_f32(u, dy.contiguous(), *params, ctx.x_is_relu_output) + (None, None)
+
+
+def conv_over_time(u, temporal_conv, x_is_relu_output=False):
+    """temporal_conv(cat of the four frames' outputs along a new last axis) of 11_just_conv_and_conv_over_time.ipynb:1446-1451;
+    temporal_conv = the notebook's nn.Sequential (modules 0, 2, 4 nn.Conv2d with kernel (1, 2)).  x_is_relu_output: du leaves
+    gated by u > 0."""
+    t = temporal_conv
+    return ConvOverTime.apply(u, t[0].weight, t[0].bias, t[2].weight, t[2].bias, t[4].weight, t[4].bias,
+                              bool(x_is_relu_output), False)
+
+
+def nb11_layers(history, stripe_start, conv, temporal_conv):
+    """Notebook 11 as conv_chain's layer table: the per-frame stack, every layer of it ending in a ReLU, then the convolution
+    over time as the chain's last layer, which ends in none (last_relu=False).  The head's ReLU gate is applied to du by the
+    convolution over time, so the head receives its dy pregated like the layers below it."""
+    t = temporal_conv
+    return [(FRAME_STRIPE_AE_OPS, conv[0], (history, stripe_start), {"stripe_width": STRIPE_WIDTH}),
+            (CONV2D_AE_OPS, conv[2]), (CONV2D_AE_P2_OPS, conv[4]), (CONV2D_HEAD_S2_OPS, conv[6]),
+            (ConvOverTime, t[4], (t[0].weight, t[0].bias, t[2].weight, t[2].bias))]
+
+
+def nb11_conv_over_time_f32(history, stripe_start, conv, temporal_conv):
+    """self.temporal_conv(cat([self.conv(cat(history[:, f:f + 1], stripe plane)).view(-1, 1, P, 1) for f in range(4)], dim=3))
+    .view(-1, 1, s', s') of 11_just_conv_and_conv_over_time.ipynb:1428-1451; conv / temporal_conv = the notebook's two
+    nn.Sequential.  history [N, 4, H, W], stripe_start [N] int32 -> [N, 1, s', s'].  The four calls of self.conv are one pass
+    over 4 N images (image 4 i + f), so every parameter's gradient is the sum over the frames, and the [N, 1, P, 4] image is
+    the head's output [4 N, 1, s', s'] read in place."""
+    return conv_chain(None, nb11_layers(history, stripe_start, conv, temporal_conv), last_relu=False)

@@ -28,13 +28,33 @@
 // output (0..8 = first maximum, row-major; 255 = maximum <= 0, no gradient); backward passes expand the pooled gradient
 // through the codes while staging.  Weight gradients: fixed slabs, each block writing its partial sums to its own
 // workspace slab, added in slab order (no atomics, identical bits run to run).
+//
+// notebooks/11_just_conv_and_conv_over_time.ipynb (the LitAutoEncoder cell, raw lines 1407-1416 and 1428-1447) adds two
+// layers to this file.  Its first layer, Conv2d 2 -> 16 on each history frame with the forecast-horizon stripe as the second
+// channel, is the counts layer's tile pair over SRC_STRIPE: image frames b + f reads plane f of history [b] in place and the
+// stripe plane of example b is synthesised while the tile is staged (Stripe / load_in of conv2d_stripe_f32.h), so neither the
+// [frames n][2][h][w] input nor the plane is stored.  Its padded layer, Conv2d 32 -> 32 padding 2, is the ConvTranspose2d 32
+// -> 32 passes of this file with the weight index switched (Fwd's w_sm / w_sc / flip; the slab sum untransposed): forward =
+// the padded form with [c_out][c_in] read as it lies, data gradient = the valid form with the mirrored, channel-swapped
+// weight, weight gradient = D[co][(ci, tap)] over the positions of dy against x zero-padded by 2.  No weight copy is made.
 #include "conv2d_ae_plan_f32.h"
 #include "conv2d_counts_f32.h"
+#include "conv2d_stripe_f32.h"
 
 namespace pv {
 namespace {
 
 constexpr int kMaxWidth = 128, kCrop = 8, kMinSide = 11;
+constexpr int kFrameStripeC = 16, kPaddedC = 32;   // notebook 11: CHANNELS // 2 of its first layer, CHANNELS of its padded one
+
+// SRC_STRIPE under the tile kernels (c_in = 2): x = history [n][n_frames][h][w], flow = the int32 stripe starts [n], t_total =
+// the stripe's width.  Image i = n_frames b + f: channel 0 is plane i of history (a one-frame history indexed by the image),
+// channel 1 the stripe plane of example b.
+template <>
+__device__ __forceinline__ float load_in<SRC_STRIPE>(const In& s, int img, int ch, int r, int col) {
+  const Stripe sp = {(const int32_t*)s.flow, s.t_total, 1};
+  return load_in<SRC_STRIPE>(s, sp, ch == 0 ? img : img / s.n_frames, ch, r, col);
+}
 
 // Windowed, normalised MSE (16_maxpool.ipynb, _training_or_validation_step: the window starts at (8, 8); 15_int16.ipynb: at
 // (0, 0)): block b takes example b; d = y_hat - (target[row0 + r][col0 + c] - mean) / std, dy_hat = 2 d / count, partial[b]
@@ -113,6 +133,36 @@ int check_counts(const char* who, int n, int h, int w, int c_out) {
   PV_REQUIRE(w <= kMaxWidth, PV_ESIZE, "%s: width %d beyond %d", who, w, kMaxWidth);
   PV_REQUIRE(h >= kMinSide && w >= kMinSide, PV_ESIZE,
              "%s: spatial extent %d x %d gives no whole 3x3 pool window after four 3x3 convolutions", who, h, w);
+  return PV_OK;
+}
+
+In frame_stripe_in(const float* history, const int32_t* stripe_start, int frames, int stripe_width, int h, int w) {
+  In s = {};
+  s.x = history, s.flow = stripe_start, s.t_total = stripe_width, s.n_frames = frames, s.c_in = 2, s.h = h, s.w = w;
+  return s;
+}
+
+// (h, w) = the extent of a history frame
+int check_frame_stripe(const char* who, int n, int frames, int h, int w, int c_out, int stripe_width) {
+  PV_REQUIRE(n > 0, PV_EINVAL, "%s: non-positive dimension", who);
+  PV_REQUIRE(frames >= 1 && frames <= kMaxHist, PV_ESIZE, "%s: unsupported frame count %d (1..%d)", who, frames, kMaxHist);
+  PV_REQUIRE(c_out == kFrameStripeC, PV_ESIZE, "%s: unsupported channel count c_out=%d (%d)", who, c_out, kFrameStripeC);
+  PV_REQUIRE(stripe_width >= 0, PV_EINVAL, "%s: negative stripe width", who);
+  PV_REQUIRE(h >= 3 && w >= 3, PV_ESIZE, "%s: spatial extent %d x %d smaller than the 3x3 kernel", who, h, w);
+  PV_REQUIRE(w <= kMaxWidth, PV_ESIZE, "%s: width %d beyond %d", who, w, kMaxWidth);
+  PV_REQUIRE((long long)n * frames * kFrameStripeC * h * w < (1LL << 31), PV_ESIZE,
+             "%s: tensor beyond 2^31 elements (32-bit indexing)", who);
+  return PV_OK;
+}
+
+// (h_in, w_in) = the extent of x, the padded layer's input; the output is (h_in + 2) x (w_in + 2)
+int check_p2(const char* who, int n, int c_in, int c_out, int h_in, int w_in) {
+  PV_REQUIRE(n > 0 && c_in > 0 && c_out > 0 && h_in > 0 && w_in > 0, PV_EINVAL, "%s: non-positive dimension", who);
+  PV_REQUIRE(c_in == kPaddedC && c_out == kPaddedC, PV_ESIZE, "%s: unsupported channel counts c_in=%d c_out=%d (32 -> 32)",
+             who, c_in, c_out);
+  PV_REQUIRE(w_in + 2 <= kMaxWidth, PV_ESIZE, "%s: output width %d beyond %d", who, w_in + 2, kMaxWidth);
+  PV_REQUIRE((long long)n * kPaddedC * (h_in + 2) * (w_in + 2) < (1LL << 31), PV_ESIZE,
+             "%s: tensor beyond 2^31 elements (32-bit indexing)", who);
   return PV_OK;
 }
 
@@ -395,6 +445,93 @@ int pv_convt2d_ae_bwd_weight_f32(const float* x, const float* dy, const float* d
   const WgPlan p = wg_plan(n, c_in, c_out, h_in + 2, w_in + 2);
   return run_wgrad<SRC_PLAIN, SRC_PLAIN>(who, plain_in(x, nullptr, c_in, h_in, w_in),
                                          plain_in(dy, dy_gate, c_out, h_in + 2, w_in + 2), 2, p, dw, dbias, true, ws,
+                                         ws_bytes, as_stream(stream));
+}
+
+int pv_conv2d_ae_frame_stripe_fwd_f32(const float* history, const int32_t* stripe_start, const float* w, const float* bias,
+                                      float* y, int32_t n, int32_t frames, int32_t h, int32_t w_img, int32_t c_out,
+                                      int32_t stripe_width, void* stream) {
+  const char* who = "pv_conv2d_ae_frame_stripe_fwd_f32";
+  PV_REQUIRE(history && stripe_start && w && bias && y, PV_EINVAL, "%s: null pointer", who);
+  int rc = check_frame_stripe(who, n, frames, h, w_img, c_out, stripe_width);
+  if (rc) return rc;
+  Fwd a = conv_fwd_args(w, bias, y, 2, c_out, h, w_img, 1);
+  a.in = frame_stripe_in(history, stripe_start, frames, stripe_width, h, w_img);
+  return run_fwd<4, 1, SRC_STRIPE, false>(who, a, n * frames, as_stream(stream));
+}
+
+int pv_conv2d_ae_frame_stripe_bwd_weight_workspace_bytes(int32_t n, int32_t frames, int32_t h, int32_t w_img, size_t* bytes) {
+  const char* who = "pv_conv2d_ae_frame_stripe_bwd_weight_workspace_bytes";
+  PV_REQUIRE(bytes, PV_EINVAL, "%s: null pointer", who);
+  int rc = check_frame_stripe(who, n, frames, h, w_img, kFrameStripeC, 0);
+  if (rc) return rc;
+  *bytes = wg_plan(n * frames, 2, kFrameStripeC, h - 2, w_img - 2).ws;
+  return PV_OK;
+}
+
+int pv_conv2d_ae_frame_stripe_bwd_weight_f32(const float* history, const int32_t* stripe_start, const float* dy, float* dw,
+                                             float* dbias, int32_t n, int32_t frames, int32_t h, int32_t w_img, int32_t c_out,
+                                             int32_t stripe_width, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "pv_conv2d_ae_frame_stripe_bwd_weight_f32";
+  PV_REQUIRE(history && stripe_start && dy && dw && dbias, PV_EINVAL, "%s: null pointer", who);
+  int rc = check_frame_stripe(who, n, frames, h, w_img, c_out, stripe_width);
+  if (rc) return rc;
+  // 9 * 2 + 1 = 19 columns: two column tiles, one per wave, against one 16-row tile
+  const WgPlan p = wg_plan(n * frames, 2, kFrameStripeC, h - 2, w_img - 2);
+  return launch_wgrad<1, 1, SRC_STRIPE, SRC_PLAIN>(who, frame_stripe_in(history, stripe_start, frames, stripe_width, h, w_img),
+                                                   plain_in(dy, nullptr, kFrameStripeC, h - 2, w_img - 2), 0, p, dw, dbias,
+                                                   false, ws, ws_bytes, as_stream(stream));
+}
+
+int pv_conv2d_ae_p2_fwd_f32(const float* x, const float* w, const float* bias, float* y, int32_t n, int32_t c_in,
+                            int32_t c_out, int32_t h_in, int32_t w_in, int32_t relu, void* stream) {
+  const char* who = "pv_conv2d_ae_p2_fwd_f32";
+  PV_REQUIRE(x && w && y, PV_EINVAL, "%s: null pointer", who);
+  int rc = check_p2(who, n, c_in, c_out, h_in, w_in);
+  if (rc) return rc;
+  // pv_convt2d_ae_fwd_f32's padded form with the weight [c_out][c_in][3][3] read as it lies: [m][c], unmirrored
+  Fwd a = full_fwd_args(w, bias, y, c_out, h_in, w_in, relu);
+  a.w_sm = c_in * 9, a.w_sc = 9, a.flip = 0;
+  a.in = plain_in(x, nullptr, c_in, h_in, w_in);
+  return run_fwd<32, 2, SRC_PLAIN, false>(who, a, n, as_stream(stream));
+}
+
+int pv_conv2d_ae_p2_bwd_data_f32(const float* dy, const float* dy_gate, const float* w, float* dx, const float* x_gate,
+                                 int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* stream) {
+  const char* who = "pv_conv2d_ae_p2_bwd_data_f32";
+  PV_REQUIRE(dy && w && dx, PV_EINVAL, "%s: null pointer", who);
+  int rc = check_p2(who, n, c_in, c_out, h_in, w_in);
+  if (rc) return rc;
+  // pv_convt2d_ae_bwd_data_f32's valid conv of dy [n][c_out][h + 2][w + 2], the weight [c_out][c_in][3][3] read as [c][m],
+  // mirrored
+  Fwd a = conv_fwd_args(w, nullptr, dx, c_out, c_in, h_in + 2, w_in + 2, 0);
+  a.w_sm = 9, a.w_sc = c_in * 9, a.flip = 1;
+  a.in = plain_in(dy, dy_gate, c_out, h_in + 2, w_in + 2);
+  a.out_gate = x_gate;
+  return run_fwd<32, 2, SRC_PLAIN, false>(who, a, n, as_stream(stream));
+}
+
+int pv_conv2d_ae_p2_bwd_weight_workspace_bytes(int32_t n, int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in,
+                                               size_t* bytes) {
+  const char* who = "pv_conv2d_ae_p2_bwd_weight_workspace_bytes";
+  PV_REQUIRE(bytes, PV_EINVAL, "%s: null pointer", who);
+  int rc = check_p2(who, n, c_in, c_out, h_in, w_in);
+  if (rc) return rc;
+  *bytes = wg_plan(n, c_in, c_out, h_in + 2, w_in + 2).ws;
+  return PV_OK;
+}
+
+int pv_conv2d_ae_p2_bwd_weight_f32(const float* x, const float* dy, const float* dy_gate, float* dw, float* dbias, int32_t n,
+                                   int32_t c_in, int32_t c_out, int32_t h_in, int32_t w_in, void* ws, size_t ws_bytes,
+                                   void* stream) {
+  const char* who = "pv_conv2d_ae_p2_bwd_weight_f32";
+  PV_REQUIRE(x && dy && dw && dbias, PV_EINVAL, "%s: null pointer", who);
+  int rc = check_p2(who, n, c_in, c_out, h_in, w_in);
+  if (rc) return rc;
+  // pv_convt2d_ae_bwd_weight_f32's sum with the slab sum untransposed: dw[co][ci][tap] = D[co][(ci, tap)]
+  const WgPlan p = wg_plan(n, c_in, c_out, h_in + 2, w_in + 2);
+  return run_wgrad<SRC_PLAIN, SRC_PLAIN>(who, plain_in(x, nullptr, c_in, h_in, w_in),
+                                         plain_in(dy, dy_gate, c_out, h_in + 2, w_in + 2), 2, p, dw, dbias, false, ws,
                                          ws_bytes, as_stream(stream));
 }
 

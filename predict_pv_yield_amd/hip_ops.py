@@ -1180,6 +1180,18 @@ def _check_aet(who, x_shape, weight_shape):
                          f"{tuple(weight_shape)}")
 
 
+AE_P2_PAIR = (32, 32)                     # (c_in, c_out) of pv_conv2d_ae_p2_*
+
+
+def _check_ae_p2(who, x_shape, weight_shape):
+    _check_ae(who, x_shape, weight_shape)
+    if (x_shape[1], weight_shape[0]) != AE_P2_PAIR:
+        raise ValueError(f"{who}: (C_in, C_out) = (32, 32) expected with padding 2, got ({x_shape[1]}, {weight_shape[0]})")
+    if min(x_shape[2:]) < 1 or x_shape[3] + 2 > WIDE_MAX_W:
+        raise ValueError(f"{who}: a non-empty plane whose output is at most {WIDE_MAX_W} columns wide expected, got "
+                         f"{x_shape[2]} x {x_shape[3]}")
+
+
 def _pooled_shape(n, c, h, w):
     return (n, c, (h - 2) // 3, (w - 2) // 3)
 
@@ -1290,6 +1302,8 @@ def _s2_hw(h, w):
 _CONV2D = _conv2d_family("conv2d", _check_c32, _valid_hw)
 _CONV2D144 = _conv2d_family("conv2d144", _check_c144, _valid_hw, ws_args=(0,))
 _CONV2D_AE = _conv2d_family("conv2d_ae", _check_ae, _valid_hw, ws_args=(0,))
+# notebook 11: the padded 32 -> 32 layer, a record of its own (its stem names its entry points and its workspace)
+_CONV2D_AE_P2 = _conv2d_family("conv2d_ae_p2", _check_ae_p2, lambda h, w: (h + 2, w + 2))
 _CONVT2D_AE = _conv2d_family("convt2d_ae", _check_aet, lambda h, w: (h + 2, w + 2), c_out_axis=1)
 _CONV2D_S2 = _conv2d_family("conv2d_s2", _check_ae, _s2_hw)
 _CONVT2D_S2 = _conv2d_family("convt2d_s2", _check_aet, lambda h, w: (2 * h + 1, 2 * w + 1), c_out_axis=1)
@@ -1618,19 +1632,26 @@ def conv2d_ae_counts_bwd_weight_f32(history, flow_pred, horizon, dy, weight_shap
     return _counts_bwd_weight(_CONV2D_AE, history, flow_pred, horizon, dy, weight_shape)
 
 
-def conv2d_ae_fwd_f32(x, weight, bias, relu=True):
-    """conv2d(x, weight) + bias (+ ReLU) for (C_in, C_out) = (16, 32) or (32, 32), W <= 128."""
-    return _conv_fwd(_CONV2D_AE, x, weight, bias, relu)
+def _ae_family(padding):
+    if padding not in (0, 2):
+        raise ValueError(f"conv2d_ae: padding 0 or 2 expected, got {padding}")
+    return _CONV2D_AE_P2 if padding else _CONV2D_AE
 
 
-def conv2d_ae_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
+def conv2d_ae_fwd_f32(x, weight, bias, relu=True, padding=0):
+    """conv2d(x, weight, padding=padding) + bias (+ ReLU), W <= 128: (C_in, C_out) = (16, 32) or (32, 32) at padding 0; (32, 32)
+    at padding 2 (notebook 11's conv.4, pv_conv2d_ae_p2_*), W + 2 <= 128."""
+    return _conv_fwd(_ae_family(padding), x, weight, bias, relu)
+
+
+def conv2d_ae_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape, padding=0):
     """dx of conv2d_ae_fwd_f32; dy zeroed where dy_gate <= 0, dx zeroed where x_gate <= 0 (either may be None)."""
-    return _conv_bwd_data(_CONV2D_AE, dy, dy_gate, weight, x_gate, x_shape)
+    return _conv_bwd_data(_ae_family(padding), dy, dy_gate, weight, x_gate, x_shape)
 
 
-def conv2d_ae_bwd_weight_f32(x, dy, dy_gate, weight_shape):
+def conv2d_ae_bwd_weight_f32(x, dy, dy_gate, weight_shape, padding=0):
     """(dw, dbias) of conv2d_ae_fwd_f32; deterministic (fixed slabs summed in order)."""
-    return _conv_bwd_weight(_CONV2D_AE, x, dy, dy_gate, weight_shape)
+    return _conv_bwd_weight(_ae_family(padding), x, dy, dy_gate, weight_shape)
 
 
 def conv2d_ae_pool_fwd_f32(x, weight, bias):
@@ -2320,6 +2341,107 @@ def convt2d_s2_frames_bwd_data_f32(dy, dy_gate, weight, x_gate, x_shape):
 def convt2d_s2_frames_bwd_weight_f32(x, dy, dy_gate, weight_shape):
     """(dw [128, 32, 3, 3], dbias [32]) of convt2d_s2_frames_fwd_f32; deterministic (fixed slabs summed in order)."""
     return _conv_bwd_weight(_CONVT2D_S2_FRAMES, x, dy, dy_gate, weight_shape)
+
+
+# ---- notebooks/11_just_conv_and_conv_over_time.ipynb: Conv2d 2 -> 16 -> 32 -> 32 (padding 2) -> 1 (stride 2, padding 2) with a
+# ReLU after each, applied to every history frame with the same weights and the forecast-horizon stripe as the second channel
+# (the frames folded into the batch, image FRAMES b + f), then three (1, 2) convolutions over the four results per pixel
+# (csrc/conv2d_ae_f32.hip, csrc/conv_time_f32.hip); planes up to 128 wide.  Layer 2 is conv2d_ae_*, layer 3 conv2d_ae_*(padding
+# = 2), layer 4 conv2d_head_s2_* on [FRAMES B, 32, ..]. ----
+FRAME_STRIPE_C_OUT = 16                           # CHANNELS // 2
+TIME_FRAMES, TIME_C = 4, 16                       # N_HIST_IMAGES, CHANNELS // 2 of temporal_conv
+TIME_PARAM_SHAPES = ((TIME_C, 1, 1, 2), (TIME_C,), (TIME_C, TIME_C, 1, 2), (TIME_C,), (1, TIME_C, 1, 2), (1,))
+
+
+def _check_frame_stripe(who, history, stripe_start, weight_shape, stripe_width):
+    """The shape rule of pv_conv2d_ae_frame_stripe_*: history [N, F, H, W] (F = 1..7), stripe_start int32 [N], weight [16, 2,
+    3, 3].  Returns the entry points' (n, frames, h, w) and the output's shape."""
+    n, frames, h, w = _check_stripe(who, history, stripe_start, stripe_width)
+    if tuple(weight_shape) != (FRAME_STRIPE_C_OUT, 2, 3, 3):
+        raise ValueError(f"{who}: weight [{FRAME_STRIPE_C_OUT}, 2, 3, 3] expected, got {tuple(weight_shape)}")
+    return (int(n), int(frames), int(h), int(w)), (n * frames, FRAME_STRIPE_C_OUT, *_CONV2D_AE.out_hw(h, w))
+
+
+def conv2d_ae_frame_stripe_fwd_f32(history, stripe_start, weight, bias, stripe_width):
+    """relu(conv2d(cat(history[:, f:f + 1], stripe plane), weight) + bias) for every frame f at once: history [N, F, H, W] f32
+    read in place, the stripe plane of example i is 1 on columns stripe_start[i] <= c < stripe_start[i] + stripe_width (inside
+    the image) -> [N F, 16, H - 2, W - 2] with image index F i + f; weight [16, 2, 3, 3]."""
+    who = "conv2d_ae_frame_stripe_fwd_f32"
+    dims, y_shape = _check_frame_stripe(who, history, stripe_start, weight.shape, stripe_width)
+    if bias is None or tuple(bias.shape) != (FRAME_STRIPE_C_OUT,):
+        raise ValueError(f"{who}: bias [{FRAME_STRIPE_C_OUT}] expected")
+    require_cuda(weight, bias)
+    _f32_contig(weight, bias)
+    y = torch.empty(y_shape, dtype=torch.float32, device=history.device)
+    check(get_lib().pv_conv2d_ae_frame_stripe_fwd_f32(ptr(history), ptr(stripe_start), ptr(weight), ptr(bias), ptr(y), *dims,
+                                                      FRAME_STRIPE_C_OUT, int(stripe_width), current_stream_ptr()),
+          "pv_" + who)
+    return y
+
+
+def conv2d_ae_frame_stripe_bwd_weight_f32(history, stripe_start, dy, weight_shape, stripe_width):
+    """(dw [16, 2, 3, 3], dbias [16]) of conv2d_ae_frame_stripe_fwd_f32's conv, summed over its frames, from its pre-activation
+    gradient dy [N F, 16, H - 2, W - 2]; deterministic."""
+    who = "conv2d_ae_frame_stripe_bwd_weight_f32"
+    dims, y_shape = _check_frame_stripe(who, history, stripe_start, weight_shape, stripe_width)
+    if tuple(dy.shape) != y_shape:
+        raise ValueError(f"{who}: dy {y_shape} expected, got {tuple(dy.shape)}")
+    require_cuda(dy)
+    _f32_contig(dy)
+    ws, nbytes = _wgrad_ws("conv2d_ae_frame_stripe", history.device, *dims)
+    dw, db = _grads_out(weight_shape, FRAME_STRIPE_C_OUT, history.device)
+    check(get_lib().pv_conv2d_ae_frame_stripe_bwd_weight_f32(ptr(history), ptr(stripe_start), ptr(dy), ptr(dw), ptr(db), *dims,
+                                                             FRAME_STRIPE_C_OUT, int(stripe_width), ptr(ws), nbytes,
+                                                             current_stream_ptr()), "pv_" + who)
+    return dw, db
+
+
+def _check_conv_time(who, u, params):
+    """The shape rule of pv_conv_time_*: u [4 N, 1, H, W] (the per-frame stack's output, image 4 i + f) and temporal_conv's six
+    parameters.  Returns the entry points' (n, frames, c_mid, p)."""
+    if u.dim() != 4 or u.shape[1] != 1 or u.shape[0] % TIME_FRAMES or u.numel() == 0:
+        raise ValueError(f"{who}: u [{TIME_FRAMES} N, 1, H, W] expected, got {tuple(u.shape)}")
+    got = tuple(tuple(t.shape) for t in params)
+    if got != TIME_PARAM_SHAPES[:len(got)]:
+        raise ValueError(f"{who}: parameters {TIME_PARAM_SHAPES[:len(got)]} expected, got {got}")
+    require_cuda(u, *params)
+    _f32_contig(u, *params)
+    return u.shape[0] // TIME_FRAMES, TIME_FRAMES, TIME_C, u.shape[2] * u.shape[3]
+
+
+def conv_time_fwd_f32(u, w1, b1, w2, b2, w3, b3):
+    """temporal_conv of notebook 11 per pixel: u [4 N, 1, H, W] f32 holds the four frames' values of example i in images 4 i ..
+    4 i + 3; conv2d (1, 2) 1 -> 16, ReLU, 16 -> 16, ReLU, 16 -> 1 over the frame axis -> [N, 1, H, W]."""
+    who = "conv_time_fwd_f32"
+    dims = _check_conv_time(who, u, (w1, b1, w2, b2, w3, b3))
+    y = torch.empty((dims[0], 1, *u.shape[2:]), dtype=torch.float32, device=u.device)
+    check(get_lib().pv_conv_time_fwd_f32(ptr(u), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(y), *dims,
+                                         current_stream_ptr()), "pv_" + who)
+    return y
+
+
+def conv_time_bwd_f32(u, dy, w1, b1, w2, b2, w3, u_is_relu_output=False):
+    """(du [4 N, 1, H, W], dw1, db1, dw2, db2, dw3, db3) of conv_time_fwd_f32 from dy [N, 1, H, W]: the hidden layers are
+    recomputed from u and gated by the recomputed values; deterministic (per-block partial sums added in order).
+    u_is_relu_output: du leaves zeroed where u <= 0 (the pre-activation gradient of the ReLU that made u)."""
+    who = "conv_time_bwd_f32"
+    dims = _check_conv_time(who, u, (w1, b1, w2, b2, w3))
+    y_shape = (dims[0], 1, *u.shape[2:])
+    if tuple(dy.shape) != y_shape:
+        raise ValueError(f"{who}: dy {y_shape} expected, got {tuple(dy.shape)}")
+    require_cuda(dy)
+    _f32_contig(dy)
+    query = "pv_conv_time_bwd_workspace_bytes"
+    nbytes = ctypes.c_size_t(0)
+    check(getattr(get_lib(), query)(*dims, ctypes.byref(nbytes)), query)
+    ws = _workspace("conv_time_bwd", nbytes.value, u.device)
+    du = torch.empty_like(u)
+    grads = tuple(torch.empty(shape, dtype=torch.float32, device=u.device) for shape in TIME_PARAM_SHAPES)
+    check(get_lib().pv_conv_time_bwd_f32(ptr(u), ptr(dy), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(du),
+                                         *(ptr(g) for g in grads), *dims, int(bool(u_is_relu_output)), ptr(ws), nbytes.value,
+                                         current_stream_ptr()),
+          "pv_" + who)
+    return (du, *grads)
 
 
 def maxpool3d_fwd_f32(x, kernel=3, stride=None, padding=0):
